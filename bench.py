@@ -11,19 +11,22 @@ X = rand(n, p), Y = rand(n, q); here the portable splitmix64 generator, filled o
 the n = 1e6 rows are sharded over the ranks (STRONG scaling, as the metric is quoted at fixed n) and every
 latent variable costs one RCCL all-reduce of [zp (p), tt].  value = nlv * steps / max-over-ranks wall time.
 
-The JSON line also carries
+A plain run sets up, warms up, times --steps fits and prints the JSON line; --dump-outputs DIR also writes what the last
+timed fit returned (dump_outputs below).  The line always carries
   roofline     : the fused sweep kernel's algorithmic bytes per launch (n_local*ld*8 + 16 n_local)
                  / its average duration measured with HIP events on the ctx stream inside the timed region,
                  against the 8 TB/s HBM3E peak;
+  collective   : (N > 1) transport and per-LV all-reduce microseconds inside the timed fits, per-rank device times.
+--full adds what takes runs of its own, after the timed region:
+  host_arrays  : (N == 1) the same fit from host arrays to a host Plsr (PCIe included);
   cpu_baseline : both CPU stand-ins of the reference's `plskern!` — the numpy/OpenBLAS restatement (the same dgemv /
                  dgemm / dgesdd Julia calls) and the C + OpenMP port of its schedule — timed on this host's cores at the
                  FULL n, two runs each; value = the faster one (rank 0, N == 1 only).
   other_configs: (N == 1) the other BASELINE.json configs that fit one GPU, run AFTER the headline's timed region: cfg4
                  plsnipals n=1e6 p=2000 q=1 nlv=50, the one-GPU share of cfg3 (bf16 storage, n=1e6), cfg5 lwplsr
                  (1000 queries x k=200) — each with value, ms_per_step and its own roofline block.
-  collective   : (N > 1) what the all-reduces cost — transport, ranks actually reached, per-LV all-reduce microseconds
-                 through RCCL and through the P2P inbox (probe on the fit's own message size + HIP-event / device-clock
-                 time inside profiled fits), prologue collectives; plus per-rank device times (min / max over ranks) and
+  collective   : (N > 1) also the probes — what the all-reduces cost through RCCL and through the P2P inbox on the
+                 fit's own message sizes, and the ranks each transport actually reached; plus
                  rank_share = the same shard fitted WITHOUT any collective on the same GPU (efficiency_vs_rank_share).
                  DESIGN.md §8 says how to read each field.
 """
@@ -304,6 +307,27 @@ def _minmax(vals):
     return {"min": float(min(vals)), "max": float(max(vals))}
 
 
+DUMP_ROWS = 65536   # rows of T and of the weights written by --dump-outputs (a fixed, seeded sample; all rows when n is smaller)
+
+
+def dump_outputs(d, k, *, T, weights, niter=None, **host):
+    """--dump-outputs: the fields of the Plsr that the timed path's last fit returned (jchemo_hip.Plsr), as float64 .npy files.
+    P, R, W, C, TT and the column statistics in full; T and the normalised weights have n rows, so only the rows listed in
+    T_rows (sorted, drawn with a fixed seed: the same rows for the same n) are written — about 14 MB at cfg2.  Under N > 1 this
+    is rank 0's shard of T and weights, and T_rows indexes that shard."""
+    os.makedirs(d, exist_ok=True)
+    n = T.shape[0]
+    rows = np.sort(np.random.default_rng(20250112).choice(n, size=min(n, DUMP_ROWS), replace=False))
+    idx = torch.from_numpy(rows).to(T.device)
+    out = {"T": T[:, :k].index_select(0, idx), "weights": weights.index_select(0, idx), "T_rows": rows}
+    out.update({name: (a[:, :k] if a.ndim == 2 else a[:k] if name == "TT" else a) for name, a in host.items()})
+    if niter is not None:
+        out["niter"] = niter[:k]
+    for name, a in out.items():
+        a = a.cpu().numpy() if isinstance(a, torch.Tensor) else a
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -323,7 +347,14 @@ def main():
     ap.add_argument("--no-host-path", action="store_true", help="skip the secondary host-arrays-in / host-Plsr-out timing")
     ap.add_argument("--no-other-configs", action="store_true", help="skip cfg4 / cfg3-share / cfg5 after the headline (N == 1)")
     ap.add_argument("--no-rank-share", action="store_true", help="N > 1: skip the collective-free fit of this rank's shard")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: host_arrays, other_configs, cpu_baseline (N == 1); collective probes and "
+                         "rank_share (N > 1).  The --no-* options above thin out a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed fit returned as DIR/<field>.npy (float64; rank 0 only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -520,6 +551,9 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=fdev)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:   # before anything below refits into the same buffers
+        dump_outputs(args.dump_outputs, got.value, T=T, weights=wn, P=P, R=R, W=W, C=Cm, TT=TT, xmeans=xm, xscales=xs, ymeans=ym, yscales=ys,
+                     niter=niter if args.algo == "plswold" else None)
 
     collective = None; ranks_stats = None; rank_share = None
     if world > 1:
@@ -538,7 +572,7 @@ def main():
         ctx.check(lib.jch_ctx_comm_info(ctx._h, C.byref(ri), C.byref(ni)))
         seen["jch_ctx_comm_info"] = {"rank": int(ri.value), "nranks": int(ni.value)}
         for name, code, ok_ in (("rccl", _lib.TRANSPORT_RCCL, (not rehearsal) and bool(rccl_ok)), ("inbox", _lib.TRANSPORT_INBOX, p2p_candidate)):
-            if not ok_:
+            if not ok_ or not args.full:         # the probes are extra runs of their own: --full only
                 probes[name] = None
                 continue
             try:
@@ -563,7 +597,7 @@ def main():
                                       "the ctx stream, so waiting for the slowest rank is included; fused inbox: wall_clock64 inside the small-state kernel); "
                                       "probe_*: 39 back-to-back all-reduces of the same message, HIP events, no compute in between"}
         # ---- this rank's shard fitted with NO communicator on the same GPU: what the fit would cost if collectives were free
-        if not args.no_rank_share:
+        if args.full and not args.no_rank_share:
             solo = J.Context(local_rank, stream="torch")
             solo.set_profiling(PROF_STRIDE if PROF_STRIDE > 1 else True)   # (the same event sampling as the timed fits)
             step(solo)
@@ -634,7 +668,7 @@ def main():
             if rank_share:
                 out["rank_share"] = rank_share
                 out["efficiency_vs_rank_share"] = rank_share["efficiency_vs_rank_share"]
-        if world == 1 and not args.no_host_path and args.algo == "plskern" and not bf16:
+        if args.full and world == 1 and not args.no_host_path and args.algo == "plskern" and not bf16:
             # SURVEY §8(d) "secondary, also reported": host arrays in -> host Plsr out (H2D of X, Y + D2H of T and the small
             # matrices inside the timed call).  PCIe-bound; never `value`.
             try:
@@ -654,7 +688,7 @@ def main():
                 del Xh, Yh
             except Exception as e:  # noqa: BLE001
                 out["host_arrays"] = {"value": None, "note": f"failed: {e}"}
-        if world == 1 and not args.no_other_configs and args.algo == "plskern" and not bf16 and (n_total, p, q, nlv) == (1_000_000, 500, 10, 25):
+        if args.full and world == 1 and not args.no_other_configs and args.algo == "plskern" and not bf16 and (n_total, p, q, nlv) == (1_000_000, 500, 10, 25):
             # the other BASELINE.json configs that fit one GPU — outside the headline's timed region, same library, same generator
             del X, Y, T, wn
             torch.cuda.empty_cache()
@@ -673,7 +707,7 @@ def main():
                 except Exception as e:  # noqa: BLE001   (never take the headline down)
                     others.append({"config": kw_.get("label", "lwplsr cfg5"), "value": None, "note": f"failed: {e}"})
             out["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(n_total, p, q, nlv, args.cpu_sample_rows or n_total)
                 if out["cpu_baseline"].get("value"):

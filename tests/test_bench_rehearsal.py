@@ -1,6 +1,6 @@
 """bench.py's multi-rank code path, executed: 3 ranks on the ONE GPU of the box (JCH_BENCH_REHEARSAL=1: gloo for the
 host-side exchange, the P2P inbox as the only transport — RCCL refuses two ranks on one device), launched exactly as the
-driver launches the N > 1 bench (`python -m torch.distributed.run ... bench.py --gpus N`).  Asserts the JSON schema of the
+driver launches the N > 1 bench (`python -m torch.distributed.run ... bench.py --gpus N --full`).  Asserts the JSON schema of the
 N > 1 line (collective block, per-rank min / max, rank-share efficiency) so that the first run on real
 xGMI is diagnosable from its one line, and that cfg3's bench code path (bf16 storage, n = 8e6 rows sharded) has run.
 What a one-GPU box cannot show — the xGMI hop and RCCL with > 1 rank — stays for the driver's scaling run."""
@@ -25,7 +25,7 @@ def _free_port():
 def _run(extra, world=3, timeout=420):
     env = dict(os.environ, JCH_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0", JCH_P2P_TIMEOUT_MS="30000")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1"] + extra
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--full"] + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

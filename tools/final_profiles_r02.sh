@@ -2,7 +2,7 @@
 # regenerates the round-2 evidence under gpurun_out/final2 (copied to profiles/r02_* afterwards by tools/collect_profiles_r02.py)
 set -x
 O=gpurun_out/final2; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 cat $O/bench.json
 export TMPDIR=/tmp; R=$PWD; cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/stats -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-path > $R/$O/stats.log 2>&1

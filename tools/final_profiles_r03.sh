@@ -2,7 +2,7 @@
 # regenerates the round-3 evidence under gpurun_out/final3 (copied to profiles/r03_* afterwards by tools/collect_profiles_r03.py)
 set -x
 O=gpurun_out/final3; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 cut -c1-400 $O/bench.json
 export TMPDIR=/tmp; R=$PWD; cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/stats -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-other-configs > $R/$O/stats.log 2>&1

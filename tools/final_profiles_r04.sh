@@ -3,7 +3,7 @@
 # part 1 (this script): bench lines + rocprofv3 kernel-trace stats; part 2: tools/final_pmc_r04.sh (counter passes)
 set -x
 O=gpurun_out/final4; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 cut -c1-300 $O/bench.json
 export TMPDIR=/tmp; R=$PWD; cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/stats -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-other-configs > $R/$O/stats.log 2>&1

@@ -3,7 +3,7 @@
 # (k_score_sums_lv), the refreshed headline; output under gpurun_out/final4b (copied to profiles/r04b_* by hand)
 set -x
 O=gpurun_out/final4b; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 cut -c1-300 $O/bench.json
 python tools/bench_accessors.py 2>/dev/null | tail -1 > $O/accessors.json; cat $O/accessors.json
 python tools/bench_gridcv.py 2>/dev/null | tail -1 > $O/gridcv.json; cat $O/gridcv.json

@@ -2,7 +2,7 @@
 # round-4 quick check on the GPU box: full -m gpu suite, headline bench, 125 k-row share, LV debug stamps
 O=gpurun_out
 timeout -k 10 700 python -m pytest tests -m gpu -q > $O/r04_gpu_tests.log 2>&1; tail -6 $O/r04_gpu_tests.log | cut -c1-300
-python bench.py --no-cpu-baseline --no-host-path > $O/r04_bench_q.json 2> $O/r04_bench_q.err
+python bench.py --full --no-cpu-baseline --no-host-path > $O/r04_bench_q.json 2> $O/r04_bench_q.err
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r04_bench_q.json').read().strip().splitlines()[-1])

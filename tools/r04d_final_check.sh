@@ -8,4 +8,4 @@ python bench.py --nlv 6 --steps 5 --warmup 2 $F > $O/bench_nlv6.json 2>$O/bench_
 python bench.py --steps 20 --warmup 5 $F > $O/bench_stride6_b.json 2>/dev/null; cut -c1-160 $O/bench_stride6_b.json
 JCH_BENCH_PROF_STRIDE=1 python bench.py --steps 20 --warmup 5 $F > $O/bench_stride1_b.json 2>/dev/null; cut -c1-160 $O/bench_stride1_b.json
 python -m pytest tests/test_bench_rehearsal.py -m gpu -x -q > $O/rehearsal.log 2>&1; tail -2 $O/rehearsal.log
-python bench.py > $O/bench_default_final.json 2> $O/bench_default_final.err; cut -c1-220 $O/bench_default_final.json
+python bench.py --full > $O/bench_default_final.json 2> $O/bench_default_final.err; cut -c1-220 $O/bench_default_final.json
