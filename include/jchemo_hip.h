@@ -313,6 +313,53 @@ JCH_API int32_t jch_score_sums_lv(jch_ctx *ctx, int32_t loc, const double *T, in
                                   const double *ymeans, const double *yscales, const double *Y, int64_t q, int64_t ldy, const double *mask,
                                   int32_t nlv_lo, int32_t nlv_hi, double *sums);
 
+/* ---- direct kernel PLS (src/dkplsr.jl:1-163): plskern on a Gram matrix built on the device -------------------------------
+ * Kernel kinds: JCH_KERN_RBF = `krbf(X, Y; gamma)` = exp(-gamma * euclsq(X, Y)) (src/kernels.jl:26-30, euclsq src/distances.jl:24-28:
+ * expanded norms clamped at 0; here on rows shifted by the column means of the second argument, which leaves the distances unchanged
+ * and removes the cancellation of the expansion); JCH_KERN_POL = `kpol(X, Y; degree, gamma, coef0)` = (gamma X Y' + coef0) raised to
+ * `degree` by degree - 1 successive multiplications (src/kernels.jl:59-70).  Float64 only; one GPU (a ctx with a communicator of
+ * more than one rank gets JCH_EINVAL). */
+#define JCH_KERN_RBF 0
+#define JCH_KERN_POL 1
+
+/* jch_kernel_gram — `krbf` / `kpol` on their own: K (m x n, ld ldk >= m) [loc] = kern(Z diag(1/zscale), X diag(1/xscale)).
+ *   Z m x p (ldz), X n x p (ldx) [loc]; zscale, xscale (p) HOST or NULL (= ones).  The train Gram (Z == X, same ld, m == n and the
+ *   same scales) computes only the tiles on or below the diagonal and stores each twice: K is bitwise symmetric and krbf's diagonal
+ *   is exactly 1.  Dot products on the f64 matrix cores; all indices 64-bit. */
+JCH_API int32_t jch_kernel_gram(jch_ctx *ctx, int32_t loc, int32_t kind, const double *Z, int64_t m, int64_t ldz, const double *zscale,
+                                const double *X, int64_t n, int64_t ldx, const double *xscale, int64_t p, double gamma, double coef0,
+                                int32_t degree, double *K, int64_t ldk);
+
+/* jch_dkplsr_fit — `dkplsr!` / `dkplsr` (src/dkplsr.jl:102-123): with desc->scal, dk_xscales = colstd(X, weights) and dk_yscales =
+ * colstd(Y, weights) (:113-116; the weights enter nowhere else), X and Y divided by them (:117-118); K = kern(X, X) (:121); then
+ * `plskern!(K, Y; nlv)` (:122) — the jch_plskern_fit path on the device, in place, WITHOUT weights (the reference passes none).
+ *   desc: n, p (columns of X), q, nlv, scal, loc, inplace (1 = `dkplsr!`: X returns scaled, Y scaled and centred, as plskern! leaves
+ *   it); dtype must be JCH_F64.  X n x p, Y n x q, weights n or NULL [loc].
+ *   Outputs of the inner fit exactly as jch_plskern_fit's with p replaced by n: T n x nlv, weights_norm n [loc]; P, R, W n x nlv,
+ *   C q x nlv, TT, xmeans, xscales (n), ymeans, yscales (q) HOST.  dk_xscales (p), dk_yscales (q) HOST: the outer scales (ones
+ *   unless scal).  K_out: a DEVICE n x n buffer (ld n) that receives the centred Gram the reference leaves in Dkplsr.K, or NULL (ctx
+ *   workspace). */
+JCH_API int32_t jch_dkplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t kind, double gamma, double coef0, int32_t degree,
+                               void *X, int64_t ldx, void *Y, int64_t ldy, const double *weights, double *K_out, double *T, double *P,
+                               double *R, double *W, double *C, double *TT, double *xmeans, double *xscales, double *ymeans,
+                               double *yscales, double *weights_norm, double *dk_xscales, double *dk_yscales, int32_t *nlv_out);
+
+/* jch_dkplsr_transform — `transform(object::Dkplsr, X; nlv)` (src/dkplsr.jl:133-137) = jch_transform on kern(scale(X, xscale),
+ * Xtrain).  jch_dkplsr_predict — `predict(object::Dkplsr, X; nlv)` (:158-163) = jch_predict on the same Gram, every block times
+ * Diagonal(dk_yscales) (NULL = ones).  X m x p (ldx), Xtrain n x p (ldxt, the model's X: already scaled), T / pred [loc]; xscale (p,
+ * the divisors of the NEW rows only; NULL = ones) and the inner model's pieces (xmeans, xscales n; R n x nlv; ymeans, yscales q;
+ * C q x nlv) HOST.  The new rows are processed in blocks so that the m x n Gram workspace stays bounded: 1 GiB per block by default,
+ * JCH_DKPLSR_QBLOCK=<rows> in the environment (read at call time) sets the block; the results do not depend on it. */
+JCH_API int32_t jch_dkplsr_transform(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, double coef0, int32_t degree, const double *X,
+                                     int64_t m, int64_t p, int64_t ldx, const double *xscale, const double *Xtrain, int64_t n,
+                                     int64_t ldxt, const double *xmeans, const double *xscales, const double *R, int32_t nlv, double *T,
+                                     int64_t ldt);
+JCH_API int32_t jch_dkplsr_predict(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, double coef0, int32_t degree, const double *X,
+                                   int64_t m, int64_t p, int64_t ldx, const double *xscale, const double *Xtrain, int64_t n, int64_t ldxt,
+                                   const double *xmeans, const double *xscales, const double *ymeans, const double *yscales,
+                                   const double *R, const double *C, int64_t q, int32_t nlv_lo, int32_t nlv_hi, const double *dk_yscales,
+                                   double *pred, int64_t ldo);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in

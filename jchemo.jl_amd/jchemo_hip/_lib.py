@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libjchemo_hip.so")
 JCH_OK, JCH_EINVAL, JCH_EHIP, JCH_ERCCL, JCH_ENOMEM, JCH_ENODEV = 0, -1, -2, -3, -4, -5
 LOC_HOST, LOC_DEVICE = 0, 1
 F64, BF16 = 0, 1
+KERN_RBF, KERN_POL = 0, 1   # include/jchemo_hip.h JCH_KERN_*
 
 SYMBOLS = (
     "jch_version", "jch_ctx_create", "jch_ctx_destroy", "jch_last_error", "jch_comm_unique_id",
@@ -28,6 +29,7 @@ SYMBOLS = (
     "jch_predict", "jch_loopback_group_create", "jch_loopback_group_destroy", "jch_ctx_comm_init_loopback",
     "jch_ctx_p2p_export", "jch_ctx_p2p_import", "jch_ctx_p2p_enable", "jch_plskern_fit_scaled", "jch_col_stats",
     "jch_ctx_get_counter", "jch_ctx_allreduce_probe", "jch_lwplsr_prepare", "jch_lwplsr_predict_prepared", "jch_lwplsr_release", "jch_lwplsr_add_query_map",
+    "jch_kernel_gram", "jch_dkplsr_fit", "jch_dkplsr_transform", "jch_dkplsr_predict",
 )
 
 
@@ -101,6 +103,12 @@ def load():
     L.jch_weighted_cov.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, dp]
     L.jch_score_sums.argtypes = [vp, i32, dp, i64, i64, i64, dp, i64, i64, dp, dp]
     L.jch_score_sums_lv.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, dp, dp, i64, i64, dp, i32, i32, dp]
+    f64 = C.c_double
+    L.jch_kernel_gram.argtypes = [vp, i32, i32, dp, i64, i64, dp, dp, i64, i64, dp, i64, f64, f64, i32, dp, i64]
+    L.jch_dkplsr_fit.argtypes = [vp, C.POINTER(PlsDesc), i32, f64, f64, i32, dp, i64, dp, i64, dp, dp] + [dp] * 13 + [C.POINTER(i32)]
+    L.jch_dkplsr_transform.argtypes = [vp, i32, i32, f64, f64, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, dp, dp, i32, dp, i64]
+    L.jch_dkplsr_predict.argtypes = [vp, i32, i32, f64, f64, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, dp, dp, dp, dp, dp, i64, i32, i32,
+                                     dp, dp, i64]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]
     L.jch_ctx_set_profiling.argtypes = [vp, i32]
     L.jch_ctx_get_profile.argtypes = [vp, C.POINTER(Profile)]

@@ -2,6 +2,7 @@
 
 Same names, argument meaning and error behaviour as Jchemo.jl (paths relative to /root/reference):
     plskern / plskern_ (= `plskern!`)      src/plskern.jl:106-178
+    dkplsr / dkplsr_ (= `dkplsr!`), krbf, kpol   src/dkplsr.jl, src/kernels.jl
     plsnipals / plsnipals_ (= `plsnipals!`) src/plsnipals.jl:31-97
     transform / coef / predict / summary    src/plskern.jl:187-260
     Plsr                                    src/plskern.jl:1-14
@@ -346,7 +347,10 @@ def _model_vec(v):
 
 
 def transform(fm: Plsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = None):
-    """src/plskern.jl:187-195: `cscale(X, xmeans, xscales) * R[:, 1:nlv]` (nlv clamped to the model's) — jch_transform."""
+    """src/plskern.jl:187-195: `cscale(X, xmeans, xscales) * R[:, 1:nlv]` (nlv clamped to the model's) — jch_transform.
+    A Dkplsr model: src/dkplsr.jl:133-137 (dkplsr_transform)."""
+    if isinstance(fm, Dkplsr):
+        return dkplsr_transform(fm, X, nlv=nlv, ctx=ctx)
     k = _nlv_arg(fm, nlv)
     if k < 1:
         raise ValueError("transform needs nlv >= 1")
@@ -377,7 +381,10 @@ def _predict_range(fm: Plsr, X, lo: int, hi: int, ctx):
 
 
 def coef(fm: Plsr, *, nlv: Optional[int] = None):
-    """src/plskern.jl:207-217 — (B p x q, int 1 x q); nlv = 0 gives B = 0.  p x q host glue."""
+    """src/plskern.jl:207-217 — (B p x q, int 1 x q); nlv = 0 gives B = 0.  p x q host glue.  Dkplsr: coef(object.fm)
+    (src/dkplsr.jl:146-148)."""
+    if isinstance(fm, Dkplsr):
+        fm = fm.fm
     k = _nlv_arg(fm, nlv)
     beta = fm.C[:, :k].T
     B = (fm.R[:, :k] / fm.xscales[:, None]) @ beta * fm.yscales[None, :]
@@ -413,6 +420,8 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
         return plslda_predict(fm, X, nlv=nlv, ctx=ctx)
     if isinstance(fm, Mbplsr):
         return mbplsr_predict(fm, X, nlv=nlv, ctx=ctx)
+    if isinstance(fm, Dkplsr):
+        return dkplsr_predict(fm, X, nlv=nlv, ctx=ctx)
     a = fm.P.shape[1]
     if nlv is None:
         rng = [a]
@@ -1290,5 +1299,206 @@ def mbplsr_predict(obj: Mbplsr, Xbl, *, nlv=None, ctx: Optional[Context] = None)
     for i, k in enumerate(rng):
         Bc[:k, i * q:(i + 1) * q] = obj.C[:, :k].T
     out = _affine(T, None, None, Bc, np.tile(obj.ymeans, len(rng)), ctx)
+    preds = [out[:, i * q:(i + 1) * q] for i in range(len(rng))]
+    return preds[0] if len(preds) == 1 else preds
+
+
+# ---------------------------------------------------------------------------------- direct kernel PLS (src/dkplsr.jl)
+_KERN_PARAMS = {"krbf": (_lib.KERN_RBF, {"gamma": 1.0}),                                        # src/kernels.jl:26-30
+                "kpol": (_lib.KERN_POL, {"degree": 1, "gamma": 1.0, "coef0": 0.0})}           # src/kernels.jl:59-70
+
+
+def _kern_args(kern: str, kwargs: dict):
+    """(kind, gamma, coef0, degree) of a kernel name and its keywords; unknown name or keyword -> ValueError."""
+    if kern not in _KERN_PARAMS:
+        raise ValueError(f"unknown kernel {kern!r} (expected 'krbf' or 'kpol')")
+    kind, defaults = _KERN_PARAMS[kern]
+    bad = set(kwargs) - set(defaults)
+    if bad:
+        raise ValueError(f"{kern}: unknown keyword(s) {sorted(bad)} (expected {sorted(defaults)})")
+    a = dict(defaults, **kwargs)
+    return kind, float(a["gamma"]), float(a.get("coef0", 0.0)), int(a.get("degree", 1))
+
+
+@dataclass
+class Dkplsr:
+    """Field names and order of the reference's `Dkplsr` (src/dkplsr.jl:1-9).  `X` is the (scaled) training X the predictions
+    are built on (same kind of array as the input), `fm` the inner `Plsr` on the Gram matrix, `K` the centred Gram as a device
+    tensor when the fit was asked to keep it (`keep_gram=True`), else None: no n x n copy goes back to the host."""
+    X: object
+    fm: Plsr
+    K: object
+    kern: str
+    xscales: np.ndarray
+    yscales: np.ndarray
+    dots: dict
+
+
+def _same_kind(A, like):
+    """A as a column-major float64 matrix of the same kind (numpy / torch on like's device) as `like`."""
+    A = ensure_mat(A)
+    if _is_torch(like):
+        if not _is_torch(A):
+            A = torch.as_tensor(np.asarray(A, dtype=np.float64), device=like.device)
+        elif A.device != like.device:
+            A = A.to(like.device)
+    elif _is_torch(A):
+        A = A.detach().cpu().numpy()
+    try:
+        _addr_ld(A)
+    except (ValueError, TypeError):
+        A = _as_colmajor_copy(A)
+    return A
+
+
+def _dkfit(X, Y, weights, nlv, kern, scal, inplace, ctx, keep_gram, kwargs) -> Dkplsr:
+    kind, gamma, coef0, degree = _kern_args(kern, kwargs)
+    dev = _is_torch(X)
+    if dev != _is_torch(Y):
+        raise TypeError("X and Y must both be host arrays or both device tensors")
+    n, p = X.shape
+    q = Y.shape[1]
+    if Y.shape[0] != n:
+        raise ValueError(f"DimensionMismatch: X has {n} rows, Y has {Y.shape[0]}")
+    device = (X.device.index or 0) if dev else 0
+    ctx = ctx or default_context(device)
+    if weights is None:
+        w_arr, w_addr = None, None
+    elif dev:
+        w_arr = (weights if _is_torch(weights) else torch.as_tensor(np.asarray(weights, dtype=np.float64), device=X.device)).to(torch.float64).contiguous()
+        w_addr = w_arr.data_ptr()
+    else:
+        w_arr = np.ascontiguousarray(np.asarray(weights.cpu() if _is_torch(weights) else weights, dtype=np.float64).reshape(-1))
+        w_addr = w_arr.ctypes.data
+    if w_arr is not None and w_arr.shape[0] != n:
+        raise ValueError(f"DimensionMismatch: weights has {w_arr.shape[0]} entries, X has {n} rows")
+    kmax = max(1, min(n, int(nlv)))
+    if dev:
+        T = colmajor_empty(n, kmax, X.device)
+        wn = torch.empty(n, dtype=torch.float64, device=X.device)
+        t_addr, wn_addr = T.data_ptr(), wn.data_ptr()
+    else:
+        T = np.empty((n, kmax), dtype=np.float64, order="F")
+        wn = np.empty(n, dtype=np.float64)
+        t_addr, wn_addr = T.ctypes.data, wn.ctypes.data
+    K = None
+    if keep_gram:
+        if torch is None:
+            raise TypeError("keep_gram=True needs torch (the Gram stays on the device)")
+        K = colmajor_empty(n, n, X.device if dev else f"cuda:{ctx.device}")
+    P = np.zeros((n, kmax), order="F"); R = np.zeros((n, kmax), order="F"); W = np.zeros((n, kmax), order="F")
+    Cm = np.zeros((q, kmax), order="F"); TT = np.zeros(kmax)
+    xm = np.empty(n); xs = np.empty(n); ym = np.empty(q); ys = np.empty(q)
+    dxs = np.empty(p); dys = np.empty(q)
+    xa, ldx = _addr_ld(X)
+    ya, ldy = _addr_ld(Y)
+    desc = PlsDesc(n=n, p=p, q=q, nlv=int(nlv), scal=int(bool(scal)), dtype=_lib.F64,
+                   loc=_lib.LOC_DEVICE if dev else _lib.LOC_HOST, inplace=int(inplace), reserved=0)
+    got = C.c_int32(0)
+    if dev:
+        torch.cuda.current_stream(X.device).synchronize()
+    elif K is not None:
+        torch.cuda.current_stream(K.device).synchronize()
+    ctx.check(_lib.load().jch_dkplsr_fit(ctx._h, C.byref(desc), kind, gamma, coef0, degree, xa, ldx, ya, ldy, w_addr,
+                                         None if K is None else K.data_ptr(), t_addr, _np(P), _np(R), _np(W), _np(Cm), _np(TT),
+                                         _np(xm), _np(xs), _np(ym), _np(ys), wn_addr, _np(dxs), _np(dys), C.byref(got)))
+    k = got.value
+    fm = Plsr(T[:, :k], P[:, :k], R[:, :k], W[:, :k], Cm[:, :k], TT[:k], xm, xs, ym, ys, wn)
+    return Dkplsr(X, fm, K, kern, dxs, dys, dict(kwargs))
+
+
+def dkplsr(X, Y, weights=None, *, nlv: int, kern: str = "krbf", scal: bool = False, ctx: Optional[Context] = None,
+           keep_gram: bool = False, **kwargs) -> Dkplsr:
+    """`dkplsr(X, Y, weights; nlv, kern = "krbf", scal = false, kwargs...)` — src/dkplsr.jl:102-106: the fit on copies of X and Y
+    (the model keeps its own, scaled, copy of X).  `kwargs` are the kernel's keywords (krbf: gamma; kpol: degree, gamma, coef0).
+    The weights only enter `colstd` when `scal` (:113-116): the inner plskern! gets none (:122)."""
+    _kern_args(kern, kwargs)
+    X = _as_colmajor_copy(X)
+    Y = ensure_mat(Y)
+    if scal:   # dkplsr! on the copies: the library scales X (and Y) in place
+        return _dkfit(X, _as_colmajor_copy(Y), weights, nlv, kern, True, True, ctx, keep_gram, kwargs)
+    try:
+        _addr_ld(Y)
+    except (ValueError, TypeError):
+        Y = _as_colmajor_copy(Y)
+    return _dkfit(X, Y, weights, nlv, kern, False, False, ctx, keep_gram, kwargs)   # (Y: the library works on a copy)
+
+
+def dkplsr_(X, Y, weights=None, *, nlv: int, kern: str = "krbf", scal: bool = False, ctx: Optional[Context] = None,
+            keep_gram: bool = False, **kwargs) -> Dkplsr:
+    """`dkplsr!(X::Matrix, Y::Matrix, ...)` — src/dkplsr.jl:108-123: with `scal`, X and Y are divided by their column stds in
+    place (:117-118); Y then ends up centred too, as `plskern!(K, Y)` (:122) leaves it.  The model refers to the caller's X."""
+    return _dkfit(_as_colmajor_view(X), _as_colmajor_view(Y), weights, nlv, kern, scal, True, ctx, keep_gram, kwargs)
+
+
+def _gram(kern, X, Y, kwargs, ctx):
+    kind, gamma, coef0, degree = _kern_args(kern, kwargs)
+    X = ensure_mat(X)
+    same = Y is X
+    X = _same_kind(X, X)
+    Y = X if same else _same_kind(Y, X)
+    m, p = X.shape
+    n = Y.shape[0]
+    if Y.shape[1] != p:
+        raise ValueError(f"DimensionMismatch: X has {p} columns, Y has {Y.shape[1]}")
+    X, out, oa, ctx, loc = _x_out(X, n, ctx)
+    xa, ldx = _addr_ld(X)
+    ya, ldy = _addr_ld(Y)
+    ctx.check(_lib.load().jch_kernel_gram(ctx._h, loc, kind, xa, m, ldx, None, ya, n, ldy, None, p, gamma, coef0, degree, oa, max(m, 1)))
+    return out
+
+
+def krbf(X, Y, *, gamma=1, ctx: Optional[Context] = None):
+    """`krbf(X, Y; gamma = 1)` — src/kernels.jl:26-30: exp.(-gamma * euclsq(X, Y)), (m, n) for X (m, p) and Y (n, p)."""
+    return _gram("krbf", X, Y, dict(gamma=gamma), ctx)
+
+
+def kpol(X, Y, *, degree=1, gamma=1, coef0=0, ctx: Optional[Context] = None):
+    """`kpol(X, Y; degree = 1, gamma = 1, coef0 = 0)` — src/kernels.jl:59-70: (gamma X Y' + coef0)^degree."""
+    return _gram("kpol", X, Y, dict(degree=degree, gamma=gamma, coef0=coef0), ctx)
+
+
+def _dk_call(obj: Dkplsr, X, k, ctx):
+    kind, gamma, coef0, degree = _kern_args(obj.kern, obj.dots)
+    X = _same_kind(X, obj.X)
+    if X.shape[1] != obj.X.shape[1]:
+        raise ValueError(f"DimensionMismatch: X has {X.shape[1]} columns, the model has {obj.X.shape[1]}")
+    X, out, oa, ctx, loc = _x_out(X, k, ctx)
+    xa, ldx = _addr_ld(X)
+    ta, ldt = _addr_ld(obj.X)
+    return (ctx, loc, kind, gamma, coef0, degree, xa, X.shape[0], X.shape[1], ldx, _np(_model_vec(obj.xscales)), ta, obj.X.shape[0], ldt), out, oa
+
+
+def dkplsr_transform(obj: Dkplsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = None):
+    """src/dkplsr.jl:133-137: `transform(fm, kern(scale(X, xscales), object.X))` — jch_dkplsr_transform (Gram blocks of the new rows)."""
+    fm = obj.fm
+    k = _nlv_arg(fm, nlv)
+    if k < 1:
+        raise ValueError("transform needs nlv >= 1")
+    args, out, oa = _dk_call(obj, X, k, ctx)
+    keep = (_model_vec(fm.xmeans), _model_vec(fm.xscales), np.asfortranarray(fm.R[:, :k], dtype=np.float64), _model_vec(obj.xscales))
+    ctx = args[0]
+    ctx.check(_lib.load().jch_dkplsr_transform(ctx._h, *args[1:], _np(keep[0]), _np(keep[1]), keep[2].ctypes.data, k, oa, max(args[7], 1)))
+    return out
+
+
+def dkplsr_predict(obj: Dkplsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Optional[Context] = None):
+    """src/dkplsr.jl:158-163: `predict(fm, kern(scale(X, xscales), object.X)).pred * Diagonal(yscales)`, one nlv (matrix) or a
+    collection (list of matrices over the contiguous range, as the Plsr predict) — jch_dkplsr_predict."""
+    fm = obj.fm
+    a = fm.P.shape[1]
+    if nlv is None:
+        rng = [a]
+    else:
+        vals = np.atleast_1d(np.asarray(nlv))
+        rng = list(range(max(0, int(vals.min())), min(a, int(vals.max())) + 1))
+    q = fm.C.shape[0]
+    lo, hi = rng[0], rng[-1]
+    args, out, oa = _dk_call(obj, X, q * (hi - lo + 1), ctx)
+    keep = [_model_vec(v) for v in (fm.xmeans, fm.xscales, fm.ymeans, fm.yscales, obj.yscales)]
+    R = np.asfortranarray(fm.R, dtype=np.float64); Cm = np.asfortranarray(fm.C, dtype=np.float64)
+    ctx = args[0]
+    ctx.check(_lib.load().jch_dkplsr_predict(ctx._h, *args[1:], _np(keep[0]), _np(keep[1]), _np(keep[2]), _np(keep[3]), R.ctypes.data,
+                                             Cm.ctypes.data, q, lo, hi, _np(keep[4]), oa, max(args[7], 1)))
     preds = [out[:, i * q:(i + 1) * q] for i in range(len(rng))]
     return preds[0] if len(preds) == 1 else preds

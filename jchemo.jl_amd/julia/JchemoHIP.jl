@@ -30,7 +30,8 @@ using LinearAlgebra
 export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!, plsrosa, plsrosa!, plswold, plswold!,
        lwplsr, transform, coef, predict, explvarx, JchCtx, attach!, nipals_one_pass!,
        msep, rmsep, ssr, bias, r2, cor2, mpar, segmkf, segmts, gridscorelv, gridcvlv,
-       Plsrda, dummy, plsrda, Mbplsr, mbplsr, vip, xfit, xresid
+       Plsrda, dummy, plsrda, Mbplsr, mbplsr, vip, xfit, xresid,
+       Dkplsr, dkplsr, dkplsr!, krbf, kpol
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -120,6 +121,9 @@ function attach!(J::Module)
     Core.eval(J, :(transform(object::$Plsr, X; nlv = nothing) = $transform(object, X; nlv = nlv)))
     Core.eval(J, :(coef(object::$Plsr; nlv = nothing) = $coef(object; nlv = nlv)))
     Core.eval(J, :(predict(object::$Plsr, X; nlv = nothing) = $predict(object, X; nlv = nlv)))
+    Core.eval(J, :(transform(object::$Dkplsr, X; nlv = nothing) = $transform(object, X; nlv = nlv)))
+    Core.eval(J, :(coef(object::$Dkplsr; nlv = nothing) = $coef(object; nlv = nlv)))
+    Core.eval(J, :(predict(object::$Dkplsr, X; nlv = nothing) = $predict(object, X; nlv = nlv)))
     J
 end
 
@@ -293,6 +297,7 @@ _nlv_fit(object) = size(object.P, 2)     # (== nco(object.T) of the reference; P
 
 "`transform(object, X; nlv)` — src/plskern.jl:187-195 on the GPU; `object`: `Jchemo.Plsr` or `JchemoHIP.Plsr`."
 function transform(object, X; nlv = nothing, ctx = default_ctx())
+    hasproperty(object, :kern) && return _transform_dkplsr(object, X, nlv, ctx)
     hasproperty(object, :lev) && return transform(object.fm, X; nlv = nlv, ctx = ctx)          # Plsrda: src/plsrda.jl:86-88
     hasproperty(object, :bscales) && return _transform_mbplsr(object, X, nlv, ctx)
     a = _nlv_fit(object)
@@ -302,6 +307,7 @@ end
 
 "`coef(object; nlv)` — src/plskern.jl:207-217 (p x q host glue, as in the reference)"
 function coef(object; nlv = nothing)
+    hasproperty(object, :kern) && return coef(object.fm; nlv = nlv)                            # Dkplsr: src/dkplsr.jl:146-148
     a = _nlv_fit(object)
     nlv = nlv === nothing ? a : min(nlv, a)
     beta = object.C[:, 1:nlv]'
@@ -333,6 +339,7 @@ function predict(object, X; nlv = nothing, ctx = default_ctx())
     hasproperty(object, :metric) && return _predict_lwplsr(object, X, nlv, ctx)
     hasproperty(object, :lev) && return _predict_plsrda(object, X, nlv, ctx)
     hasproperty(object, :bscales) && return _predict_mbplsr(object, X, nlv, ctx)
+    hasproperty(object, :kern) && return _predict_dkplsr(object, X, nlv, ctx)
     a = _nlv_fit(object); q = size(object.C, 1)
     rng = nlv === nothing ? (a:a) : (max(0, minimum(nlv)):min(a, maximum(nlv)))
     out = _predict_range(object, X, first(rng), last(rng), ctx)
@@ -832,6 +839,121 @@ function xresid(object, X; nlv = nothing, ctx = default_ctx())
     a = _nlv_fit(object); k = nlv === nothing ? a : min(nlv, a); p = size(object.P, 1)
     M = Matrix{Float64}(I, p, p) - object.R[:, 1:k] * object.P[:, 1:k]'
     _affine(X, object.xmeans, object.xscales, M .* object.xscales', nothing, ctx)
+end
+
+# ---- direct kernel PLS (src/dkplsr.jl): plskern! on a Gram matrix built on the device (include/jchemo_hip.h jch_dkplsr_*) ---------
+struct Dkplsr                     # fallback record, fields of the reference's struct (src/dkplsr.jl:1-9); K is an empty matrix:
+    X                             # the n x n Gram stays in the library's device workspace
+    fm
+    K::Matrix{Float64}
+    kern
+    xscales::Vector{Float64}
+    yscales::Vector{Float64}
+    dots
+end
+
+const _KERNS = Dict("krbf" => (Int32(0), (:gamma,)), "kpol" => (Int32(1), (:degree, :gamma, :coef0)))   # JCH_KERN_RBF / JCH_KERN_POL
+
+# (kind, gamma, coef0, degree) of a kernel name and its keywords (defaults of src/kernels.jl:26, :59)
+function _kern_args(kern, dots)
+    haskey(_KERNS, kern) || throw(ArgumentError("unknown kernel \"$kern\" (krbf or kpol)"))
+    kind, names = _KERNS[kern]
+    for k in keys(dots)
+        k in names || throw(ArgumentError("$kern: unknown keyword $k"))
+    end
+    (kind, Float64(get(dots, :gamma, 1)), Float64(get(dots, :coef0, 0)), Int32(get(dots, :degree, 1)))
+end
+
+function _gram(kern, X, Y, dots, ctx)
+    kind, gamma, coef0, degree = _kern_args(kern, dots)
+    same = X === Y
+    X = _in(X); Y = same ? X : _in(Y)
+    m, p = size(X); n = size(Y, 1)
+    size(Y, 2) == p || throw(DimensionMismatch("X has $p columns, Y has $(size(Y, 2))"))
+    K = _similar(X, m, n)
+    GC.@preserve X Y K check(ctx, ccall((:jch_kernel_gram, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Float64,
+         Float64, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), kind, pointer(X), m, stride(X, 2), Ptr{Float64}(C_NULL), pointer(Y), n, stride(Y, 2), Ptr{Float64}(C_NULL), p,
+        gamma, coef0, degree, pointer(K), max(m, 1)))
+    K
+end
+
+"`krbf(X, Y; gamma = 1)` — src/kernels.jl:26-30 on the GPU."
+krbf(X, Y; gamma = 1, ctx = default_ctx()) = _gram("krbf", X, Y, (gamma = gamma,), ctx)
+"`kpol(X, Y; degree = 1, gamma = 1, coef0 = 0)` — src/kernels.jl:59-70 on the GPU."
+kpol(X, Y; degree = 1, gamma = 1, coef0 = 0, ctx = default_ctx()) = _gram("kpol", X, Y, (degree = degree, gamma = gamma, coef0 = coef0), ctx)
+
+"`dkplsr(X, Y, weights; nlv, kern = \"krbf\", scal = false, kwargs...)` — src/dkplsr.jl:102-106 (on copies of X and Y)."
+dkplsr(X, Y, weights = nothing; nlv, kern = "krbf", scal = false, ctx = default_ctx(), kwargs...) =
+    dkplsr!(copy(_in(X)), copy(_in(Y)), weights; nlv = nlv, kern = kern, scal = scal, ctx = ctx, kwargs...)
+
+"""`dkplsr!(X, Y, weights; nlv, kern = "krbf", scal = false, kwargs...)` — src/dkplsr.jl:108-123: with `scal`, X and Y are divided by
+their weighted column stds in place; K = kern(X, X) and `plskern!(K, Y; nlv)` (no weights) run on the device (Y ends up centred, as
+plskern! leaves it)."""
+function dkplsr!(X, Y, weights = nothing; nlv, kern = "krbf", scal = false, ctx = default_ctx(), kwargs...)
+    kind, gamma, coef0, degree = _kern_args(kern, kwargs)
+    X = ensure_mat(X); Y = ensure_mat(Y)
+    n, p = size(X); q = size(Y, 2)
+    size(Y, 1) == n || throw(DimensionMismatch("X has $n rows, Y has $(size(Y, 1))"))
+    weights = _w(weights, X)
+    kmax = max(1, min(n, nlv))
+    T = _similar(X, n, kmax); wn = _similar(X, n)
+    P = zeros(n, kmax); R = zeros(n, kmax); W = zeros(n, kmax); C = zeros(q, kmax); TT = zeros(kmax)
+    xm = zeros(n); xs = zeros(n); ym = zeros(q); ys = zeros(q); dxs = ones(p); dys = ones(q); got = Ref{Int32}(0)
+    desc = Ref(PlsDesc(n, p, q, nlv, scal ? 1 : 0, 0, _loc(X), 1, 0))
+    GC.@preserve X Y weights T wn check(ctx, ccall((:jch_dkplsr_fit, LIB), Int32,
+        (Ptr{Cvoid}, Ref{PlsDesc}, Int32, Float64, Float64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+        ctx.h, desc, kind, gamma, coef0, degree, pointer(X), stride(X, 2), pointer(Y), max(stride(Y, 2), n),
+        weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights), Ptr{Float64}(C_NULL), pointer(T), P, R, W, C, TT, xm, xs, ym, ys,
+        pointer(wn), dxs, dys, got))
+    k = Int(got[])
+    cut(A) = k == size(A, 2) ? A : A[:, 1:k]
+    fm = _record(cut(T), cut(P), cut(R), cut(W), cut(C), k == length(TT) ? TT : TT[1:k], xm, xs, ym, ys, wn, nothing)
+    J = jchemo_module()
+    if J !== nothing && X isa Matrix{Float64} && fm isa getfield(J, :Plsr)
+        return Base.invokelatest(getfield(J, :Dkplsr), X, fm, zeros(0, 0), kern, dxs, dys, kwargs)
+    end
+    Dkplsr(X, fm, zeros(0, 0), kern, dxs, dys, kwargs)
+end
+
+function _transform_dkplsr(object, X, nlv, ctx)
+    kind, gamma, coef0, degree = _kern_args(object.kern, object.dots)
+    fm = object.fm; a = _nlv_fit(fm)
+    nlv = nlv === nothing ? a : min(nlv, a)
+    X = _in(X); Xt = object.X; m, p = size(X); n = size(Xt, 1)
+    out = _similar(X, m, nlv)
+    R = Matrix{Float64}(fm.R); xm = Vector{Float64}(vec(fm.xmeans)); xs = Vector{Float64}(vec(fm.xscales))
+    dxs = Vector{Float64}(object.xscales)
+    GC.@preserve X Xt out R xm xs dxs check(ctx, ccall((:jch_dkplsr_transform, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), m, p, stride(X, 2), pointer(dxs), pointer(Xt), n, stride(Xt, 2),
+        pointer(xm), pointer(xs), pointer(R), nlv, pointer(out), max(m, 1)))
+    out
+end
+
+function _predict_dkplsr(object, X, nlv, ctx)
+    kind, gamma, coef0, degree = _kern_args(object.kern, object.dots)
+    fm = object.fm; a = _nlv_fit(fm); q = size(fm.C, 1)
+    rng = nlv === nothing ? (a:a) : (max(0, minimum(nlv)):min(a, maximum(nlv)))
+    X = _in(X); Xt = object.X; m, p = size(X); n = size(Xt, 1)
+    out = _similar(X, m, q * length(rng))
+    R = Matrix{Float64}(fm.R); Cm = Matrix{Float64}(fm.C)
+    xm = Vector{Float64}(vec(fm.xmeans)); xs = Vector{Float64}(vec(fm.xscales))
+    ym = Vector{Float64}(vec(fm.ymeans)); ys = Vector{Float64}(vec(fm.yscales))
+    dxs = Vector{Float64}(object.xscales); dys = Vector{Float64}(object.yscales)
+    GC.@preserve X Xt out R Cm xm xs ym ys dxs dys check(ctx, ccall((:jch_dkplsr_predict, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64},
+         Ptr{Float64}, Int64),
+        ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), m, p, stride(X, 2), pointer(dxs), pointer(Xt), n, stride(Xt, 2),
+        pointer(xm), pointer(xs), pointer(ym), pointer(ys), pointer(R), pointer(Cm), q, first(rng), last(rng), pointer(dys),
+        pointer(out), max(m, 1)))
+    pred = [out[:, (i - 1) * q + 1:i * q] for i in 1:length(rng)]
+    (pred = length(rng) == 1 ? pred[1] : pred,)
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
