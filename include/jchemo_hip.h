@@ -360,6 +360,38 @@ JCH_API int32_t jch_dkplsr_predict(jch_ctx *ctx, int32_t loc, int32_t kind, doub
                                    const double *R, const double *C, int64_t q, int32_t nlv_lo, int32_t nlv_hi, const double *dk_yscales,
                                    double *pred, int64_t ldo);
 
+/* ---- kernel NIPALS PLS (src/kplsr.jl:1-250, Rosipal & Trejo 2001) on a Gram matrix built on the device ----------------------
+ * jch_kplsr_fit — `kplsr!` / `kplsr` (src/kplsr.jl:119-193): w = mweight(weights) (:124); ymeans = colmean(Y, w); with desc->scal
+ * xscales = colstd(X, w) and yscales = colstd(Y, w), X DIVIDED only and Y centred and scaled, else Y centred (:125-135);
+ * K = kern(X, X) (:137); Kc = K - vtot 1' - 1 vtot' + w'Kw with vtot = K w (:138-142); the NIPALS LV loop (:157-188) with tol and
+ * maxit (q > 1 only; iter[a] = 0 when q == 1); R = DU inv(T' D Kc DU) (:189-190).  The deflation K .= z*K*z' (:182-183) is
+ * postponed: every LV reads Kc once against an n x q panel projected with the previous LVs' z_i.
+ *   desc: n, p (columns of X), q (<= 1024), nlv, scal, loc, inplace (1 = `kplsr!`: X returns scaled when scal, Y centred / scaled
+ *   AND deflated, as the reference leaves it); dtype must be JCH_F64.  X n x p, Y n x q, weights n or NULL [loc].
+ *   nlv is clamped to n (the reference does not clamp: it allocates n x nlv and runs every LV); *nlv_out = min(n, nlv).
+ *   Outputs: T, U, R n x nlv (ld n), vtot n, weights_norm n [loc]; C q x nlv, xscales p, ymeans q, yscales q, iter nlv HOST; any may be
+ *   NULL.  K_out: a DEVICE n x n buffer (ld n) that receives the UNcentred Gram (the reference's Kplsr.Kt), or NULL.  The centred
+ *   Gram lives in ctx workspace (n^2 doubles); a Gram that does not fit returns JCH_ENOMEM.  Float64 only; one GPU. */
+JCH_API int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t kind, double gamma, double coef0, int32_t degree, double tol,
+                              int32_t maxit, void *X, int64_t ldx, void *Y, int64_t ldy, const double *weights, double *K_out, double *T,
+                              double *U, double *R, double *vtot, double *C, double *xscales, double *ymeans, double *yscales,
+                              double *weights_norm, int32_t *iter, int32_t *nlv_out);
+
+/* jch_kplsr_transform — `transform(object::Kplsr, X; nlv)` (src/kplsr.jl:202-212): Knew = kern(scale(X, xscales), Xtrain),
+ * Kc_new = Knew - vnew 1' - 1 vtot' + weights . vtot with vnew = Knew weights, T = Kc_new R[:, 1:nlv].  jch_kplsr_predict —
+ * `predict(object::Kplsr, X; nlv)` (:238-250 through coef :221-228) for every nlv in [nlv_lo, nlv_hi], laid out as jch_predict's:
+ * ymeans + Kc_new R[:, 1:a] C[:, 1:a]' diag(yscales).  X m x p (ldx), Xtrain n x p (ldxt, the model's X: already scaled), T / pred
+ * [loc]; xscales (p, NULL = ones), weights (the normalised weights, n), vtot (n), R (n x nlv, ld n), ymeans, yscales (q), C (q x nlv)
+ * HOST.  The new rows are processed in Gram blocks of 1 GiB by default; JCH_KPLSR_QBLOCK=<rows> in the environment (read at call
+ * time) sets the block; the results do not depend on it. */
+JCH_API int32_t jch_kplsr_transform(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, double coef0, int32_t degree, const double *X,
+                                    int64_t m, int64_t p, int64_t ldx, const double *xscales, const double *Xtrain, int64_t n, int64_t ldxt,
+                                    const double *weights, const double *vtot, const double *R, int32_t nlv, double *T, int64_t ldt);
+JCH_API int32_t jch_kplsr_predict(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, double coef0, int32_t degree, const double *X,
+                                  int64_t m, int64_t p, int64_t ldx, const double *xscales, const double *Xtrain, int64_t n, int64_t ldxt,
+                                  const double *weights, const double *vtot, const double *ymeans, const double *yscales, const double *R,
+                                  const double *C, int64_t q, int32_t nlv_lo, int32_t nlv_hi, double *pred, int64_t ldo);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in

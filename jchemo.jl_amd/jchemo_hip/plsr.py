@@ -3,6 +3,7 @@
 Same names, argument meaning and error behaviour as Jchemo.jl (paths relative to /root/reference):
     plskern / plskern_ (= `plskern!`)      src/plskern.jl:106-178
     dkplsr / dkplsr_ (= `dkplsr!`), krbf, kpol   src/dkplsr.jl, src/kernels.jl
+    kplsr / kplsr_ (= `kplsr!`)            src/kplsr.jl
     plsnipals / plsnipals_ (= `plsnipals!`) src/plsnipals.jl:31-97
     transform / coef / predict / summary    src/plskern.jl:187-260
     Plsr                                    src/plskern.jl:1-14
@@ -348,9 +349,11 @@ def _model_vec(v):
 
 def transform(fm: Plsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = None):
     """src/plskern.jl:187-195: `cscale(X, xmeans, xscales) * R[:, 1:nlv]` (nlv clamped to the model's) — jch_transform.
-    A Dkplsr model: src/dkplsr.jl:133-137 (dkplsr_transform)."""
+    A Dkplsr model: src/dkplsr.jl:133-137 (dkplsr_transform).  A Kplsr model: src/kplsr.jl:202-212 (kplsr_transform)."""
     if isinstance(fm, Dkplsr):
         return dkplsr_transform(fm, X, nlv=nlv, ctx=ctx)
+    if isinstance(fm, Kplsr):
+        return kplsr_transform(fm, X, nlv=nlv, ctx=ctx)
     k = _nlv_arg(fm, nlv)
     if k < 1:
         raise ValueError("transform needs nlv >= 1")
@@ -382,7 +385,9 @@ def _predict_range(fm: Plsr, X, lo: int, hi: int, ctx):
 
 def coef(fm: Plsr, *, nlv: Optional[int] = None):
     """src/plskern.jl:207-217 — (B p x q, int 1 x q); nlv = 0 gives B = 0.  p x q host glue.  Dkplsr: coef(object.fm)
-    (src/dkplsr.jl:146-148)."""
+    (src/dkplsr.jl:146-148).  Kplsr: (beta = C[:, 1:nlv]', int = ymeans') (src/kplsr.jl:221-228)."""
+    if isinstance(fm, Kplsr):
+        return kplsr_coef(fm, nlv=nlv)
     if isinstance(fm, Dkplsr):
         fm = fm.fm
     k = _nlv_arg(fm, nlv)
@@ -422,6 +427,8 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
         return mbplsr_predict(fm, X, nlv=nlv, ctx=ctx)
     if isinstance(fm, Dkplsr):
         return dkplsr_predict(fm, X, nlv=nlv, ctx=ctx)
+    if isinstance(fm, Kplsr):
+        return kplsr_predict(fm, X, nlv=nlv, ctx=ctx)
     a = fm.P.shape[1]
     if nlv is None:
         rng = [a]
@@ -1500,5 +1507,170 @@ def dkplsr_predict(obj: Dkplsr, X, *, nlv: Union[None, int, Sequence[int]] = Non
     ctx = args[0]
     ctx.check(_lib.load().jch_dkplsr_predict(ctx._h, *args[1:], _np(keep[0]), _np(keep[1]), _np(keep[2]), _np(keep[3]), R.ctypes.data,
                                              Cm.ctypes.data, q, lo, hi, _np(keep[4]), oa, max(args[7], 1)))
+    preds = [out[:, i * q:(i + 1) * q] for i in range(len(rng))]
+    return preds[0] if len(preds) == 1 else preds
+
+
+@dataclass
+class Kplsr:
+    """Field names and order of the reference's `Kplsr` (src/kplsr.jl:1-18).  `X` is the (scaled) training X the predictions are
+    built on; T, U, R (n x nlv) and vtot (1 x n) live where X lives; C (q x nlv), the scales and means are host arrays.  `Kt` is the
+    uncentred Gram as a device tensor when the fit was asked to keep it (`keep_gram=True`), else None.  `D` holds the weight vector
+    (the diagonal of the reference's Diagonal(weights)); `DKt` is always None: its only use, sum(D * DKt'), equals weights . vtot."""
+    X: object
+    Kt: object
+    T: object
+    C: np.ndarray
+    U: object
+    R: object
+    D: object
+    DKt: object
+    vtot: object
+    xscales: np.ndarray
+    ymeans: np.ndarray
+    yscales: np.ndarray
+    weights: object
+    kern: str
+    dots: dict
+    iter: np.ndarray
+
+
+def _kpfit(X, Y, weights, nlv, kern, tol, maxit, scal, inplace, ctx, keep_gram, kwargs) -> Kplsr:
+    kind, gamma, coef0, degree = _kern_args(kern, kwargs)
+    if int(nlv) < 1:
+        raise ValueError(f"nlv = {nlv} must be >= 1")
+    if int(maxit) < 1:
+        raise ValueError(f"maxit = {maxit} must be >= 1")
+    dev = _is_torch(X)
+    if dev != _is_torch(Y):
+        raise TypeError("X and Y must both be host arrays or both device tensors")
+    n, p = X.shape
+    q = Y.shape[1]
+    if Y.shape[0] != n:
+        raise ValueError(f"DimensionMismatch: X has {n} rows, Y has {Y.shape[0]}")
+    device = (X.device.index or 0) if dev else 0
+    ctx = ctx or default_context(device)
+    if weights is None:
+        w_arr, w_addr = None, None
+    elif dev:
+        w_arr = (weights if _is_torch(weights) else torch.as_tensor(np.asarray(weights, dtype=np.float64), device=X.device)).to(torch.float64).contiguous()
+        w_addr = w_arr.data_ptr()
+    else:
+        w_arr = np.ascontiguousarray(np.asarray(weights.cpu() if _is_torch(weights) else weights, dtype=np.float64).reshape(-1))
+        w_addr = w_arr.ctypes.data
+    if w_arr is not None and w_arr.shape[0] != n:
+        raise ValueError(f"DimensionMismatch: weights has {w_arr.shape[0]} entries, X has {n} rows")
+    kmax = min(n, int(nlv))
+    if dev:
+        T, U, R = (colmajor_empty(n, kmax, X.device) for _ in range(3))
+        vt = torch.empty((1, n), dtype=torch.float64, device=X.device)
+        wn = torch.empty(n, dtype=torch.float64, device=X.device)
+        addrs = [a.data_ptr() for a in (T, U, R, vt)]
+        wn_addr = wn.data_ptr()
+    else:
+        T, U, R = (np.empty((n, kmax), dtype=np.float64, order="F") for _ in range(3))
+        vt = np.empty((1, n), dtype=np.float64)
+        wn = np.empty(n, dtype=np.float64)
+        addrs = [a.ctypes.data for a in (T, U, R, vt)]
+        wn_addr = wn.ctypes.data
+    K = None
+    if keep_gram:
+        if torch is None:
+            raise TypeError("keep_gram=True needs torch (the Gram stays on the device)")
+        K = colmajor_empty(n, n, X.device if dev else f"cuda:{ctx.device}")
+    Cm = np.zeros((q, kmax), order="F")
+    xs = np.empty(p); ym = np.empty(q); ys = np.empty(q)
+    it = np.zeros(kmax, dtype=np.int32)
+    xa, ldx = _addr_ld(X)
+    ya, ldy = _addr_ld(Y)
+    desc = PlsDesc(n=n, p=p, q=q, nlv=int(nlv), scal=int(bool(scal)), dtype=_lib.F64,
+                   loc=_lib.LOC_DEVICE if dev else _lib.LOC_HOST, inplace=int(inplace), reserved=0)
+    got = C.c_int32(0)
+    if dev:
+        torch.cuda.current_stream(X.device).synchronize()
+    elif K is not None:
+        torch.cuda.current_stream(K.device).synchronize()
+    ctx.check(_lib.load().jch_kplsr_fit(ctx._h, C.byref(desc), kind, gamma, coef0, degree, float(tol), int(maxit), xa, ldx, ya, ldy, w_addr,
+                                        None if K is None else K.data_ptr(), *addrs, _np(Cm), _np(xs), _np(ym), _np(ys), wn_addr,
+                                        it.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(got)))
+    return Kplsr(X, K, T, Cm, U, R, wn, None, vt, xs, ym, ys, wn, kern, dict(kwargs), it.astype(np.int64))
+
+
+def kplsr(X, Y, weights=None, *, nlv: int, kern: str = "krbf", tol: float = 1.5e-8, maxit: int = 100, scal: bool = False,
+          ctx: Optional[Context] = None, keep_gram: bool = False, **kwargs) -> Kplsr:
+    """`kplsr(X, Y, weights; nlv, kern = "krbf", tol = 1.5e-8, maxit = 100, scal = false, kwargs...)` — src/kplsr.jl:111-117: the
+    fit on copies of X and Y (the model keeps its own, scaled when `scal`, copy of X; the inputs are left untouched).  `kwargs` are
+    the kernel's keywords (krbf: gamma; kpol: degree, gamma, coef0).  nlv is clamped to n (the reference does not clamp)."""
+    _kern_args(kern, kwargs)
+    return _kpfit(_as_colmajor_copy(X), _as_colmajor_copy(Y), weights, nlv, kern, tol, maxit, scal, True, ctx, keep_gram, kwargs)
+
+
+def kplsr_(X, Y, weights=None, *, nlv: int, kern: str = "krbf", tol: float = 1.5e-8, maxit: int = 100, scal: bool = False,
+           ctx: Optional[Context] = None, keep_gram: bool = False, **kwargs) -> Kplsr:
+    """`kplsr!(X::Matrix, Y::Matrix, ...)` — src/kplsr.jl:119-193: with `scal`, X is divided by its column stds in place (:131);
+    Y comes back centred (and scaled) AND deflated by every LV (:184), as the reference leaves it.  The model refers to the caller's X."""
+    return _kpfit(_as_colmajor_view(X), _as_colmajor_view(Y), weights, nlv, kern, tol, maxit, scal, True, ctx, keep_gram, kwargs)
+
+
+def _kp_call(obj: Kplsr, X, k, ctx):
+    kind, gamma, coef0, degree = _kern_args(obj.kern, obj.dots)
+    X = _same_kind(X, obj.X)
+    if X.shape[1] != obj.X.shape[1]:
+        raise ValueError(f"DimensionMismatch: X has {X.shape[1]} columns, the model has {obj.X.shape[1]}")
+    X, out, oa, ctx, loc = _x_out(X, k, ctx)
+    xa, ldx = _addr_ld(X)
+    ta, ldt = _addr_ld(obj.X)
+    keep = (_model_vec(obj.xscales), _model_vec(_np_host(obj.weights)), _model_vec(_np_host(obj.vtot).reshape(-1)), X)   # (X: a copy
+    # that _same_kind / _x_out may have made must outlive the library call that reads it)
+    args = (ctx, loc, kind, gamma, coef0, degree, xa, X.shape[0], X.shape[1], ldx, _np(keep[0]), ta, obj.X.shape[0], ldt,
+            _np(keep[1]), _np(keep[2]))
+    return args, out, oa, keep
+
+
+def _np_host(a):
+    return a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a)
+
+
+def _kp_nlv(obj: Kplsr, nlv) -> int:
+    a = obj.T.shape[1]
+    return a if nlv is None else min(int(nlv), a)
+
+
+def kplsr_transform(obj: Kplsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = None):
+    """src/kplsr.jl:202-212: Kc = K - vnew 1' - 1 vtot' + weights . vtot with K = kern(scale(X, xscales), object.X),
+    T = Kc R[:, 1:nlv] — jch_kplsr_transform (Gram blocks of the new rows)."""
+    k = _kp_nlv(obj, nlv)
+    if k < 1:
+        raise ValueError("transform needs nlv >= 1")
+    args, out, oa, keep = _kp_call(obj, X, k, ctx)
+    R = np.asfortranarray(_np_host(obj.R)[:, :k], dtype=np.float64)
+    ctx = args[0]
+    ctx.check(_lib.load().jch_kplsr_transform(ctx._h, *args[1:], R.ctypes.data, k, oa, max(args[7], 1)))
+    return out
+
+
+def kplsr_coef(obj: Kplsr, *, nlv: Optional[int] = None):
+    """src/kplsr.jl:221-228: (beta = C[:, 1:nlv]', int = ymeans')."""
+    k = _kp_nlv(obj, nlv)
+    return obj.C[:, :k].T, obj.ymeans.reshape(1, -1)
+
+
+def kplsr_predict(obj: Kplsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Optional[Context] = None):
+    """src/kplsr.jl:238-250: ymeans + T[:, 1:a] C[:, 1:a]' diag(yscales) for one nlv (matrix) or a collection (list of matrices over
+    the contiguous range max(0, min):min(a, max), as the Plsr predict) — jch_kplsr_predict, all levels from one Gram pass."""
+    a = obj.T.shape[1]
+    if nlv is None:
+        rng = [a]
+    else:
+        vals = np.atleast_1d(np.asarray(nlv))
+        rng = list(range(max(0, int(vals.min())), min(a, int(vals.max())) + 1))
+    q = obj.C.shape[0]
+    lo, hi = rng[0], rng[-1]
+    args, out, oa, keep = _kp_call(obj, X, q * (hi - lo + 1), ctx)
+    R = np.asfortranarray(_np_host(obj.R), dtype=np.float64); Cm = np.asfortranarray(obj.C, dtype=np.float64)
+    ym, ys = _model_vec(obj.ymeans), _model_vec(obj.yscales)
+    ctx = args[0]
+    ctx.check(_lib.load().jch_kplsr_predict(ctx._h, *args[1:], _np(ym), _np(ys), R.ctypes.data, Cm.ctypes.data, q, lo, hi, oa,
+                                            max(args[7], 1)))
     preds = [out[:, i * q:(i + 1) * q] for i in range(len(rng))]
     return preds[0] if len(preds) == 1 else preds

@@ -31,7 +31,7 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        lwplsr, transform, coef, predict, explvarx, JchCtx, attach!, nipals_one_pass!,
        msep, rmsep, ssr, bias, r2, cor2, mpar, segmkf, segmts, gridscorelv, gridcvlv,
        Plsrda, dummy, plsrda, Mbplsr, mbplsr, vip, xfit, xresid,
-       Dkplsr, dkplsr, dkplsr!, krbf, kpol
+       Dkplsr, dkplsr, dkplsr!, krbf, kpol, Kplsr, kplsr, kplsr!
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -124,6 +124,11 @@ function attach!(J::Module)
     Core.eval(J, :(transform(object::$Dkplsr, X; nlv = nothing) = $transform(object, X; nlv = nlv)))
     Core.eval(J, :(coef(object::$Dkplsr; nlv = nothing) = $coef(object; nlv = nlv)))
     Core.eval(J, :(predict(object::$Dkplsr, X; nlv = nothing) = $predict(object, X; nlv = nlv)))
+    for K in (Kplsr, getfield(J, :Kplsr))   # the fallback record and the reference's own (Kt / DKt empty, D = the weights)
+        Core.eval(J, :(transform(object::$K, X; nlv = nothing) = $transform(object, X; nlv = nlv)))
+        Core.eval(J, :(coef(object::$K; nlv = nothing) = $coef(object; nlv = nlv)))
+        Core.eval(J, :(predict(object::$K, X; nlv = nothing) = $predict(object, X; nlv = nlv)))
+    end
     J
 end
 
@@ -297,6 +302,7 @@ _nlv_fit(object) = size(object.P, 2)     # (== nco(object.T) of the reference; P
 
 "`transform(object, X; nlv)` — src/plskern.jl:187-195 on the GPU; `object`: `Jchemo.Plsr` or `JchemoHIP.Plsr`."
 function transform(object, X; nlv = nothing, ctx = default_ctx())
+    hasproperty(object, :vtot) && return _transform_kplsr(object, X, nlv, ctx)
     hasproperty(object, :kern) && return _transform_dkplsr(object, X, nlv, ctx)
     hasproperty(object, :lev) && return transform(object.fm, X; nlv = nlv, ctx = ctx)          # Plsrda: src/plsrda.jl:86-88
     hasproperty(object, :bscales) && return _transform_mbplsr(object, X, nlv, ctx)
@@ -307,6 +313,7 @@ end
 
 "`coef(object; nlv)` — src/plskern.jl:207-217 (p x q host glue, as in the reference)"
 function coef(object; nlv = nothing)
+    hasproperty(object, :vtot) && return _coef_kplsr(object, nlv)
     hasproperty(object, :kern) && return coef(object.fm; nlv = nlv)                            # Dkplsr: src/dkplsr.jl:146-148
     a = _nlv_fit(object)
     nlv = nlv === nothing ? a : min(nlv, a)
@@ -339,6 +346,7 @@ function predict(object, X; nlv = nothing, ctx = default_ctx())
     hasproperty(object, :metric) && return _predict_lwplsr(object, X, nlv, ctx)
     hasproperty(object, :lev) && return _predict_plsrda(object, X, nlv, ctx)
     hasproperty(object, :bscales) && return _predict_mbplsr(object, X, nlv, ctx)
+    hasproperty(object, :vtot) && return _predict_kplsr(object, X, nlv, ctx)
     hasproperty(object, :kern) && return _predict_dkplsr(object, X, nlv, ctx)
     a = _nlv_fit(object); q = size(object.C, 1)
     rng = nlv === nothing ? (a:a) : (max(0, minimum(nlv)):min(a, maximum(nlv)))
@@ -952,6 +960,100 @@ function _predict_dkplsr(object, X, nlv, ctx)
         ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), m, p, stride(X, 2), pointer(dxs), pointer(Xt), n, stride(Xt, 2),
         pointer(xm), pointer(xs), pointer(ym), pointer(ys), pointer(R), pointer(Cm), q, first(rng), last(rng), pointer(dys),
         pointer(out), max(m, 1)))
+    pred = [out[:, (i - 1) * q + 1:i * q] for i in 1:length(rng)]
+    (pred = length(rng) == 1 ? pred[1] : pred,)
+end
+
+# ---- kernel NIPALS PLS (src/kplsr.jl): one pass over the centred Gram per LV on the device (include/jchemo_hip.h jch_kplsr_*) ------
+struct Kplsr                      # fallback record, fields of the reference's struct (src/kplsr.jl:1-18); Kt and DKt are empty
+    X                             # matrices (the Gram stays in the library's device workspace), D holds the weight vector
+    Kt::Matrix{Float64}
+    T
+    C::Matrix{Float64}
+    U
+    R
+    D
+    DKt::Matrix{Float64}
+    vtot
+    xscales::Vector{Float64}
+    ymeans::Vector{Float64}
+    yscales::Vector{Float64}
+    weights
+    kern
+    dots
+    iter::Vector{Int}
+end
+
+"`kplsr(X, Y, weights; nlv, kern = \"krbf\", tol = 1.5e-8, maxit = 100, scal = false, kwargs...)` — src/kplsr.jl:111-117 (on copies)."
+kplsr(X, Y, weights = nothing; nlv, kern = "krbf", tol = 1.5e-8, maxit = 100, scal = false, ctx = default_ctx(), kwargs...) =
+    kplsr!(copy(_in(X)), copy(_in(Y)), weights; nlv = nlv, kern = kern, tol = tol, maxit = maxit, scal = scal, ctx = ctx, kwargs...)
+
+"""`kplsr!(X, Y, weights; nlv, kern = "krbf", tol = 1.5e-8, maxit = 100, scal = false, kwargs...)` — src/kplsr.jl:119-193: with `scal`,
+X is divided by its weighted column stds in place; Y comes back centred (and scaled) and deflated, as the reference leaves it.  The
+Gram, its centring and the NIPALS loop run on the device; nlv is clamped to n (the reference does not clamp)."""
+function kplsr!(X, Y, weights = nothing; nlv, kern = "krbf", tol = 1.5e-8, maxit = 100, scal = false, ctx = default_ctx(), kwargs...)
+    kind, gamma, coef0, degree = _kern_args(kern, kwargs)
+    nlv >= 1 || throw(ArgumentError("nlv = $nlv must be >= 1"))
+    maxit >= 1 || throw(ArgumentError("maxit = $maxit must be >= 1"))
+    X = ensure_mat(X); Y = ensure_mat(Y)
+    n, p = size(X); q = size(Y, 2)
+    size(Y, 1) == n || throw(DimensionMismatch("X has $n rows, Y has $(size(Y, 1))"))
+    weights = _w(weights, X)
+    kmax = min(n, nlv)
+    T = _similar(X, n, kmax); U = _similar(X, n, kmax); R = _similar(X, n, kmax); vt = _similar(X, 1, n); wn = _similar(X, n)
+    C = zeros(q, kmax); xs = ones(p); ym = zeros(q); ys = ones(q); it = zeros(Int32, kmax); got = Ref{Int32}(0)
+    desc = Ref(PlsDesc(n, p, q, nlv, scal ? 1 : 0, 0, _loc(X), 1, 0))
+    GC.@preserve X Y weights T U R vt wn check(ctx, ccall((:jch_kplsr_fit, LIB), Int32,
+        (Ptr{Cvoid}, Ref{PlsDesc}, Int32, Float64, Float64, Int32, Float64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Ref{Int32}),
+        ctx.h, desc, kind, gamma, coef0, degree, Float64(tol), Int32(maxit), pointer(X), stride(X, 2), pointer(Y), max(stride(Y, 2), n),
+        weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights), Ptr{Float64}(C_NULL), pointer(T), pointer(U), pointer(R),
+        pointer(vt), C, xs, ym, ys, pointer(wn), it, got))
+    iter = Vector{Int}(it)
+    J = jchemo_module()
+    if J !== nothing && X isa Matrix{Float64} && T isa Matrix{Float64}
+        return Base.invokelatest(getfield(J, :Kplsr), X, zeros(0, 0), T, C, U, R, wn, zeros(0, 0), vt, xs, ym, ys, wn, kern, kwargs, iter)
+    end
+    Kplsr(X, zeros(0, 0), T, C, U, R, wn, zeros(0, 0), vt, xs, ym, ys, wn, kern, kwargs, iter)
+end
+
+function _coef_kplsr(object, nlv)                       # src/kplsr.jl:221-228
+    a = size(object.T, 2)
+    nlv = nlv === nothing ? a : min(nlv, a)
+    (beta = object.C[:, 1:nlv]', int = reshape(object.ymeans, 1, :))
+end
+
+function _transform_kplsr(object, X, nlv, ctx)          # src/kplsr.jl:202-212
+    kind, gamma, coef0, degree = _kern_args(object.kern, object.dots)
+    a = size(object.T, 2)
+    nlv = nlv === nothing ? a : min(nlv, a)
+    X = _in(X); Xt = object.X; m, p = size(X); n = size(Xt, 1)
+    out = _similar(X, m, nlv)
+    R = Matrix{Float64}(object.R); xs = Vector{Float64}(object.xscales)
+    w = Vector{Float64}(vec(object.weights)); vt = Vector{Float64}(vec(object.vtot))
+    GC.@preserve X Xt out R xs w vt check(ctx, ccall((:jch_kplsr_transform, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), m, p, stride(X, 2), pointer(xs), pointer(Xt), n, stride(Xt, 2),
+        pointer(w), pointer(vt), pointer(R), nlv, pointer(out), max(m, 1)))
+    out
+end
+
+function _predict_kplsr(object, X, nlv, ctx)            # src/kplsr.jl:238-250
+    kind, gamma, coef0, degree = _kern_args(object.kern, object.dots)
+    a = size(object.T, 2); q = size(object.C, 1)
+    rng = nlv === nothing ? (a:a) : (max(0, minimum(nlv)):min(a, maximum(nlv)))
+    X = _in(X); Xt = object.X; m, p = size(X); n = size(Xt, 1)
+    out = _similar(X, m, q * length(rng))
+    R = Matrix{Float64}(object.R); Cm = Matrix{Float64}(object.C); xs = Vector{Float64}(object.xscales)
+    w = Vector{Float64}(vec(object.weights)); vt = Vector{Float64}(vec(object.vtot))
+    ym = Vector{Float64}(vec(object.ymeans)); ys = Vector{Float64}(vec(object.yscales))
+    GC.@preserve X Xt out R Cm xs w vt ym ys check(ctx, ccall((:jch_kplsr_predict, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), m, p, stride(X, 2), pointer(xs), pointer(Xt), n, stride(Xt, 2),
+        pointer(w), pointer(vt), pointer(ym), pointer(ys), pointer(R), pointer(Cm), q, first(rng), last(rng), pointer(out), max(m, 1)))
     pred = [out[:, (i - 1) * q + 1:i * q] for i in 1:length(rng)]
     (pred = length(rng) == 1 ? pred[1] : pred,)
 end

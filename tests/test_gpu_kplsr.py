@@ -1,0 +1,296 @@
+"""Kernel NIPALS PLS on the GPU (kplsr, include/jchemo_hip.h jch_kplsr_*) against the numpy restatements of src/kplsr.jl in
+test_kplsr_static.py.  No sign alignment: t is fixed by y (or Y[:, 1]).  Parity bound: relative Frobenius error <= 1e-6."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "jchemo.jl_amd"), os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+import jchemo_hip as J  # noqa: E402
+from jchemo_hip import _lib  # noqa: E402
+from test_kplsr_static import np_kplsr, np_kplsr_predict, np_kplsr_transform, rel_fro  # noqa: E402
+
+TOL = 1e-6
+ACHIEVED = {}
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    return J.default_context(0)
+
+
+def spectra(seed, n, p, base=0.0):
+    rng = np.random.default_rng(seed)
+    grid = np.linspace(0, 1, p)
+    c = np.array([0.2, 0.45, 0.7, 0.85])
+    H = rng.random((n, c.size))
+    X = H @ np.exp(-((grid[None, :] - c[:, None]) / 0.08) ** 2) + 0.01 * rng.standard_normal((n, p)) + base
+    return np.asfortranarray(X), H
+
+
+def data(seed, n, p, q):
+    X, H = spectra(seed, n, p)
+    rng = np.random.default_rng(seed + 1)
+    Y = np.column_stack([np.sin(3 * H @ rng.random(H.shape[1])) + 0.05 * rng.standard_normal(n) for _ in range(q)])
+    return X, np.asfortranarray(Y)
+
+
+def host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def check_fit(fm, ref, tag, tol=TOL):
+    errs = {f: rel_fro(ref[f], host(getattr(fm, f))) for f in ("T", "U", "C", "R", "vtot")}
+    errs["xscales"] = rel_fro(ref["xscales"], fm.xscales)
+    errs["ymeans"] = rel_fro(ref["ymeans"], fm.ymeans) if np.any(ref["ymeans"]) else 0.0
+    errs["yscales"] = rel_fro(ref["yscales"], fm.yscales)
+    errs["weights"] = rel_fro(ref["weights"], host(fm.weights))
+    ACHIEVED[tag] = max(errs.values())
+    assert max(errs.values()) <= tol, (tag, errs)
+    assert np.array_equal(np.asarray(fm.iter), ref["iter"]), (tag, fm.iter, ref["iter"])
+
+
+def weights_of(kind, n, seed):
+    rng = np.random.default_rng(seed)
+    if kind == "uniform":
+        return None
+    w = rng.random(n) + 0.1
+    if kind == "zeros":
+        w[rng.choice(n, n // 5, replace=False)] = 0.0
+    return w
+
+
+KERNS = {"krbf": dict(gamma=0.5), "kpol": dict(degree=2, gamma=0.3, coef0=1.0)}
+
+
+@pytest.mark.parametrize("kern", ["krbf", "kpol"])
+@pytest.mark.parametrize("q", [1, 3, 20])
+@pytest.mark.parametrize("scal", [False, True])
+@pytest.mark.parametrize("wkind", ["uniform", "random", "zeros"])
+def test_fit_matches_the_literal_restatement(ctx, kern, q, scal, wkind):
+    n, p, nlv = 160, 24, 8
+    X, Y = data(11 + q, n, p, q)
+    w = weights_of(wkind, n, 5)
+    ref = np_kplsr(X, Y, w, nlv=nlv, kern=kern, scal=scal, **KERNS[kern])
+    fm = J.kplsr(X, Y, w, nlv=nlv, kern=kern, scal=scal, ctx=ctx, **KERNS[kern])
+    check_fit(fm, ref, f"{kern}-q{q}-{scal}-{wkind}")
+    assert fm.T.shape == (n, nlv) and fm.C.shape == (q, nlv) and fm.vtot.shape == (1, n)
+    assert fm.DKt is None and fm.Kt is None
+
+
+@pytest.mark.parametrize("nlv", [1, 2, 5, 15])
+def test_fit_nlv_range(ctx, nlv):
+    X, Y = data(3, 200, 30, 2)
+    ref = np_kplsr(X, Y, nlv=nlv, gamma=0.2)
+    fm = J.kplsr(X, Y, nlv=nlv, gamma=0.2, ctx=ctx)
+    check_fit(fm, ref, f"nlv{nlv}")
+
+
+def test_nlv_clamped_to_n(ctx):
+    X, Y = data(4, 12, 5, 1)
+    fm = J.kplsr(X, Y, nlv=30, gamma=0.5, ctx=ctx)
+    assert fm.T.shape == (12, 12) and fm.U.shape == (12, 12) and fm.R.shape == (12, 12) and fm.C.shape == (1, 12)
+    assert len(fm.iter) == 12
+
+
+def test_host_and_device_inputs_give_identical_bits(ctx):
+    X, Y = data(5, 150, 20, 3)
+    w = weights_of("random", 150, 9)
+    a = J.kplsr(X, Y, w, nlv=6, scal=True, gamma=0.4, ctx=ctx)
+    Xd = torch.as_tensor(X, device="cuda").T.contiguous().T
+    Yd = torch.as_tensor(Y, device="cuda").T.contiguous().T
+    b = J.kplsr(Xd, Yd, torch.as_tensor(w, device="cuda"), nlv=6, scal=True, gamma=0.4, ctx=ctx)
+    for f in ("T", "U", "R", "vtot", "weights", "X"):
+        assert np.array_equal(host(getattr(a, f)), host(getattr(b, f))), f
+    for f in ("C", "xscales", "ymeans", "yscales", "iter"):
+        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    pa = J.predict(a, X[:7], nlv=[0, 6], ctx=ctx)
+    pb = J.predict(b, Xd[:7], nlv=[0, 6], ctx=ctx)
+    for u, v in zip(pa, pb):
+        assert np.array_equal(u, host(v))
+
+
+def test_sinc_example_from_the_docstring(ctx):
+    x = np.arange(-10, 10.0001, 0.2)
+    x[np.abs(x) < 1e-12] = 1e-5
+    zy = np.sin(np.abs(x)) / np.abs(x)
+    y = zy + 0.2 * np.random.default_rng(0).standard_normal(x.size)
+    X = x.reshape(-1, 1); Y = y.reshape(-1, 1)
+    ref = np_kplsr(X, Y, nlv=2)
+    fm = J.kplsr(X, Y, nlv=2, ctx=ctx)
+    check_fit(fm, ref, "sinc")
+    pred = J.predict(fm, X, ctx=ctx)
+    assert rel_fro(np_kplsr_predict(ref, X), pred) <= TOL
+    assert np.sqrt(np.mean((pred.ravel() - zy) ** 2)) < 0.2   # the fitted model follows sinc
+
+
+@pytest.mark.parametrize("scal", [False, True])
+def test_transform_and_predict_on_new_rows(ctx, scal, monkeypatch):
+    X, Y = data(6, 180, 25, 2)
+    Xn, _ = data(60, 37, 25, 2)
+    w = weights_of("random", 180, 3)
+    ref = np_kplsr(X, Y, w, nlv=7, scal=scal, gamma=0.3)
+    fm = J.kplsr(X, Y, w, nlv=7, scal=scal, gamma=0.3, ctx=ctx)
+    for m in (1, 37):
+        Z = np.asfortranarray(Xn[:m])
+        T = J.transform(fm, Z, ctx=ctx)
+        T4 = J.transform(fm, Z, nlv=4, ctx=ctx)
+        P1 = J.predict(fm, Z, nlv=5, ctx=ctx)
+        PR = J.predict(fm, Z, nlv=range(0, 8), ctx=ctx)
+        assert rel_fro(np_kplsr_transform(ref, Z), T) <= TOL
+        assert rel_fro(np_kplsr_transform(ref, Z, 4), T4) <= TOL
+        assert rel_fro(np_kplsr_predict(ref, Z, 5), P1) <= TOL
+        for a, b in zip(np_kplsr_predict(ref, Z, range(0, 8)), PR):
+            assert rel_fro(a, b) <= TOL
+        monkeypatch.setenv("JCH_KPLSR_QBLOCK", "5")
+        assert np.array_equal(T, J.transform(fm, Z, ctx=ctx))
+        assert np.array_equal(P1, J.predict(fm, Z, nlv=5, ctx=ctx))
+        for a, b in zip(PR, J.predict(fm, Z, nlv=range(0, 8), ctx=ctx)):
+            assert np.array_equal(a, b)
+        monkeypatch.delenv("JCH_KPLSR_QBLOCK")
+    B, intercept = J.coef(fm, nlv=3)
+    assert np.array_equal(B, fm.C[:, :3].T) and np.array_equal(intercept, fm.ymeans.reshape(1, -1))
+
+
+def test_near_constant_kernel(ctx):
+    """Spectra on a large baseline and a small gamma: Kc << K entrywise; guards the centring arithmetic."""
+    X, H = spectra(8, 150, 40, base=50.0)
+    Y = np.asfortranarray((H @ np.array([1.0, -0.5, 0.3, 0.8])).reshape(-1, 1))
+    Xn, _ = spectra(80, 20, 40, base=50.0)
+    ref = np_kplsr(X, Y, nlv=4, gamma=1e-3)
+    Kc = ref["K"] - ref["vtot"].T - ref["vtot"] + ref["weights"] @ ref["vtot"].ravel()
+    assert np.abs(Kc).max() < 1e-2 * np.abs(ref["K"]).min()
+    fm = J.kplsr(X, Y, nlv=4, gamma=1e-3, ctx=ctx)
+    check_fit(fm, ref, "near-constant")
+    assert rel_fro(np_kplsr_predict(ref, Xn, [1, 4])[-1], J.predict(fm, Xn, nlv=[1, 4], ctx=ctx)[-1]) <= TOL
+
+
+def test_copy_semantics(ctx):
+    X, Y = data(9, 120, 15, 2)
+    X0, Y0 = X.copy(order="F"), Y.copy(order="F")
+    fm = J.kplsr(X, Y, nlv=4, scal=True, gamma=0.3, ctx=ctx)
+    assert np.array_equal(X, X0) and np.array_equal(Y, Y0)
+    ref = np_kplsr(X0, Y0, nlv=4, scal=True, gamma=0.3)
+    assert rel_fro(ref["X"], fm.X) <= 1e-14
+    Xi, Yi = X0.copy(order="F"), Y0.copy(order="F")
+    fi = J.kplsr_(Xi, Yi, nlv=4, scal=True, gamma=0.3, ctx=ctx)
+    assert fi.X is Xi
+    assert rel_fro(ref["X"], Xi) <= 1e-14                     # X divided by xscales (src/kplsr.jl:131)
+    assert np.linalg.norm(ref["Y"] - Yi) <= TOL * np.linalg.norm((Y0 - ref["ymeans"]) / ref["yscales"])   # centred, scaled, deflated
+    check_fit(fi, ref, "inplace")
+
+
+def test_two_fits_are_bitwise_equal(ctx):
+    X, Y = data(10, 170, 20, 4)
+    a = J.kplsr(X, Y, nlv=6, gamma=0.5, ctx=ctx)
+    b = J.kplsr(X, Y, nlv=6, gamma=0.5, ctx=ctx)
+    for f in ("T", "U", "C", "R", "vtot", "iter"):
+        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+
+
+def test_keep_gram(ctx):
+    X, Y = data(12, 140, 18, 1)
+    fm = J.kplsr(X, Y, nlv=3, gamma=0.7, keep_gram=True, ctx=ctx)
+    K = J.krbf(X, X, gamma=0.7, ctx=ctx)
+    assert torch.is_tensor(fm.Kt) and fm.Kt.shape == (140, 140)
+    assert np.array_equal(fm.Kt.cpu().numpy(), K)
+    ref = np_kplsr(X, Y, nlv=3, gamma=0.7)
+    check_fit(fm, ref, "keep_gram")
+
+
+def test_gridscorelv_with_kplsr(ctx):
+    X, Y = data(13, 150, 20, 1)
+    Xt, Yt = data(14, 40, 20, 1)
+    res = J.gridscorelv(X, Y, Xt, Yt, score=J.rmsep, fun=J.kplsr, nlv=range(0, 6), pars=J.mpar(gamma=[0.1, 1.0]), ctx=ctx)
+    out = np.asarray(res["res"]).reshape(-1)
+    k = 0
+    for g in (0.1, 1.0):
+        fm = J.kplsr(X, Y, nlv=5, gamma=g, ctx=ctx)
+        for pr in J.predict(fm, Xt, nlv=range(0, 6), ctx=ctx):
+            assert abs(out[k] - float(np.asarray(J.rmsep(pr, Yt)).ravel()[0])) <= 1e-12 * max(1.0, abs(out[k]))
+            k += 1
+    assert k == out.size
+
+
+def test_errors(ctx):
+    X, Y = data(15, 30, 5, 1)
+    with pytest.raises(ValueError):
+        J.kplsr(X, Y, nlv=2, kern="ksig", ctx=ctx)
+    with pytest.raises(ValueError):
+        J.kplsr(X, Y, nlv=2, sigma=1.0, ctx=ctx)
+    with pytest.raises(ValueError):
+        J.kplsr(X, Y[:20], nlv=2, ctx=ctx)
+    with pytest.raises(ValueError):
+        J.kplsr(X, Y, nlv=0, ctx=ctx)
+    with pytest.raises(ValueError):
+        J.kplsr(X, Y, nlv=2, maxit=0, ctx=ctx)
+    # the C ABI validates on its own
+    desc = _lib.PlsDesc(n=30, p=5, q=1, nlv=0, scal=0, dtype=_lib.F64, loc=_lib.LOC_HOST, inplace=0, reserved=0)
+    import ctypes as C
+    got = C.c_int32(0)
+    it = np.zeros(2, dtype=np.int32)
+    args = lambda d, maxit: (ctx._h, C.byref(d), _lib.KERN_RBF, 1.0, 0.0, 1, 1.5e-8, maxit, X.ctypes.data, 30, Y.ctypes.data, 30, None,
+                             None, None, None, None, None, None, None, None, None, None, it.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(got))
+    assert _lib.load().jch_kplsr_fit(*args(desc, 10)) == _lib.JCH_EINVAL
+    desc.nlv = 2
+    assert _lib.load().jch_kplsr_fit(*args(desc, 0)) == _lib.JCH_EINVAL
+    assert _lib.load().jch_kplsr_fit(ctx._h, C.byref(desc), 7, 1.0, 0.0, 1, 1.5e-8, 10, X.ctypes.data, 30, Y.ctypes.data, 30, None, None,
+                                     None, None, None, None, None, None, None, None, None, None, None) == _lib.JCH_EINVAL
+    assert _lib.load().jch_kplsr_fit(*args(desc, 10)) == 0 and got.value == 2
+
+
+@pytest.mark.parametrize("q", [1, 4])
+def test_full_size_fit(ctx, q):
+    """n = 16 384, p = 512, nlv = 25 against the rank-two restatement (O(n^2) per LV on the host)."""
+    n, p, nlv = 16384, 512, 25
+    X, Y = data(21, n, p, q)
+    Xd = torch.as_tensor(X, device="cuda").T.contiguous().T
+    Yd = torch.as_tensor(Y, device="cuda").T.contiguous().T
+    fm = J.kplsr(Xd, Yd, nlv=nlv, gamma=1.0 / p, ctx=ctx, keep_gram=True)
+    K = fm.Kt.cpu().numpy()
+    # the restatement on the device's K (the Gram itself is covered by the dkplsr tests): src/kplsr.jl:138-190 with rank-two deflation
+    w = np.full(n, 1.0 / n)
+    Yc = Y - Y.mean(axis=0)
+    vtot = K @ w
+    s = w @ vtot
+    Kc = K - vtot[:, None] - vtot[None, :] + s
+    del K
+    Ka = Kc.copy()
+    T = np.zeros((n, nlv)); U = np.zeros((n, nlv)); Cm = np.zeros((q, nlv)); it = np.zeros(nlv, dtype=np.int64)
+    for a in range(nlv):
+        u = Yc[:, 0].copy()
+        ztol, ziter = 1.0, 1
+        while True:
+            t = Ka @ (w * u); t /= np.sqrt(t @ (w * t)); dt = w * t
+            c = Yc.T @ dt; zu = Yc @ c; zu /= np.sqrt(zu @ zu)
+            if q == 1:
+                u = zu
+                break
+            ztol = np.sqrt(np.sum((u - zu) ** 2)); u = zu; ziter += 1
+            if not (ztol > 1.5e-8 and ziter <= 100):
+                break
+        it[a] = 0 if q == 1 else ziter - 1
+        av = Ka @ dt
+        Ka -= np.outer(t, av); Ka -= np.outer(av, t); Ka += (dt @ av) * np.outer(t, t)
+        Yc = Yc - np.outer(t, c)
+        T[:, a] = t; U[:, a] = u; Cm[:, a] = c
+    DU = w[:, None] * U
+    R = DU @ np.linalg.inv(T.T @ (w[:, None] * (Kc @ DU)))
+    errs = {"T": rel_fro(T, host(fm.T)), "U": rel_fro(U, host(fm.U)), "C": rel_fro(Cm, fm.C), "R": rel_fro(R, host(fm.R)),
+            "vtot": rel_fro(vtot, host(fm.vtot).ravel())}
+    ACHIEVED[f"full-q{q}"] = max(errs.values())
+    assert max(errs.values()) <= TOL, errs
+    assert np.array_equal(np.asarray(fm.iter), it)
+
+
+def test_report_achieved():
+    if ACHIEVED:
+        print("\nkplsr: worst rel. Frobenius error per case:", {k: f"{v:.1e}" for k, v in sorted(ACHIEVED.items())})
