@@ -392,12 +392,40 @@ JCH_API int32_t jch_kplsr_predict(jch_ctx *ctx, int32_t loc, int32_t kind, doubl
                                   const double *weights, const double *vtot, const double *ymeans, const double *yscales, const double *R,
                                   const double *C, int64_t q, int32_t nlv_lo, int32_t nlv_hi, double *pred, int64_t ldo);
 
+/* ---- kernel PCA (src/kpca.jl:1-147) on a Gram matrix built on the device ---------------------------------------------------
+ * jch_kpca_fit — `kpca(X, weights; nlv, kern, scal, kwargs...)` (src/kpca.jl:82-115): w = mweight(weights) (:93); with scal
+ * xscales = colstd(X, w) and X DIVIDED by them in place (:94-98; X is not centred); K = kern(X, X), vtot = K w,
+ * Kc = K - vtot' - vtot + w'vtot (:99-103); the leading nlv eigenpairs of Kd = sqrtD Kc sqrtD, ordered by |lambda| (the singular
+ * triplets of svd(Kd), :104-108), from block subspace iteration with Rayleigh-Ritz on the device (one read of Kc per iteration,
+ * DESIGN.md §12); eig = |lambda|, sv = sqrt(eig) (:109-110), P = sqrtD U diag(1/sv) (:113), T = Kc P (:114).  Sign rule: the
+ * largest-|.| entry of every U column is positive.  An eigenvalue that is exactly 0 gives Inf / NaN in P, as in the reference.
+ *   X n x p (ldx), weights n or NULL [loc]; kind / gamma / coef0 / degree as jch_kernel_gram.  nlv is clamped to n (:100);
+ *   *nlv_out = min(n, nlv).  tol > 0, maxit >= 1: the iteration stops when every one of the first nlv residual norms
+ *   |Kd u_i - lambda_i u_i| is <= tol * eig[0], or after maxit iterations; it never fails for lack of convergence.
+ *   Outputs: T, P n x nlv (ld n), vtot n, weights_norm n [loc]; xscales p (ones without scal), sv, eig, resid nlv, sstot 1,
+ *   niter 1 HOST; any may be NULL.  sv / eig hold the nlv leading values only (the reference keeps all n).  The fit converged iff
+ *   every resid[i] <= tol * eig[0].  sstot = sum of all n singular values of Kd (summary's denominator, :138-147): computed as
+ *   trace(Kd) = sum_i w_i Kc_ii for the kernels that are PSD by construction (krbf with gamma >= 0; kpol with gamma >= 0 and
+ *   degree == 1 or coef0 >= 0); NaN for any other parameter set.  K_out: a DEVICE n x n buffer (ld n) that receives the
+ *   UNcentred Gram (the reference's Kpca.Kt), or NULL.  The centred Gram lives in ctx workspace (n^2 doubles); a Gram that does
+ *   not fit returns JCH_ENOMEM.  Float64 only; one GPU (a communicator of more than one rank: JCH_EINVAL).
+ *   `transform(object::Kpca, X; nlv)` (:123-129) is jch_kplsr_transform with R = P (the model's X, weights_norm, vtot and xscales).
+ *   The block size is min(n, roundup16(nlv + 7)); JCH_KPCA_OVERSAMPLE=<k> in the environment replaces the 7 (measurement only). */
+JCH_API int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, double coef0, int32_t degree, double *X, int64_t n, int64_t p,
+                             int64_t ldx, const double *weights, int32_t nlv, int32_t scal, double tol, int32_t maxit, double *K_out, double *T,
+                             double *P, double *vtot, double *weights_norm, double *xscales, double *sv, double *eig, double *sstot,
+                             int32_t *niter, double *resid, int32_t *nlv_out);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in
  * (README.md:79-94), identical to oracle/plsr_oracle.py:splitmix64_uniform. */
 JCH_API int32_t jch_fill_uniform(jch_ctx *ctx, double *dev_out, int64_t n, int64_t p, int64_t ld, int64_t row0,
                          int64_t n_total, uint64_t seed);
+
+/* out (n x b, ld ldo) = Kc V, Kc n x n (ld n), V n x b (ld ldv), all DEVICE pointers: the panel product of jch_kpca_fit on the
+ * f64 matrix cores (any b >= 1, in chunks of 64 columns).  Every output is one workgroup's fixed-order sum. */
+JCH_API int32_t jch_kc_panel(jch_ctx *ctx, const double *Kc, int64_t n, const double *V, int64_t ldv, int32_t b, double *out, int64_t ldo);
 
 typedef struct jch_profile {
     double fit_ms;        /* device time of the last fit, first kernel -> last kernel (HIP events)   */

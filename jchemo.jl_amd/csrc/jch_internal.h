@@ -72,6 +72,7 @@ struct jch_ctx {
     jch_buf gram, xr, yr, xstage, ystage, wstage, tbuf, dnorm, part, kpart, small, colpart, gemm_b, gemm_out, xq, tickets, qz, lw_work, lw_xrm, lvws, lw_flags, lw_screen;
     jch_buf kg_ws, dk_x, dk_y, dk_k, dk_q, dk_o, dk_s;   // Gram kernel workspace (kgram.hip), dkplsr staging (dkplsr.hip)
     jch_buf kp_ws;   // kplsr panels and small state (kplsr.hip)
+    jch_buf kc_vt, pc_ws;   // panel operand of the Kc pass, kpca panels and small state (kpca.hip)
     // profiling
     bool profiling = false;
     int prof_stride = 1;        // jch_ctx_set_profiling(ctx, N > 1): event pairs around every N-th launch of the sampled dominant kernels only
@@ -271,6 +272,12 @@ int32_t jch_launch_scores(jch_ctx *ctx, const double *Xr, int64_t n, int p, int 
 // pointer, ld and divisors), only the tiles on or below the diagonal are computed and each is stored twice
 int32_t jch_launch_kgram(jch_ctx *ctx, int kind, const double *Z, int64_t m, int64_t ldz, const double *zdiv, const double *X, int64_t n,
                          int64_t ldx, const double *xdiv, int64_t p, double gamma, double coef0, int degree, bool sym, double *K, int64_t ldk);
+// kplsr.hip: K = kern(X, X) into Kraw, vtot = K w, *sdev = w'vtot, Kc = K - vtot 1' - 1 vtot' + *sdev (Kc == Kraw allowed)
+int32_t jch_launch_kp_centred_gram(jch_ctx *ctx, int kind, double gamma, double coef0, int degree, const double *X, int64_t n, int64_t ldx,
+                                   const double *xdiv, int64_t p, const double *wn, double *Kraw, double *Kc, double *vt, double *sdev);
+// kpca.hip: out (n x b, ld ldo) = Kc (diag(d) V) on the f64 matrix cores (d: device n-vector or null); any b, chunks of 64 columns
+int32_t jch_launch_kc_panel(jch_ctx *ctx, const double *Kc, int64_t n, int64_t ldk, const double *V, int64_t ldv, int b, const double *d,
+                            double *out, int64_t ldo);
 // util.hip
 int32_t jch_launch_fill(jch_ctx *ctx, double *out, int64_t n, int64_t p, int64_t ld, int64_t row0, int64_t n_total,
                         uint64_t seed);

@@ -479,6 +479,18 @@ int32_t kp_apply(jch_ctx *ctx, const char *who, int32_t loc, int32_t kind, doubl
 
 }  // namespace
 
+// K = kern(X, X) (symmetric path) into Kraw, vtot = K w, s = w'vtot and Kc = K - vtot 1' - 1 vtot' + s into Kc (Kc == Kraw allowed):
+// the same launches as jch_kplsr_fit below, for kpca.hip
+int32_t jch_launch_kp_centred_gram(jch_ctx *ctx, int kind, double gamma, double coef0, int degree, const double *X, int64_t n, int64_t ldx,
+                                   const double *xdiv, int64_t p, const double *wn, double *Kraw, double *Kc, double *vt, double *sdev)
+{
+    JCH_TRY(jch_launch_kgram(ctx, kind, X, n, ldx, xdiv, X, n, ldx, xdiv, p, gamma, coef0, degree, true, Kraw, n));
+    JCH_TRY(launch_pass(ctx, Kraw, n, wn, n, 1, vt, n));
+    hipLaunchKernelGGL(k_kp_wdot, dim3(1), dim3(KP_NT), 0, ctx->stream, wn, vt, n, sdev);
+    JCH_HIP(ctx, hipGetLastError());
+    return launch_center(ctx, Kraw, n, Kc, n, n, n, vt, vt, sdev, 0.0);
+}
+
 extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t kind, double gamma, double coef0, int32_t degree, double tol,
                                  int32_t maxit, void *X, int64_t ldx, void *Y, int64_t ldy, const double *weights, double *K_out, double *T,
                                  double *U, double *R, double *vtot, double *C, double *xscales, double *ymeans, double *yscales,

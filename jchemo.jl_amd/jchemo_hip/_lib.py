@@ -30,7 +30,7 @@ SYMBOLS = (
     "jch_ctx_p2p_export", "jch_ctx_p2p_import", "jch_ctx_p2p_enable", "jch_plskern_fit_scaled", "jch_col_stats",
     "jch_ctx_get_counter", "jch_ctx_allreduce_probe", "jch_lwplsr_prepare", "jch_lwplsr_predict_prepared", "jch_lwplsr_release", "jch_lwplsr_add_query_map",
     "jch_kernel_gram", "jch_dkplsr_fit", "jch_dkplsr_transform", "jch_dkplsr_predict",
-    "jch_kplsr_fit", "jch_kplsr_transform", "jch_kplsr_predict",
+    "jch_kplsr_fit", "jch_kplsr_transform", "jch_kplsr_predict", "jch_kpca_fit", "jch_kc_panel",
 )
 
 
@@ -114,6 +114,9 @@ def load():
     L.jch_kplsr_transform.argtypes = [vp, i32, i32, f64, f64, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, dp, dp, i32, dp, i64]
     L.jch_kplsr_predict.argtypes = [vp, i32, i32, f64, f64, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, dp, dp, dp, dp, dp, i64, i32, i32,
                                     dp, i64]
+    L.jch_kpca_fit.argtypes = [vp, i32, i32, f64, f64, i32, dp, i64, i64, i64, dp, i32, i32, f64, i32] + [dp] * 9 + [C.POINTER(i32), dp,
+                                                                                                            C.POINTER(i32)]
+    L.jch_kc_panel.argtypes = [vp, dp, i64, dp, i64, i32, dp, i64]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]
     L.jch_ctx_set_profiling.argtypes = [vp, i32]
     L.jch_ctx_get_profile.argtypes = [vp, C.POINTER(Profile)]

@@ -4,6 +4,7 @@ Same names, argument meaning and error behaviour as Jchemo.jl (paths relative to
     plskern / plskern_ (= `plskern!`)      src/plskern.jl:106-178
     dkplsr / dkplsr_ (= `dkplsr!`), krbf, kpol   src/dkplsr.jl, src/kernels.jl
     kplsr / kplsr_ (= `kplsr!`)            src/kplsr.jl
+    kpca, kpca_transform, kpca_summary     src/kpca.jl
     plsnipals / plsnipals_ (= `plsnipals!`) src/plsnipals.jl:31-97
     transform / coef / predict / summary    src/plskern.jl:187-260
     Plsr                                    src/plskern.jl:1-14
@@ -354,6 +355,8 @@ def transform(fm: Plsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] 
         return dkplsr_transform(fm, X, nlv=nlv, ctx=ctx)
     if isinstance(fm, Kplsr):
         return kplsr_transform(fm, X, nlv=nlv, ctx=ctx)
+    if isinstance(fm, Kpca):
+        return kpca_transform(fm, X, nlv=nlv, ctx=ctx)
     k = _nlv_arg(fm, nlv)
     if k < 1:
         raise ValueError("transform needs nlv >= 1")
@@ -1674,3 +1677,127 @@ def kplsr_predict(obj: Kplsr, X, *, nlv: Union[None, int, Sequence[int]] = None,
                                             max(args[7], 1)))
     preds = [out[:, i * q:(i + 1) * q] for i in range(len(rng))]
     return preds[0] if len(preds) == 1 else preds
+
+
+# ---------------------------------------------------------------------------------- kernel PCA (src/kpca.jl)
+@dataclass
+class Kpca:
+    """Field names and order of the reference's `Kpca` (src/kpca.jl:1-15), then the eigensolver's report.  `X` is the (scaled)
+    training X the transforms are built on; T, P (n x nlv) and vtot (1 x n) live where X lives; sv and eig are host arrays of the
+    nlv leading values (the reference keeps all n).  `Kt` is the uncentred Gram as a device tensor when the fit was asked to keep
+    it (`keep_gram=True`), else None.  `D` holds the weight vector; `DKt` is always None (its only use, sum(D * DKt'), equals
+    weights . vtot).  sstot is the sum of all n singular values of Kd (NaN for a kernel that is not PSD by construction), niter
+    the subspace iterations, resid the final residual norms |Kd u_i - eig_i u_i| and converged whether all are <= eig_tol * eig[0]."""
+    X: object
+    Kt: object
+    T: object
+    P: object
+    sv: np.ndarray
+    eig: np.ndarray
+    D: object
+    DKt: object
+    vtot: object
+    xscales: np.ndarray
+    weights: object
+    kern: str
+    dots: dict
+    sstot: float
+    niter: int
+    resid: np.ndarray
+    converged: bool
+
+
+def kpca(X, weights=None, *, nlv: int, kern: str = "krbf", scal: bool = False, eig_tol: float = 1e-10, eig_maxit: int = 300,
+         ctx: Optional[Context] = None, keep_gram: bool = False, **kwargs) -> Kpca:
+    """`kpca(X, weights; nlv, kern = "krbf", scal = false, kwargs...)` — src/kpca.jl:82-115 through jch_kpca_fit: the nlv leading
+    eigenpairs of Kd = sqrtD Kc sqrtD by block subspace iteration on the device instead of the full svd(Kd).  The fit works on a
+    copy of X (the inputs are left untouched); `kwargs` are the kernel's keywords (krbf: gamma; kpol: degree, gamma, coef0).
+    eig_tol / eig_maxit control the iteration; a fit that did not converge warns and returns what it has."""
+    kind, gamma, coef0, degree = _kern_args(kern, kwargs)
+    if int(nlv) < 1:
+        raise ValueError(f"nlv = {nlv} must be >= 1")
+    if int(eig_maxit) < 1:
+        raise ValueError(f"eig_maxit = {eig_maxit} must be >= 1")
+    if not float(eig_tol) > 0.0:
+        raise ValueError(f"eig_tol = {eig_tol} must be > 0")
+    X = _as_colmajor_copy(X)
+    dev = _is_torch(X)
+    n, p = X.shape
+    if weights is None:
+        w_arr, w_addr = None, None
+    elif dev:
+        w_arr = (weights if _is_torch(weights) else torch.as_tensor(np.asarray(weights, dtype=np.float64), device=X.device)).to(torch.float64).reshape(-1).contiguous()
+        w_addr = w_arr.data_ptr()
+    else:
+        w_arr = np.ascontiguousarray(np.asarray(weights.cpu() if _is_torch(weights) else weights, dtype=np.float64).reshape(-1))
+        w_addr = w_arr.ctypes.data
+    if w_arr is not None and w_arr.shape[0] != n:
+        raise ValueError(f"DimensionMismatch: weights has {w_arr.shape[0]} entries, X has {n} rows")
+    ctx = ctx or default_context((X.device.index or 0) if dev else 0)
+    kmax = min(n, int(nlv))
+    if dev:
+        T, P = colmajor_empty(n, kmax, X.device), colmajor_empty(n, kmax, X.device)
+        vt = torch.empty((1, n), dtype=torch.float64, device=X.device)
+        wn = torch.empty(n, dtype=torch.float64, device=X.device)
+        addrs = [T.data_ptr(), P.data_ptr(), vt.data_ptr(), wn.data_ptr()]
+    else:
+        T, P = np.empty((n, kmax), order="F"), np.empty((n, kmax), order="F")
+        vt = np.empty((1, n)); wn = np.empty(n)
+        addrs = [T.ctypes.data, P.ctypes.data, vt.ctypes.data, wn.ctypes.data]
+    K = None
+    if keep_gram:
+        if torch is None:
+            raise TypeError("keep_gram=True needs torch (the Gram stays on the device)")
+        K = colmajor_empty(n, n, X.device if dev else f"cuda:{ctx.device}")
+    xs = np.empty(p); sv = np.empty(kmax); eig = np.empty(kmax); res = np.empty(kmax)
+    sst = C.c_double(0.0); nit = C.c_int32(0); got = C.c_int32(0)
+    xa, ldx = _addr_ld(X)
+    if dev:
+        torch.cuda.current_stream(X.device).synchronize()
+    elif K is not None:
+        torch.cuda.current_stream(K.device).synchronize()
+    ctx.check(_lib.load().jch_kpca_fit(ctx._h, _lib.LOC_DEVICE if dev else _lib.LOC_HOST, kind, gamma, coef0, degree, xa, n, p, ldx, w_addr,
+                                       int(nlv), int(bool(scal)), float(eig_tol), int(eig_maxit), None if K is None else K.data_ptr(),
+                                       *addrs, xs.ctypes.data, sv.ctypes.data, eig.ctypes.data, C.addressof(sst), C.byref(nit),
+                                       res.ctypes.data, C.byref(got)))
+    conv = bool(np.all(res <= float(eig_tol) * eig[0]))
+    if not conv:
+        import warnings
+        warnings.warn(f"kpca: the subspace iteration did not converge in {nit.value} iterations (max residual "
+                      f"{float(res.max()):.3g}, tolerance {float(eig_tol) * eig[0]:.3g})", RuntimeWarning, stacklevel=2)
+    return Kpca(X, K, T, P, sv, eig, wn, None, vt, xs, wn, kern, dict(kwargs), float(sst.value), int(nit.value), res, conv)
+
+
+def kpca_transform(obj: Kpca, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = None):
+    """src/kpca.jl:123-132: Kc = K - vnew 1' - 1 vtot' + weights . vtot with K = kern(scale(X, xscales), object.X), T = Kc P[:, 1:nlv]
+    — jch_kplsr_transform with R = P (the same centring and Gram blocks)."""
+    a = obj.T.shape[1]
+    k = a if nlv is None else min(int(nlv), a)
+    if k < 1:
+        raise ValueError("transform needs nlv >= 1")
+    kind, gamma, coef0, degree = _kern_args(obj.kern, obj.dots)
+    X = _same_kind(X, obj.X)
+    if X.shape[1] != obj.X.shape[1]:
+        raise ValueError(f"DimensionMismatch: X has {X.shape[1]} columns, the model has {obj.X.shape[1]}")
+    X, out, oa, ctx, loc = _x_out(X, k, ctx)
+    xa, ldx = _addr_ld(X)
+    ta, ldt = _addr_ld(obj.X)
+    xs, w, vt = _model_vec(obj.xscales), _model_vec(_np_host(obj.weights)), _model_vec(_np_host(obj.vtot).reshape(-1))
+    Pk = np.asfortranarray(_np_host(obj.P)[:, :k], dtype=np.float64)
+    ctx.check(_lib.load().jch_kplsr_transform(ctx._h, loc, kind, gamma, coef0, degree, xa, X.shape[0], X.shape[1], ldx, xs.ctypes.data, ta,
+                                              obj.X.shape[0], ldt, w.ctypes.data, vt.ctypes.data, Pk.ctypes.data, k, oa, max(X.shape[0], 1)))
+    return out
+
+
+def kpca_summary(obj: Kpca):
+    """src/kpca.jl:138-147: explvarx = (lv, var = tt, pvar = tt / sstot, cumpvar) with tt = colsum(D T^2) (a per-column device
+    reduction: the weighted mean and std of every column of T, tt = std^2 + mean^2 with the normalised weights) and sstot = the sum of
+    all n singular values of Kd.  Raises for a kernel that is not PSD by construction: sstot would need the whole spectrum."""
+    if not np.isfinite(obj.sstot):
+        raise ValueError("kpca summary: sstot (the sum of all n singular values of Kd) is only available for kernels that are PSD by "
+                         "construction (krbf with gamma >= 0; kpol with gamma >= 0 and degree == 1 or coef0 >= 0); this model's "
+                         f"kernel {obj.kern} {obj.dots} may be indefinite")
+    mu, sd = _col_stats(obj.T, obj.weights, True, None)
+    tt = sd ** 2 + mu ** 2
+    pvar = tt / obj.sstot
+    return dict(lv=np.arange(1, tt.shape[0] + 1), var=tt, pvar=pvar, cumpvar=np.cumsum(pvar))

@@ -31,7 +31,7 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        lwplsr, transform, coef, predict, explvarx, JchCtx, attach!, nipals_one_pass!,
        msep, rmsep, ssr, bias, r2, cor2, mpar, segmkf, segmts, gridscorelv, gridcvlv,
        Plsrda, dummy, plsrda, Mbplsr, mbplsr, vip, xfit, xresid,
-       Dkplsr, dkplsr, dkplsr!, krbf, kpol, Kplsr, kplsr, kplsr!
+       Dkplsr, dkplsr, dkplsr!, krbf, kpol, Kplsr, kplsr, kplsr!, Kpca, kpca
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -1056,6 +1056,82 @@ function _predict_kplsr(object, X, nlv, ctx)            # src/kplsr.jl:238-250
         pointer(w), pointer(vt), pointer(ym), pointer(ys), pointer(R), pointer(Cm), q, first(rng), last(rng), pointer(out), max(m, 1)))
     pred = [out[:, (i - 1) * q + 1:i * q] for i in 1:length(rng)]
     (pred = length(rng) == 1 ? pred[1] : pred,)
+end
+
+# ---- kernel PCA (src/kpca.jl): block subspace iteration on the centred Gram on the device (include/jchemo_hip.h jch_kpca_fit) ------
+struct Kpca                       # fallback record, fields of the reference's struct (src/kpca.jl:1-15), then the eigensolver's
+    X                             # report; Kt and DKt are empty matrices (the Gram stays in the library's device workspace), D
+    Kt::Matrix{Float64}           # holds the weight vector, sv / eig the nlv leading values (the reference keeps all n)
+    T
+    P
+    sv::Vector{Float64}
+    eig::Vector{Float64}
+    D
+    DKt::Matrix{Float64}
+    vtot
+    xscales::Vector{Float64}
+    weights
+    kern
+    dots
+    sstot::Float64
+    niter::Int
+    resid::Vector{Float64}
+    converged::Bool
+end
+
+"""`kpca(X, weights; nlv, kern = "krbf", scal = false, kwargs...)` — src/kpca.jl:82-115 on a copy of X: the nlv leading eigenpairs of
+Kd = sqrtD Kc sqrtD come from block subspace iteration on the device (`eig_tol`, `eig_maxit`) instead of the full svd(Kd).  A fit
+that did not converge warns and returns what it has."""
+function kpca(X, weights = nothing; nlv, kern = "krbf", scal = false, ctx = default_ctx(), eig_tol = 1e-10, eig_maxit = 300, kwargs...)
+    kind, gamma, coef0, degree = _kern_args(kern, kwargs)
+    nlv >= 1 || throw(ArgumentError("nlv = $nlv must be >= 1"))
+    eig_maxit >= 1 || throw(ArgumentError("eig_maxit = $eig_maxit must be >= 1"))
+    eig_tol > 0 || throw(ArgumentError("eig_tol = $eig_tol must be > 0"))
+    X = copy(_in(X))
+    n, p = size(X)
+    weights = _w(weights, X)
+    weights === nothing || length(weights) == n || throw(DimensionMismatch("weights has $(length(weights)) entries, X has $n rows"))
+    kmax = min(n, nlv)
+    T = _similar(X, n, kmax); P = _similar(X, n, kmax); vt = _similar(X, 1, n); wn = _similar(X, n)
+    xs = ones(p); sv = zeros(kmax); eig = zeros(kmax); res = zeros(kmax); sst = Ref{Float64}(0.0); nit = Ref{Int32}(0); got = Ref{Int32}(0)
+    GC.@preserve X weights T P vt wn check(ctx, ccall((:jch_kpca_fit, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int32, Int32, Float64, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
+         Ref{Int32}, Ptr{Float64}, Ref{Int32}),
+        ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), n, p, stride(X, 2),
+        weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights), Int32(nlv), Int32(scal ? 1 : 0), Float64(eig_tol), Int32(eig_maxit),
+        Ptr{Float64}(C_NULL), pointer(T), pointer(P), pointer(vt), pointer(wn), xs, sv, eig, sst, nit, res, got))
+    conv = all(res .<= eig_tol * eig[1])
+    conv || @warn "kpca: the subspace iteration did not converge in $(nit[]) iterations" maxresid = maximum(res) tol = eig_tol * eig[1]
+    Kpca(X, zeros(0, 0), T, P, sv, eig, wn, zeros(0, 0), vt, xs, wn, kern, kwargs, sst[], Int(nit[]), res, conv)
+end
+
+"`transform(object::Kpca, X; nlv)` — src/kpca.jl:123-132: Kc_new P[:, 1:nlv], which is jch_kplsr_transform with R = P."
+function transform(object::Kpca, X; nlv = nothing, ctx = default_ctx())
+    kind, gamma, coef0, degree = _kern_args(object.kern, object.dots)
+    a = size(object.T, 2)
+    nlv = nlv === nothing ? a : min(nlv, a)
+    X = _in(X); Xt = object.X; m, p = size(X); n = size(Xt, 1)
+    out = _similar(X, m, nlv)
+    P = Matrix{Float64}(object.P); xs = Vector{Float64}(object.xscales)
+    w = Vector{Float64}(vec(object.weights)); vt = Vector{Float64}(vec(object.vtot))
+    GC.@preserve X Xt out P xs w vt check(ctx, ccall((:jch_kplsr_transform, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), m, p, stride(X, 2), pointer(xs), pointer(Xt), n, stride(Xt, 2),
+        pointer(w), pointer(vt), pointer(P), nlv, pointer(out), max(m, 1)))
+    out
+end
+
+"""`summary(object::Kpca)` — src/kpca.jl:138-147: explvarx (lv, var = tt, pvar = tt / sstot, cumpvar), tt = colsum(D T^2) from the
+device's weighted column statistics of T (tt = std^2 + mean^2).  sstot is only known for kernels that are PSD by construction."""
+function Base.summary(object::Kpca; ctx = default_ctx())
+    isfinite(object.sstot) || throw(ArgumentError("kpca summary: sstot (the sum of all n singular values of Kd) is only available for " *
+        "kernels that are PSD by construction (krbf with gamma >= 0; kpol with gamma >= 0 and degree == 1 or coef0 >= 0)"))
+    st = col_stats(object.T, object.weights; ctx = ctx)
+    tt = st.stds .^ 2 .+ st.means .^ 2
+    pvar = tt ./ object.sstot
+    (explvarx = _table((lv = collect(1:length(tt)), var = tt, pvar = pvar, cumpvar = cumsum(pvar))),)
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
