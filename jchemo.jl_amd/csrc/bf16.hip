@@ -59,7 +59,9 @@ __global__ __launch_bounds__(256) void k_moments_bf16(const bf16_t *__restrict__
 // 16-byte variant of K1: a thread owns 8 consecutive rows (one 16-B load per column, the 8 weights stay in registers)
 // and walks over MCG columns, so the weight vector is read once per MCG columns instead of once per column (it is 4x
 // the bytes of a bf16 column) and every global access is 16 B.  Needs 16-B aligned bases and leading dimensions % 8.
-template <bool VAR, int MCG>
+// (measured: 16 / 8 / 4 columns per thread -> prologue 1.40 / 1.27 / 1.29 ms at n = 1e6, p = 500)
+#define BF16_K1_COLS 8
+template <bool VAR>
 __global__ __launch_bounds__(256) void k_moments_bf16_v8(const bf16_t *__restrict__ Xc, int64_t ldx, const bf16_t *__restrict__ Yc,
                                                           int64_t ldy, const double *__restrict__ d, int64_t n, int p, int q,
                                                           int64_t chunk, const double *__restrict__ means,
@@ -67,6 +69,7 @@ __global__ __launch_bounds__(256) void k_moments_bf16_v8(const bf16_t *__restric
 {
     __shared__ double sc[4];
     typedef double v2f64_ __attribute__((ext_vector_type(2)));
+    constexpr int MCG = BF16_K1_COLS;
     const int j0 = blockIdx.x * MCG;
     const int m = p + q;
     const int64_t i0 = (int64_t)blockIdx.y * chunk;                 // chunk is a multiple of 8 * 256
@@ -151,22 +154,16 @@ static int32_t launch_moments_bf16(jch_ctx *ctx, const bf16_t *Xc, int64_t ldx, 
                                    int64_t n, int p, int q, const double *means, double *out)
 {
     const int m = p + q;
-    const bool v8 = ldx % 8 == 0 && ldy % 8 == 0 && ((uintptr_t)Xc) % 16 == 0 && ((uintptr_t)Yc) % 16 == 0 && ((uintptr_t)d) % 16 == 0 &&
-                    !getenv("JCH_BF16_SCALAR_PROLOGUE");
+    const bool v8 = ldx % 8 == 0 && ldy % 8 == 0 && ((uintptr_t)Xc) % 16 == 0 && ((uintptr_t)Yc) % 16 == 0 && ((uintptr_t)d) % 16 == 0;
     if (v8) {
-        static int mcg = -1;
-        if (mcg < 0) { const char *e = getenv("JCH_BF16_MCG"); mcg = e ? atoi(e) : 8; }   // measured: 16 / 8 / 4 columns per thread -> prologue 1.40 / 1.27 / 1.29 ms at n = 1e6, p = 500
-        const int MCGv = mcg == 4 ? 4 : (mcg == 16 ? 16 : 8);
-        const int cg = (m + MCGv - 1) / MCGv;
+        const int cg = (m + BF16_K1_COLS - 1) / BF16_K1_COLS;
         int S = std::max(1, (ctx->cus * 8 + cg - 1) / cg);
         int64_t chunk = ((n + S - 1) / S + 2047) / 2048 * 2048;      // multiple of 8 rows x 256 threads
         S = (int)std::max<int64_t>(1, (n + chunk - 1) / chunk);
         JCH_TRY(jch_reserve(ctx, ctx->colpart, sizeof(double) * ((size_t)S * m + 4096)));
         double *colpart = (double *)ctx->colpart.ptr;
-#define JCH_K1B(V, M) hipLaunchKernelGGL((k_moments_bf16_v8<V, M>), dim3(cg, S), dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, d, n, p, q, chunk, means, colpart)
-        if (means) { if (MCGv == 4) JCH_K1B(true, 4); else if (MCGv == 8) JCH_K1B(true, 8); else JCH_K1B(true, 16); }
-        else { if (MCGv == 4) JCH_K1B(false, 4); else if (MCGv == 8) JCH_K1B(false, 8); else JCH_K1B(false, 16); }
-#undef JCH_K1B
+        if (means) hipLaunchKernelGGL(k_moments_bf16_v8<true>, dim3(cg, S), dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, d, n, p, q, chunk, means, colpart);
+        else hipLaunchKernelGGL(k_moments_bf16_v8<false>, dim3(cg, S), dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, d, n, p, q, chunk, means, colpart);
         hipLaunchKernelGGL(k_colreduce_b, dim3((m + 63) / 64), dim3(1024), 0, ctx->stream, colpart, S, m, out);
         JCH_TRY(jch_allreduce_f64(ctx, out, (size_t)m));
         if (means) hipLaunchKernelGGL(k_sqrt_b, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, out, m);
@@ -269,7 +266,7 @@ __global__ __launch_bounds__(256) void k_center_xty_bf16_v8(const bf16_t *__rest
                                                              int64_t ldy, const double *__restrict__ d, int64_t n, int p, int q,
                                                              const double *__restrict__ mom, const double *__restrict__ scl,
                                                              bf16_t *__restrict__ Xr, int ldr, double *__restrict__ Yr, int qpad,
-                                                             double *__restrict__ Kpart, int kp_rows, int ones_col, int dbg_skip)
+                                                             double *__restrict__ Kpart, int kp_rows, int ones_col)
 {
     __shared__ double yt[64 * YT_LD];
     // The X tile lives in LDS as RAW bf16 only, COLUMN-major [col][XR_LD rows] (9 KB instead of a 33 KB fp64 tile: 8 blocks per
@@ -342,7 +339,7 @@ __global__ __launch_bounds__(256) void k_center_xty_bf16_v8(const bf16_t *__rest
         }
         __syncthreads();
         if (c + gridDim.x < nchunks) prefetch(c + gridDim.x);
-        if (yg == 0 && !(dbg_skip & 2)) {
+        if (yg == 0) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int row = (2 * wv + k) * 8 + (lane >> 3), cg = lane & 7;
@@ -404,8 +401,7 @@ __global__ __launch_bounds__(256) void k_reduce_kpart_b(const double *__restrict
 // is converted, multiplied and stored.  Handles FULL tiles only (rows [0, nfull), nfull % TH == 0); the ragged tail
 // goes to k_center_xty_bf16_v8.  q <= 16, 16-B aligned columns / weights.
 typedef unsigned long long v2u64b __attribute__((ext_vector_type(2)));
-// SKIP (measurement only, results then wrong by design): 1 = no products, 2 = no LDS tile / row-major stores
-template <int NT, int NH, bool SCAL, int SKIP>
+template <int NT, int NH, bool SCAL>
 __global__ __launch_bounds__(256, NH <= 2 ? 2 : 1) void k_center_xty_bf16_panel(
     const bf16_t *__restrict__ Xc, int64_t ldx, const bf16_t *__restrict__ Yc, int64_t ldy, const double *__restrict__ d, int64_t nfull,
     int p, int q, const double *__restrict__ mom, const double *__restrict__ scl, bf16_t *__restrict__ Xr, int ldr,
@@ -503,10 +499,10 @@ __global__ __launch_bounds__(256, NH <= 2 ? 2 : 1) void k_center_xty_bf16_panel(
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const unsigned w = w4[e >> 1];
-                    if (!(SKIP & 2)) xw[(32 * h + e) * pitch] = (bf16_t)((e & 1) ? (w >> 16) : w);
+                    xw[(32 * h + e) * pitch] = (bf16_t)((e & 1) ? (w >> 16) : w);
                     double a = (double)__uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16)) - cm;
                     if (SCAL) a /= cs;
-                    if (!(SKIP & 1)) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bs[(8 * h + e) * 64 + lane], acc[ct], 0, 0, 0);
+                    acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bs[(8 * h + e) * 64 + lane], acc[ct], 0, 0, 0);
                 }
             }
             if (ct + RING < NT) issue_piece(i0, ct + RING);                                      // (folded: the loop is unrolled)
@@ -515,7 +511,7 @@ __global__ __launch_bounds__(256, NH <= 2 ? 2 : 1) void k_center_xty_bf16_panel(
         __syncthreads();   // tile complete in LDS; every wave is done reading Bs
         if (decltype(has_next)::value) build_b(i0 + istep);
         // ---- the tile leaves as complete rows: wave wv stores rows wv, wv + 4, ...; 16 B per lane
-        if (!(SKIP & 2)) {
+        {
             const int c16n = wcols >> 3;
 #pragma unroll 4
             for (int row = wv; row < TH; row += 4) {
@@ -751,7 +747,7 @@ __device__ __forceinline__ void wave_sum_rows(float (&s)[R], float (&t)[R])
 
 // ---------------------------------------------------------------- K4 (bf16 storage): fused sweep, fp32 row arithmetic
 // lane l owns columns 8l..8l+7 (+512k): one 16-B load per row chunk.  rt, off: see the header comment.
-template <int KC, int R, bool PF>
+template <int KC, int R>
 __global__ __launch_bounds__(256) void k_sweep_bf16(const bf16_t *__restrict__ Xr, int64_t n, int ldr, const double *__restrict__ dw,
                                                     const double *__restrict__ rvec, const double *__restrict__ mom,
                                                     const double *__restrict__ scl, int p,
@@ -813,7 +809,7 @@ __global__ __launch_bounds__(256) void k_sweep_bf16(const bf16_t *__restrict__ X
 #pragma unroll
             for (int k = 0; k < KC; ++k) x[rr][k] = xn[rr][k];
         }
-        if (PF && g + gstride < ngroups) fetch(g + gstride);
+        if (g + gstride < ngroups) fetch(g + gstride);
         double tsel = 0.0;
         float sp[R], tr[R];
 #pragma unroll
@@ -843,7 +839,6 @@ __global__ __launch_bounds__(256) void k_sweep_bf16(const bf16_t *__restrict__ X
             if (lane == rr) tsel = (double)t;
         }
         if (lane < R && row0 + lane < n) tcol[row0 + lane] = tsel;
-        if (!PF && g + gstride < ngroups) fetch(g + gstride);
     }
     double *zred = red;                 // [4][KC*512]
     double *tred = red + 4 * KC * 512;  // [8]
@@ -913,7 +908,7 @@ __device__ __forceinline__ constexpr int bf_rowsum_lane(int rr)
     return 16 * (((rr & 3) == 1) ? 2 : ((rr & 3) == 2) ? 1 : (rr & 3)) + (R == 8 ? 8 * (rr >> 2) : 0);
 }
 
-template <int KC, int R, int NBUF = 2>   // NBUF register buffers in rotation: NBUF - 1 row groups in flight behind the one being reduced
+template <int KC, int R>
 __global__ __launch_bounds__(256) void k_sweep_bf16_v2(const bf16_t *__restrict__ Xr, int64_t n, int ldr, const double *__restrict__ dw,
                                                        const double *__restrict__ rvec, const double *__restrict__ mom,
                                                        const double *__restrict__ scl, int p,
@@ -929,6 +924,7 @@ __global__ __launch_bounds__(256) void k_sweep_bf16_v2(const bf16_t *__restrict_
     }
     const int64_t ngroups = (n + R - 1) / R;
     const int64_t gstride = (int64_t)gridDim.x * 4;
+    constexpr int NBUF = 2;   // register buffers in rotation: NBUF - 1 row groups in flight behind the one being reduced
     v4u32 X[NBUF][R][KC];
     double D[NBUF][R];   // (kept as loaded: converting here would make the prefetch wait for its own loads)
     auto fetch = [&](v4u32 (&xb)[R][KC], double (&db)[R], int64_t gg) {
@@ -1045,7 +1041,7 @@ __global__ __launch_bounds__(256) void k_bf16_fix_zt(const double *__restrict__ 
     if (j == 0) zt_small[ldr_small] = tt;
 }
 
-template <int KC, int R, bool PF = true>
+template <int KC, int R>
 static int32_t launch_sweep_bf16_t(jch_ctx *ctx, const bf16_t *Xr, int64_t n, int ldr_b, const double *d, const double *rvec,
                                    const double *mom, const double *scl, int p, double *tcol, double *zt8, int ldzb, int *nslice)
 {
@@ -1054,28 +1050,26 @@ static int32_t launch_sweep_bf16_t(jch_ctx *ctx, const bf16_t *Xr, int64_t n, in
     static jch_per_device_once occ_once;
     if (!occ_once.done(ctx->device)) {
         int nblk = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_bf16<KC, R, PF>, 256, lds);
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_bf16<KC, R>, 256, lds);
         bpc = (e == hipSuccess && nblk > 0) ? nblk : 2;
         if (lds > 64 * 1024)
-            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_sweep_bf16<KC, R, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_sweep_bf16<KC, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         occ_once.mark(ctx->device);
     }
     const int64_t ngroups = (n + R - 1) / R;
-    static int bpc_env = -1;
-    if (bpc_env < 0) { const char *e = getenv("JCH_BF16_BPC"); bpc_env = e ? atoi(e) : 0; }
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * (bpc_env > 0 ? bpc_env : bpc)));
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * bpc));
     const int m = ldr_b + 2, ldpart = (m + 7) & ~7;
     JCH_TRY(jch_reserve(ctx, ctx->part, sizeof(double) * (size_t)nb * ldpart));
     double *part = (double *)ctx->part.ptr;
     (void)jch_ev(ctx);
-    hipLaunchKernelGGL((k_sweep_bf16<KC, R, PF>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr_b, d, rvec, mom, scl, p, tcol, part, ldpart);
+    hipLaunchKernelGGL((k_sweep_bf16<KC, R>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr_b, d, rvec, mom, scl, p, tcol, part, ldpart);
     (void)jch_ev(ctx);
     JCH_TRY(jch_launch_reduce_part8(ctx, part, nb, ldpart, m, zt8, ldzb, nslice));
     JCH_HIP(ctx, hipGetLastError());
     return JCH_OK;
 }
 
-template <int KC, int R, int NBUF = 2>
+template <int KC, int R>
 static int32_t launch_sweep_bf16_v2_t(jch_ctx *ctx, const bf16_t *Xr, int64_t n, int ldr_b, const double *d, const double *rvec,
                                       const double *mom, const double *scl, int p, double *tcol, double *zt8, int ldzb, int *nslice,
                                       jch_part_view *pv = nullptr /*split small-state path on one rank / with the per-block inbox: leave the block partials unreduced*/)
@@ -1085,23 +1079,20 @@ static int32_t launch_sweep_bf16_v2_t(jch_ctx *ctx, const bf16_t *Xr, int64_t n,
     static jch_per_device_once occ_once;
     if (!occ_once.done(ctx->device)) {
         int nblk = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_bf16_v2<KC, R, NBUF>, 256, lds);
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_bf16_v2<KC, R>, 256, lds);
         bpc = (e == hipSuccess && nblk > 0) ? nblk : 2;
         if (lds > 64 * 1024)
-            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_sweep_bf16_v2<KC, R, NBUF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_sweep_bf16_v2<KC, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         occ_once.mark(ctx->device);
     }
     const int64_t ngroups = (n + R - 1) / R;
-    const char *eb = getenv("JCH_BF16_BPC");
-    const int use_bpc = (eb && atoi(eb) > 0) ? atoi(eb) : bpc;
-    int nb = (int)std::max<int64_t>(1, std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * use_bpc));
-    if (const char *e_nb = getenv("JCH_SWEEP_NB")) { const int v = atoi(e_nb); if (v > 0 && v < nb) nb = v; }   // (A/B runs: the grid)
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * bpc));
     const int m = ldr_b + 2, ldpart = (m + 7) & ~7;
     JCH_TRY(jch_reserve(ctx, ctx->part, sizeof(double) * (size_t)nb * ldpart));
     double *part = (double *)ctx->part.ptr;
     const bool timed = jch_prof_sample(ctx);
     if (timed) (void)jch_ev(ctx);
-    hipLaunchKernelGGL((k_sweep_bf16_v2<KC, R, NBUF>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr_b, d, rvec, mom, scl, p, tcol, part, ldpart);
+    hipLaunchKernelGGL((k_sweep_bf16_v2<KC, R>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr_b, d, rvec, mom, scl, p, tcol, part, ldpart);
     if (timed) (void)jch_ev(ctx);
     if (pv) { pv->part = part; pv->nb = nb; pv->ldpart = ldpart; *nslice = 1; JCH_HIP(ctx, hipGetLastError()); return JCH_OK; }
     JCH_TRY(jch_launch_reduce_part8(ctx, part, nb, ldpart, m, zt8, ldzb, nslice));
@@ -1160,8 +1151,7 @@ int32_t jch_fit_plskern_bf16(jch_ctx *ctx, const jch_pls_desc &d, const void *Xv
     // RAW prologue (no scaling, 16-byte kernels, q <= 15): as in the f64 path (fit.hip) the means pass over X is dropped —
     // K2 subtracts a pivot (mean of a strided row sample) instead of the means and multiplies against [Yc | 1], so
     // the means come out of the XtY pass: mu = pivot + K[:, q].
-    const bool raw_b = !d.scal && q <= 15 && ldx % 8 == 0 && ((uintptr_t)Xc) % 16 == 0 && !getenv("JCH_BF16_SCALAR_PROLOGUE") &&
-                       !getenv("JCH_CENTRED_COPY");
+    const bool raw_b = !d.scal && q <= 15 && ldx % 8 == 0 && ((uintptr_t)Xc) % 16 == 0 && !jch_knob_set("JCH_CENTRED_COPY");
     if (raw_b) {
         hipLaunchKernelGGL(k_pivot_rows_bf16, dim3((p + 3) / 4), dim3(256), 0, ctx->stream, Xc, ldx, n, p, s.hdr, s.scl);
         JCH_TRY(jch_allreduce_f64(ctx, s.scl, (size_t)p));
@@ -1175,31 +1165,25 @@ int32_t jch_fit_plskern_bf16(jch_ctx *ctx, const jch_pls_desc &d, const void *Xv
     {
         const int ptiles = (ldr_b + 63) / 64, kp_rows = ptiles * 64, ygroups = qpad / 16;
         const int64_t nchunks = (n + 63) / 64;
-        static int k2skip = -1;
-        if (k2skip < 0) { const char *e = getenv("JCH_K2_SKIP"); k2skip = e ? atoi(e) : 0; }
-        static int k2bpc = -1;
-        if (k2bpc < 0) { const char *e = getenv("JCH_BF16_K2_BPC"); k2bpc = e ? atoi(e) : 3; }
-        int nbx = std::max(1, (ctx->cus * k2bpc + ptiles * ygroups - 1) / (ptiles * ygroups));
+        int nbx = std::max(1, (ctx->cus * 3 + ptiles * ygroups - 1) / (ptiles * ygroups));
         if (nbx > nchunks) nbx = (int)std::max<int64_t>(nchunks, 1);
         JCH_TRY(jch_reserve(ctx, ctx->kpart, sizeof(double) * (size_t)nbx * kp_rows * qpad));
         double *Kpart = (double *)ctx->kpart.ptr;
         dim3 grid(nbx, ptiles, ygroups);
-        const bool v8 = ldx % 8 == 0 && ((uintptr_t)Xc) % 16 == 0 && !getenv("JCH_BF16_SCALAR_PROLOGUE");
+        const bool v8 = ldx % 8 == 0 && ((uintptr_t)Xc) % 16 == 0;
         // row-panel kernel (round 3, default): q <= 16, 16-B aligned X / Y columns and weights, at least one full row tile
-        // (measurement knobs, read on every call so that one process can compare the variants)
-        const char *e_pn = getenv("JCH_BF16_K2_PANEL"), *e_nh = getenv("JCH_BF16_K2_NH"), *e_pb = getenv("JCH_BF16_K2_PBPC");
-        const int k2panel = e_pn ? atoi(e_pn) : 1, k2nh = e_nh ? atoi(e_nh) : 2, k2pbpc = e_pb ? atoi(e_pb) : 0;
-        const int NHv = k2nh == 4 ? 4 : 2, THv = 32 * NHv;
+        // (JCH_BF16_K2_PANEL=0: the tile kernel; JCH_BF16_K2_NH=4: 128-row tiles)
+        const int k2panel = jch_knob("JCH_BF16_K2_PANEL", 1);
+        const int NHv = jch_knob("JCH_BF16_K2_NH", 2) == 4 ? 4 : 2, THv = 32 * NHv;
         const int64_t nfull = (n / THv) * THv;
         const bool panel = k2panel && v8 && qpad == 16 && ldy % 8 == 0 && ((uintptr_t)Yc) % 16 == 0 && ((uintptr_t)dn) % 16 == 0 && nfull > 0;
         // unit weights, raw mode: the products on the bf16 matrix pipe (k_xty_bf16_panel_m32; JCH_BF16_K2_M32=0: the f64 products)
-        const char *e_m32 = getenv("JCH_BF16_K2_M32");
-        m32 = panel && raw_b && !wdev && !(e_m32 && atoi(e_m32) == 0) && NHv == 2;
+        m32 = panel && raw_b && !wdev && jch_knob("JCH_BF16_K2_M32", 1) != 0 && NHv == 2;
         if (m32) {
             const int ncg = (ldr_b + 511) / 512;
             const int wmax = std::min(ldr_b, 512), ntile = (wmax + 63) / 64;
             const int NTv = ntile <= 1 ? 1 : (ntile <= 2 ? 2 : (ntile <= 4 ? 4 : 8));
-            const int bpc = k2pbpc > 0 ? k2pbpc : 2;
+            const int bpc = 2;
             int G = std::max(1, ctx->cus * bpc / ncg);
             G = (int)std::min<int64_t>(G, nfull / THv);
             const int kpr = ncg * 512;
@@ -1223,7 +1207,7 @@ int32_t jch_fit_plskern_bf16(jch_ctx *ctx, const jch_pls_desc &d, const void *Xv
             const int ncg = (ldr_b + 511) / 512;                       // 512-column groups (blockIdx.y)
             const int wmax = std::min(ldr_b, 512), ntile = (wmax + 63) / 64;
             const int NTv = ntile <= 1 ? 1 : (ntile <= 2 ? 2 : (ntile <= 4 ? 4 : 8));
-            const int bpc = k2pbpc > 0 ? k2pbpc : (NHv == 2 ? 2 : 1);
+            const int bpc = NHv == 2 ? 2 : 1;
             int G = std::max(1, ctx->cus * bpc / ncg);
             G = (int)std::min<int64_t>(G, nfull / THv);
             const int kpr = ncg * 512;
@@ -1233,37 +1217,32 @@ int32_t jch_fit_plskern_bf16(jch_ctx *ctx, const jch_pls_desc &d, const void *Xv
             const size_t lds = sizeof(double) * (8 * NHv * 64 + (d.scal ? 1024 : 512)) + sizeof(bf16_t) * (size_t)THv * 516 + 16;
             const double *momp = raw_b ? s.scl : s.mom;
             const int onesc = raw_b ? q : -1;
-#define JCH_K2PB_S(NT, NH, SC, SK) do { \
+#define JCH_K2PB(NT, NH, SC) do { \
                 static jch_per_device_once once_; \
-                if (!once_.done(ctx->device)) { JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_center_xty_bf16_panel<NT, NH, SC, SK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once_.mark(ctx->device); } \
-                hipLaunchKernelGGL((k_center_xty_bf16_panel<NT, NH, SC, SK>), dim3(G, ncg), dim3(256), lds, ctx->stream, Xc, ldx, Yc, ldy, dn, nfull, p, q, momp, s.scl, \
+                if (!once_.done(ctx->device)) { JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_center_xty_bf16_panel<NT, NH, SC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once_.mark(ctx->device); } \
+                hipLaunchKernelGGL((k_center_xty_bf16_panel<NT, NH, SC>), dim3(G, ncg), dim3(256), lds, ctx->stream, Xc, ldx, Yc, ldy, dn, nfull, p, q, momp, s.scl, \
                                    Xr, ldr_b, Yr, Kpart, kpr, onesc); } while (0)
-#define JCH_K2PB(NT, NH, SC) JCH_K2PB_S(NT, NH, SC, 0)
 #define JCH_K2PB_NT(NH, SC) do { if (NTv == 1) JCH_K2PB(1, NH, SC); else if (NTv == 2) JCH_K2PB(2, NH, SC); else if (NTv == 4) JCH_K2PB(4, NH, SC); else JCH_K2PB(8, NH, SC); } while (0)
-            if (NHv == 2 && NTv == 8 && !d.scal && (k2skip & 3)) {   // measurement variants of the headline instantiation
-                if ((k2skip & 3) == 1) JCH_K2PB_S(8, 2, false, 1); else if ((k2skip & 3) == 2) JCH_K2PB_S(8, 2, false, 2); else JCH_K2PB_S(8, 2, false, 3);
-            } else
             if (NHv == 2) { if (d.scal) JCH_K2PB_NT(2, true); else JCH_K2PB_NT(2, false); }
             else { if (d.scal) JCH_K2PB_NT(4, true); else JCH_K2PB_NT(4, false); }
 #undef JCH_K2PB_NT
 #undef JCH_K2PB
-#undef JCH_K2PB_S
             JCH_HIP(ctx, hipGetLastError());
             if (tail) {   // the last n % TH rows: the tile kernel on that row range, its partial in slot G
                 const int64_t nt = n - nfull;
                 dim3 tgrid(1, ptiles, 1);
                 double *kslot = Kpart + (size_t)G * kpr * 16;
                 if (d.scal) hipLaunchKernelGGL(k_center_xty_bf16_v8<true>, tgrid, dim3(256), 0, ctx->stream, Xc + nfull, ldx, Yc + nfull, ldy, dn + nfull, nt, p, q,
-                                               s.mom, s.scl, Xr + (size_t)nfull * ldr_b, ldr_b, Yr + (size_t)nfull * qpad, qpad, kslot, kpr, -1, k2skip);
+                                               s.mom, s.scl, Xr + (size_t)nfull * ldr_b, ldr_b, Yr + (size_t)nfull * qpad, qpad, kslot, kpr, -1);
                 else hipLaunchKernelGGL(k_center_xty_bf16_v8<false>, tgrid, dim3(256), 0, ctx->stream, Xc + nfull, ldx, Yc + nfull, ldy, dn + nfull, nt, p, q,
-                                        momp, s.scl, Xr + (size_t)nfull * ldr_b, ldr_b, Yr + (size_t)nfull * qpad, qpad, kslot, kpr, onesc, k2skip);
+                                        momp, s.scl, Xr + (size_t)nfull * ldr_b, ldr_b, Yr + (size_t)nfull * qpad, qpad, kslot, kpr, onesc);
             }
             hipLaunchKernelGGL(k_reduce_kpart_bw, dim3((p * qpad + 63) / 64), dim3(256), 0, ctx->stream, Kpart, G + (tail ? 1 : 0), kpr, p, qpad, s.K);
         } else
         if (v8 && d.scal) hipLaunchKernelGGL(k_center_xty_bf16_v8<true>, grid, dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, dn, n, p, q, s.mom,
-                                             s.scl, Xr, ldr_b, Yr, qpad, Kpart, kp_rows, -1, k2skip);
+                                             s.scl, Xr, ldr_b, Yr, qpad, Kpart, kp_rows, -1);
         else if (v8) hipLaunchKernelGGL(k_center_xty_bf16_v8<false>, grid, dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, dn, n, p, q,
-                                        raw_b ? s.scl : s.mom, s.scl, Xr, ldr_b, Yr, qpad, Kpart, kp_rows, raw_b ? q : -1, k2skip);
+                                        raw_b ? s.scl : s.mom, s.scl, Xr, ldr_b, Yr, qpad, Kpart, kp_rows, raw_b ? q : -1);
         else if (d.scal) hipLaunchKernelGGL(k_center_xty_bf16<true>, grid, dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, dn, n, p, q, s.mom,
                                        s.scl, Xr, ldr_b, Yr, qpad, Kpart, kp_rows);
         else hipLaunchKernelGGL(k_center_xty_bf16<false>, grid, dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, dn, n, p, q, s.mom,
@@ -1285,42 +1264,23 @@ int32_t jch_fit_plskern_bf16(jch_ctx *ctx, const jch_pls_desc &d, const void *Xv
     JCH_TRY(jch_launch_lv_update(ctx, s, p, q, qpad, ldr_small, -1, nlv, 0, 1, ldz, fast));
     for (int a = 0; a < nlv; ++a) {
         double *tcol = Tdev + (size_t)a * (size_t)n;
-        static int rsel = -1;
-        if (rsel < 0) { const char *e = getenv("JCH_BF16_R"); rsel = e ? atoi(e) : 4; }   // measured at n = 1e6, p = 500 with the prefetch: R = 2 / 4 / 8 -> 5.35 / 5.84 / 5.40 TB/s (without: 4.67 / 5.07)
         int nslice = 1;
         jch_part_view pv;
-        const bool fuse_now = fast && ctx->p2p.ready && !ctx->loop && !getenv("JCH_P2P_UNFUSED") && (size_t)(ldr_b + 2) <= ctx->p2p.cap;
+        const bool fuse_now = fast && ctx->p2p.ready && !ctx->loop && (size_t)(ldr_b + 2) <= ctx->p2p.cap;
         jch_part_view *pvp = (fast && s.kr && (ctx->nranks == 1 || fuse_now)) ? &pv : nullptr;   // split path: k_lv_spread sums the block partials
-        {   // v2 kernels (permlane row sums, rotating buffers); JCH_BF16_V2=0 selects the round-1 kernels below (read per call)
-            const char *e2 = getenv("JCH_BF16_V2");
-            const int v2 = e2 ? atoi(e2) : 1;
-            if (v2 && ldr_b >= 8 && ldr_b <= 1024) {
-                // (Measured, round 4: deeper rotations of the row-group buffers, NBUF template parameter — <1,8,3> 221-225 us per launch at
-                // n = 1e6 (one wave per SIMD), <1,4,4> 196-201, <1,4,3> 164-168 against 160-168 for the default <1,8,2>; n = 8e6: 1 575 /
-                // 1 338 against 1 282 — more bytes in flight per wave do not make up for the waves they cost.)
-                if (ldr_b <= 512) { if (v2 == 4) JCH_TRY((launch_sweep_bf16_v2_t<1, 4>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice, pvp)));
-                                    else JCH_TRY((launch_sweep_bf16_v2_t<1, 8>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice, pvp))); }
-                else JCH_TRY((launch_sweep_bf16_v2_t<2, 8>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice, pvp)));
-                goto swept;
-            }
-        }
-#define JCH_SWB(KC, R) JCH_TRY((launch_sweep_bf16_t<KC, R>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice)))
-        static int pfsel = -1;
-        if (pfsel < 0) { const char *e = getenv("JCH_BF16_PF"); pfsel = e ? atoi(e) : 1; }
-        if (ldr_b <= 512 && rsel == 4 && !pfsel) JCH_TRY((launch_sweep_bf16_t<1, 4, false>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice)));
-        else if (ldr_b <= 512 && rsel == 2 && !pfsel) JCH_TRY((launch_sweep_bf16_t<1, 2, false>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice)));
-        else if (ldr_b <= 512 && rsel == 4) JCH_SWB(1, 4);
-        else if (ldr_b <= 512 && rsel == 2) JCH_SWB(1, 2);
-        else if (ldr_b <= 512) JCH_SWB(1, 8);
-        else if (ldr_b <= 1024) JCH_SWB(2, 4);
-        else JCH_SWB(4, 2);
-#undef JCH_SWB
-    swept:;
+        // v2 kernels (permlane row sums, two rotating buffers) up to 1024 columns, 8 rows per wave-iteration.  (Measured, round 4:
+        // deeper rotations of the row-group buffers — <1,8,3> 221-225 us per launch at n = 1e6 (one wave per SIMD), <1,4,4> 196-201,
+        // <1,4,3> 164-168 against 160-168 for the default <1,8,2>; n = 8e6: 1 575 / 1 338 against 1 282 — more bytes in flight per wave
+        // do not make up for the waves they cost.  Round-1 kernel at n = 1e6, p = 500 with the prefetch: R = 2 / 4 / 8 -> 5.35 / 5.84 /
+        // 5.40 TB/s (without: 4.67 / 5.07).)
+        if (ldr_b <= 512) JCH_TRY((launch_sweep_bf16_v2_t<1, 8>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice, pvp)));
+        else if (ldr_b <= 1024) JCH_TRY((launch_sweep_bf16_v2_t<2, 8>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice, pvp)));
+        else JCH_TRY((launch_sweep_bf16_t<4, 2>(ctx, Xr, n, ldr_b, dn, s.r, s.mom, s.scl, p, tcol, zt8, ldzb, &nslice)));   // wider rows: the round-1 kernel (prefetched)
         if (ctx->nranks > 1) nslice = JCH_ZT_SLICES;                      // rank-independent message size (unused slices hold zeros)
         // ONE collective per LV: [zp_raw, tt, st].  Fast small-state kernel: it adds the slices, (with the inbox transport)
         // all-reduces them and applies the centring / scaling fix-up itself; generic kernel: separate steps.
         if (fast) {
-            const bool fuse = ctx->p2p.ready && !ctx->loop && !getenv("JCH_P2P_UNFUSED") && (size_t)(ldr_b + 2) <= ctx->p2p.cap;
+            const bool fuse = ctx->p2p.ready && !ctx->loop && (size_t)(ldr_b + 2) <= ctx->p2p.cap;
             if (!fuse && !pv.part) JCH_TRY(jch_allreduce_slices(ctx, zt8, ldr_b + 2, nslice, ldzb, &nslice));
             else if (fuse) ctx->coll_transport = JCH_TRANSPORT_INBOX_FUSED;
             if (s.kr) {   // split small-state path (smallstate_split.hip): the partial rows / slices are summed (and, with the inbox, exchanged) by its p-parallel kernel

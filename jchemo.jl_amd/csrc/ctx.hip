@@ -24,6 +24,15 @@ int32_t jch_fail(jch_ctx *ctx, int32_t code, const char *fmt, ...)
     return code;
 }
 
+// The library's only readers of the environment (switches that survive: DESIGN.md §5c).  Nothing caches a value: a switch is
+// read when the exported call that consults it starts, so a change between two calls on the same ctx takes effect.
+bool jch_knob_set(const char *name) { return getenv(name) != nullptr; }
+int jch_knob(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
 extern "C" int32_t jch_version(void) { return JCH_VERSION; }
 
 extern "C" const char *jch_last_error(const jch_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
@@ -49,8 +58,6 @@ extern "C" int32_t jch_ctx_create(jch_ctx **out, int32_t device_id, void *stream
     if (!ctx) return jch_fail(nullptr, JCH_ENOMEM, "jch_ctx_create: host allocation failed");
     ctx->device = device_id;
     ctx->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    // JCH_CUS=<count> (measurement knob, A/B runs): size every persistent grid as if the device had this many CUs
-    if (const char *e_cus = getenv("JCH_CUS")) { const int v = atoi(e_cus); if (v >= 8 && v <= ctx->cus) ctx->cus = v; }
     e = hipSetDevice(device_id);
     if (e == hipSuccess) {
         if (stream) {
@@ -64,7 +71,6 @@ extern "C" int32_t jch_ctx_create(jch_ctx **out, int32_t device_id, void *stream
         delete ctx;
         return jch_fail(nullptr, JCH_EHIP, "jch_ctx_create: %s", hipGetErrorString(e));
     }
-    if (const char *s = getenv("JCH_SWEEP_BLOCKS_PER_CU")) ctx->sweep_blocks_per_cu = atoi(s);
     *out = ctx;
     return JCH_OK;
 }
@@ -116,8 +122,7 @@ int32_t jch_reserve(jch_ctx *ctx, jch_buf &b, size_t bytes)
         return jch_fail(ctx, JCH_ENOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
     }
     b.bytes = bytes;
-    static const bool trace = getenv("JCH_TRACE_ALLOC") != nullptr;
-    if (trace && bytes >= (1u << 20)) fprintf(stderr, "[jch] workspace %p  %zu bytes\n", b.ptr, bytes);
+    if (jch_knob_set("JCH_TRACE_ALLOC") && bytes >= (1u << 20)) fprintf(stderr, "[jch] workspace %p  %zu bytes\n", b.ptr, bytes);
     return JCH_OK;
 }
 

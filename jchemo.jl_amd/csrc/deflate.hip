@@ -116,11 +116,11 @@ __global__ __launch_bounds__(256) void k_reduce_kpart2(const double *__restrict_
 // no LDS transpose, 16-B coalesced loads and stores, K_next accumulated like zp.  Per-block partials
 // part[b][k * ldr + c] are summed in fixed order by k_reduce_kstream (deterministic).
 typedef double v2f64 __attribute__((ext_vector_type(2)));
-template <int KC, int R, int Q, bool PF>
+template <int KC, int R, int Q>
 __global__ __launch_bounds__(256) void k_deflate_stream(double *__restrict__ Xr, int64_t n, int ldr, double *__restrict__ Yr,
                                                          int qpad, const double *__restrict__ dw,
                                                          const double *__restrict__ tcol, const double *__restrict__ zpc,
-                                                         double *__restrict__ part, int ldpart, int plain_stores)
+                                                         double *__restrict__ part, int ldpart)
 {
     extern __shared__ __attribute__((aligned(16))) double red[];  // [4][Q][KC*128]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void k_deflate_stream(double *__restrict__ Xr,
     const int64_t ngroups = (n + R - 1) / R;
     const int64_t gstride = (int64_t)gridDim.x * 4;
     // software prefetch: rows, scores and weights of the wave's next group are requested before the current group is
-    // rewritten (JCH_DEFLATE_PF=0 restores the plain loop)
+    // rewritten
     v2f64 xn[R][KC];
     double tn[R], dn_[R];
     auto fetch = [&](int64_t gg) {
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void k_deflate_stream(double *__restrict__ Xr,
 #pragma unroll
             for (int k = 0; k < KC; ++k) x[rr][k] = xn[rr][k];
         }
-        if (PF && g + gstride < ngroups) fetch(g + gstride);
+        if (g + gstride < ngroups) fetch(g + gstride);
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) {
             const int64_t row = row0 + rr;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void k_deflate_stream(double *__restrict__ Xr,
                 for (int k = 0; k < KC; ++k) {
                     x[rr][k].x -= t * zpf[k].x;
                     x[rr][k].y -= t * zpf[k].y;
-                    if (in[k]) { if (plain_stores) wp[64 * k] = x[rr][k]; else __builtin_nontemporal_store(x[rr][k], wp + 64 * k); }
+                    if (in[k]) __builtin_nontemporal_store(x[rr][k], wp + 64 * k);
                 }
 #pragma unroll
                 for (int y = 0; y < Q; ++y) {
@@ -194,7 +194,6 @@ __global__ __launch_bounds__(256) void k_deflate_stream(double *__restrict__ Xr,
                 }
             }
         }
-        if (!PF && g + gstride < ngroups) fetch(g + gstride);
     }
     double *prow = part + (size_t)blockIdx.x * ldpart;
 #pragma unroll
@@ -234,8 +233,8 @@ __global__ __launch_bounds__(1024) void k_reduce_kstream(const double *__restric
     }
 }
 
-template <int KC, int R, int Q, bool PF>
-static int32_t launch_deflate_stream_pf(jch_ctx *ctx, double *Xr, int64_t n, int p, int ldr, double *Yr, int qpad, const double *d,
+template <int KC, int R, int Q>
+static int32_t launch_deflate_stream(jch_ctx *ctx, double *Xr, int64_t n, int p, int ldr, double *Yr, int qpad, const double *d,
                                      const double *tcol, const double *zpc, double *Knext)
 {
     const size_t lds = sizeof(double) * 4 * Q * KC * 128;
@@ -243,25 +242,21 @@ static int32_t launch_deflate_stream_pf(jch_ctx *ctx, double *Xr, int64_t n, int
     static jch_per_device_once occ_once;
     if (!occ_once.done(ctx->device)) {
         int nblk = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_deflate_stream<KC, R, Q, PF>, 256, lds);
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_deflate_stream<KC, R, Q>, 256, lds);
         bpc = (e == hipSuccess && nblk > 0) ? nblk : 2;
         if (lds > 64 * 1024)
-            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_deflate_stream<KC, R, Q, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_deflate_stream<KC, R, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         occ_once.mark(ctx->device);
     }
     const int64_t ngroups = (n + R - 1) / R;
-    // (measurement knobs, read per call: JCH_DEFLATE_BPC blocks per CU instead of the occupancy maximum, JCH_DEFLATE_NT=0 plain stores)
-    const char *e_bpc = getenv("JCH_DEFLATE_BPC"), *e_nt = getenv("JCH_DEFLATE_NT");
-    const int use_bpc = (e_bpc && atoi(e_bpc) > 0) ? std::min(atoi(e_bpc), bpc) : bpc;
-    const int plain_stores = (e_nt && atoi(e_nt) == 0) ? 1 : 0;
-    int64_t nb64 = std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * use_bpc);
+    int64_t nb64 = std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * bpc);
     const int nb = (int)std::max<int64_t>(nb64, 1);
     const int ldpart = (Q * ldr + 7) & ~7;
     JCH_TRY(jch_reserve(ctx, ctx->kpart, sizeof(double) * (size_t)nb * ldpart));
     double *part = (double *)ctx->kpart.ptr;
     (void)jch_ev(ctx);
-    hipLaunchKernelGGL((k_deflate_stream<KC, R, Q, PF>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, Yr, qpad, d, tcol, zpc,
-                       part, ldpart, plain_stores);
+    hipLaunchKernelGGL((k_deflate_stream<KC, R, Q>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, Yr, qpad, d, tcol, zpc,
+                       part, ldpart);
     (void)jch_ev(ctx);
     if (Knext) {
         // pad columns of K (y >= q) must stay zero: they are never written here and were zeroed by the prologue
@@ -271,16 +266,6 @@ static int32_t launch_deflate_stream_pf(jch_ctx *ctx, double *Xr, int64_t n, int
     }
     JCH_HIP(ctx, hipGetLastError());
     return JCH_OK;
-}
-
-template <int KC, int R, int Q>
-static int32_t launch_deflate_stream(jch_ctx *ctx, double *Xr, int64_t n, int p, int ldr, double *Yr, int qpad, const double *d,
-                                     const double *tcol, const double *zpc, double *Knext)
-{
-    static int pf = -1;
-    if (pf < 0) { const char *e = getenv("JCH_DEFLATE_PF"); pf = e ? atoi(e) : 1; }
-    if (pf) return launch_deflate_stream_pf<KC, R, Q, true>(ctx, Xr, n, p, ldr, Yr, qpad, d, tcol, zpc, Knext);
-    return launch_deflate_stream_pf<KC, R, Q, false>(ctx, Xr, n, p, ldr, Yr, qpad, d, tcol, zpc, Knext);
 }
 
 // ---- postponed write-back (see k_sweep_lazy, sweep.hip): the same pass as k_deflate_stream, but the rows in memory are
@@ -423,9 +408,7 @@ static int32_t launch_kpass_lazy_t(jch_ctx *ctx, double *Xr, int64_t n, int p, i
         once.mark(ctx->device);
     }
     if (lds > 160 * 1024) return jch_fail(ctx, JCH_EINVAL, "internal: lazy NIPALS pass: %zu bytes of LDS", lds);
-    const char *e_bpc = getenv("JCH_DEFLATE_BPC");
-    int use_bpc = (e_bpc && atoi(e_bpc) > 0) ? std::min(atoi(e_bpc), bpc) : bpc;
-    use_bpc = std::max(1, std::min<int>(use_bpc, (int)((160 * 1024) / lds)));
+    const int use_bpc = std::max(1, std::min<int>(bpc, (int)((160 * 1024) / lds)));
     const int64_t ngroups = (n + R - 1) / R;
     const int nb = (int)std::max<int64_t>(std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * use_bpc), 1);
     const int ldpart = (Q * ldr + 7) & ~7;
@@ -543,11 +526,8 @@ __global__ __launch_bounds__(1024) void k_reduce_kpart3(const double *__restrict
 // waves of a block share the rows of a chunk and split its spans (s = wave + 4 u), so the B operand d_i * y_i (with this
 // LV's Y step applied) and the pending scores are staged ONCE per chunk in LDS, double-buffered: one barrier per chunk,
 // nothing else.  Pending loadings of the lane's 2 NS columns sit in registers.  X is prefetched one chunk ahead.
-// NW (round 4): waves per block.  NW = 8 with half the spans per wave (NS = 2 at p <= 512) keeps a wave's state inside 256
-// registers, so TWO waves share a SIMD: one wave's products and pending corrections run while the other waits for its rows (with
-// one wave per SIMD at 337 registers 56 % of the wave cycles were issue stalls and nothing else was resident to use them).
-template <int NS, int STEPS, int MP, int MINB, int NW>
-__global__ __launch_bounds__(64 * NW, MINB) void k_kpass_mfma_lazy(double *__restrict__ Xr, int64_t n, int ldr, double *__restrict__ Yr, int q,
+template <int NS, int STEPS, int MP>
+__global__ __launch_bounds__(256, 1) void k_kpass_mfma_lazy(double *__restrict__ Xr, int64_t n, int ldr, double *__restrict__ Yr, int q,
                                                          const double *__restrict__ dw, const double *__restrict__ pend_p, int ldp, int npend,
                                                          const double *__restrict__ tpend, int64_t tstride, const double *__restrict__ cvec,
                                                          int flush, double *__restrict__ Kpart, int kp_rows)
@@ -562,7 +542,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_kpass_mfma_lazy(double *__res
     double pk[MP][NS][2];
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
-        const int col = 32 * (wv + NW * u) + 2 * c16;
+        const int col = 32 * (wv + 4 * u) + 2 * c16;
         in[u] = col < ldr;
         coff[u] = in[u] ? col : ldr - 2;
 #pragma unroll
@@ -577,10 +557,9 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_kpass_mfma_lazy(double *__res
     const int64_t nchunks = (n + RB - 1) / RB;
     const int knew = npend - 1;
     // staging roles: thread (row = tid >> 4, y = tid & 15) builds the B entry, thread (k = tid >> 4, row = tid & 15) a score
-    // (with NW = 8 the second 256 threads have no staging role: their srow / tk fall outside RB / npend <= MP <= 16 rows ... 15)
-    const int srow = tid < 256 ? tid >> 4 : RB, sy = tid & 15;
+    const int srow = tid >> 4, sy = tid & 15;
     const double cy = sy < q ? cvec[sy] : 0.0;
-    const int tk = tid < 256 ? tid >> 4 : MP, trow = tid & 15;
+    const int tk = tid >> 4, trow = tid & 15;
     // X is prefetched one whole chunk ahead.  (Rotating two buffers and re-requesting every consumed step for chunk c + 2 G
     // — 1.5 chunks in flight — was measured SLOWER for the read-only pass, 968 against 800 us at cfg2 shape: the loads then
     // queue behind each step's eight 64-cycle MFMAs instead of going out ahead of all of them.)
@@ -673,13 +652,13 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_kpass_mfma_lazy(double *__res
             for (int h = 0; h < 2; ++h)
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg) {
-                    const int j = 32 * (wv + NW * u) + 2 * (4 * reg + g) + h;
+                    const int j = 32 * (wv + 4 * u) + 2 * (4 * reg + g) + h;
                     if (j < kp_rows) kp[(size_t)j * 16 + c16] = acc[u][h][reg];
                 }
     }
 }
 
-template <int NS, int STEPS, int MP, int MINB = 1, int NW = 4>
+template <int NS, int STEPS, int MP>
 static int32_t launch_kpass_mfma_lazy_t(jch_ctx *ctx, double *Xr, int64_t n, int p, int ldr, double *Yr, int q, const double *d,
                                         const double *pend_p, int npend, const double *tpend, int64_t tstride, const double *cvec,
                                         bool flush, double *Knext)
@@ -687,14 +666,12 @@ static int32_t launch_kpass_mfma_lazy_t(jch_ctx *ctx, double *Xr, int64_t n, int
     constexpr int RB = 4 * STEPS;
     if (npend > MP) return jch_fail(ctx, JCH_EINVAL, "internal: lazy MFMA pass: %d pending corrections, at most %d", npend, MP);
     const int64_t nchunks = (n + RB - 1) / RB;
-    const char *e_bpc = getenv("JCH_DEFLATE_BPC");
-    const int bpc = (e_bpc && atoi(e_bpc) > 0) ? atoi(e_bpc) : MINB;
-    const int nb = (int)std::max<int64_t>(std::min<int64_t>(nchunks, (int64_t)ctx->cus * bpc), 1);
+    const int nb = (int)std::max<int64_t>(std::min<int64_t>(nchunks, (int64_t)ctx->cus), 1);   // one block per CU
     const int kp_rows = ldr;
     JCH_TRY(jch_reserve(ctx, ctx->kpart, sizeof(double) * (size_t)nb * kp_rows * 16));
     double *Kpart = (double *)ctx->kpart.ptr;
     (void)jch_ev(ctx);
-    hipLaunchKernelGGL((k_kpass_mfma_lazy<NS, STEPS, MP, MINB, NW>), dim3(nb), dim3(64 * NW), 0, ctx->stream, Xr, n, ldr, Yr, q, d, pend_p,
+    hipLaunchKernelGGL((k_kpass_mfma_lazy<NS, STEPS, MP>), dim3(nb), dim3(256), 0, ctx->stream, Xr, n, ldr, Yr, q, d, pend_p,
                        jch_nipals_lazy_pitch(ldr), npend, tpend, tstride, cvec, flush ? 1 : 0, Knext ? Kpart : nullptr, kp_rows);
     (void)jch_ev(ctx);
     if (Knext) {
@@ -741,22 +718,19 @@ int32_t jch_launch_kpass_lazy(jch_ctx *ctx, double *Xr, int64_t n, int p, int ld
     if (npend < 1 || npend > npend_max || npend_max > jch_nipals_lazy_capacity(ldr, q))
         return jch_fail(ctx, JCH_EINVAL, "internal: lazy NIPALS pass: bad pending count");
     if (!lazy_stream_shape(ldr, q)) {
-        if (qpad == 16 && ldr <= 1024 && !getenv("JCH_KPASS_TILE")) {   // (JCH_KPASS_TILE=1: the LDS-transposing tile kernel instead)
-#define JCH_KM(NS, STEPS, MP, ...) return launch_kpass_mfma_lazy_t<NS, STEPS, MP, ##__VA_ARGS__>(ctx, Xr, n, p, ldr, Yr, q, d, pend_p, npend, tpend, tstride, cvec, flush, Knext)
+        if (qpad == 16 && ldr <= 1024) {   // (wider rows: the LDS-transposing tile kernel below)
+#define JCH_KM(NS, STEPS, MP) return launch_kpass_mfma_lazy_t<NS, STEPS, MP>(ctx, Xr, n, p, ldr, Yr, q, d, pend_p, npend, tpend, tstride, cvec, flush, Knext)
             if (ldr <= 128) JCH_KM(1, 4, 6);
             if (ldr <= 256) JCH_KM(2, 4, 6);
             // (measured at cfg2 shape, read-only pass: 16-row chunks 800-845 us; 32-row chunks with 2 loadings 802; 8-row chunks
             // 914, with two blocks per CU and 3 loadings 745 — but rewriting every 3rd LV instead of every 6th costs as much;
             // 4-row chunks with two blocks per CU 896)
-            // round 4, measured and NOT the default (JCH_KPASS_NW=8): eight waves per block, two per SIMD, half the spans per wave
+            // round 4, measured and NOT adopted: eight waves per block, two per SIMD, half the spans per wave
             // (200 registers instead of 337).  plsnipals q = 10 at cfg2 shape: 548.5 LV/s against 550.8 with four waves (pass 1.682
             // against 1.675 ms per LV), plswold 523.7 against 534.9 — a second resident wave does not fill the issue stalls: the f64
             // products and the vector work of BOTH waves queue for the same SIMD (the pipe does not overlap them), and
             // the bytes in flight per CU are unchanged.
-            const char *e_nw = getenv("JCH_KPASS_NW");
-            const bool nw8 = e_nw && atoi(e_nw) == 8;
-            if (ldr <= 512) { if (nw8) JCH_KM(2, 4, 6, 1, 8); JCH_KM(4, 4, 6); }
-            if (nw8) JCH_KM(4, 2, 3, 1, 8);
+            if (ldr <= 512) JCH_KM(4, 4, 6);
             JCH_KM(8, 2, 3);
 #undef JCH_KM
         }
@@ -778,7 +752,7 @@ int32_t jch_launch_kpass_lazy(jch_ctx *ctx, double *Xr, int64_t n, int p, int ld
 int32_t jch_launch_deflate(jch_ctx *ctx, double *Xr, int64_t n, int p, int ldr, double *Yr, int qpad, int q,
                            const double *d, const double *tcol, const double *zpc, double *Knext)
 {
-    if (q <= 4 && !getenv("JCH_DEFLATE_TILE")) {
+    if (q <= 4) {
 #define JCH_DS(KC, R) do { \
         if (q == 1) return launch_deflate_stream<KC, R, 1>(ctx, Xr, n, p, ldr, Yr, qpad, d, tcol, zpc, Knext); \
         if (q == 2) return launch_deflate_stream<KC, R, 2>(ctx, Xr, n, p, ldr, Yr, qpad, d, tcol, zpc, Knext); \
@@ -788,12 +762,8 @@ int32_t jch_launch_deflate(jch_ctx *ctx, double *Xr, int64_t n, int p, int ldr, 
         if (ldr <= 512) JCH_DS(4, 2);
         if (ldr <= 1024) JCH_DS(8, 1);
         if (ldr <= 2048) {   // Q x KC accumulators: keep registers in check at the widest rows
-            if (q == 1) {
-                static int r2 = -1;
-                if (r2 < 0) { const char *e = getenv("JCH_DEFLATE_R2"); r2 = e ? atoi(e) : 1; }   // two rows per wave-iteration: 77.85 -> 77.2 ms per 10 LVs at cfg4 shape
-                if (r2) return launch_deflate_stream<16, 2, 1>(ctx, Xr, n, p, ldr, Yr, qpad, d, tcol, zpc, Knext);
-                return launch_deflate_stream<16, 1, 1>(ctx, Xr, n, p, ldr, Yr, qpad, d, tcol, zpc, Knext);
-            }
+            // q = 1: two rows per wave-iteration (77.85 -> 77.2 ms per 10 LVs at cfg4 shape against one)
+            if (q == 1) return launch_deflate_stream<16, 2, 1>(ctx, Xr, n, p, ldr, Yr, qpad, d, tcol, zpc, Knext);
             if (q == 2) return launch_deflate_stream<16, 1, 2>(ctx, Xr, n, p, ldr, Yr, qpad, d, tcol, zpc, Knext);
         }
 #undef JCH_DS

@@ -50,10 +50,8 @@ int32_t divcols(jch_ctx *ctx, double *A, int64_t lda, int64_t n, int64_t cols, c
 // rows of new data per Gram block: JCH_DKPLSR_QBLOCK, else 1 GiB of Gram (2^27 doubles)
 int64_t qblock(int64_t n)
 {
-    if (const char *e = getenv("JCH_DKPLSR_QBLOCK")) {
-        const long long v = atoll(e);
-        if (v >= 1) return v;
-    }
+    const int v = jch_knob("JCH_DKPLSR_QBLOCK", 0);
+    if (v >= 1) return v;
     return std::max<int64_t>(1, ((int64_t)1 << 27) / n);
 }
 

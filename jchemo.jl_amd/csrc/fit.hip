@@ -106,7 +106,7 @@ public:
     t_column_copier(jch_ctx *ctx, double *host_T, const double *dev_T, int64_t n, int ncols)
         : ctx_(ctx), host_(host_T), dev_(dev_T), n_(n)
     {
-        if (!host_T || ncols < 1 || getenv("JCH_HOST_T_OVERLAP_OFF")) return;
+        if (!host_T || ncols < 1) return;
         if (hipStreamCreateWithFlags(&cs_, hipStreamNonBlocking) != hipSuccess) { cs_ = nullptr; return; }
         ev_.resize((size_t)ncols, nullptr);
         for (auto &e : ev_)
@@ -215,18 +215,18 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     const jch_pls_desc &d = *io.d;
     const int64_t n = d.n;
     const int p = (int)d.p, q = (int)d.q;
-    // row pitch of the row-major working copy: a multiple of `ralign` doubles (pad columns are zero)
-    const char *e_al = getenv("JCH_LDR_ALIGN");
-    const int ralign = e_al ? std::max(2, atoi(e_al) & ~1) : 2;
-    const int ldr = std::min(((p + ralign - 1) / ralign) * ralign, std::max(JCH_SWEEP_MAXP, (p + 1) & ~1)), qpad = ((q + 15) / 16) * 16;
+    // row pitch of the row-major working copy: an even number of doubles (the pad column is zero)
+    const int ldr = (p + 1) & ~1, qpad = ((q + 15) / 16) * 16;
     const bool host = d.loc == JCH_LOC_HOST;
     const bool inplace = d.inplace != 0;
     ctx->ev_used = 0;
     ctx->prof = jch_profile{};
     jch_coll_reset(ctx);
     ctx->sweep_seq = 0;   // (JCH_SWEEP_ALT: every fit starts its walk in the same direction — repeated fits stay bit-identical)
+    ctx->sweep_alt = jch_knob("JCH_SWEEP_ALT", 0);
+    ctx->sweep_fused_reduce = jch_knob("JCH_SWEEP_FUSED_REDUCE", 0) == 1;
     // JCH_HOST_TIMING=1: host-side timeline of a fit on host arrays (stderr): where the wall time of the secondary metric goes
-    static const bool host_timing = getenv("JCH_HOST_TIMING") != nullptr;
+    const bool host_timing = jch_knob_set("JCH_HOST_TIMING");
     auto now_ms = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tl0 = now_ms();
     double tl_h2d = tl0, tl_enq = tl0, tl_sync = tl0;
@@ -237,7 +237,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     // from the copy (prologue.hip k_xty_rows); otherwise the bit changes nothing.
     const xcopy_key xkey{io.X, (int64_t)n, (int64_t)io.ldx, p, host ? 1 : 0};
     const bool reuse_x = (d.reserved & JCH_REUSE_XCOPY) && allow_raw && ctx->xcopy_valid && ctx->xcopy == xkey && d.dtype == JCH_F64 &&
-                         q + 1 <= 12 && ldr <= 512 && !getenv("JCH_NO_REUSE_XCOPY");
+                         q + 1 <= 12 && ldr <= 512 && !jch_knob_set("JCH_NO_REUSE_XCOPY");
     if (!reuse_x) ctx->xcopy_valid = false;   // (whatever this fit does to the workspace, the old copy is not to be trusted afterwards)
     // ---- inputs on the device (column-major as handed over)
     double *Xc = (double *)io.X, *Yc = (double *)io.Y;
@@ -312,14 +312,13 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         memcpy(&qual_host, h + ((const char *)qual_dev - (const char *)s.P), sizeof(double));
         return JCH_OK;
     };
-    s.dbg = getenv("JCH_LV_DEBUG") ? cv.take(512 + 16 * (nlv_cap + 2)) : nullptr;
+    s.dbg = jch_knob_set("JCH_LV_DEBUG") ? cv.take(512 + 16 * (nlv_cap + 2)) : nullptr;
     // plsnipals / plswold with a narrow Y: the rewrite of X after every LV is postponed and done every `defer_m`-th LV
     // (k_sweep_lazy / k_kpass_lazy; JCH_NIPALS_DEFER=1 restores the eager deflation)
     int defer_m = 1;
     double *pend_p = nullptr;
     if (!kern_like && d.dtype == JCH_F64) {
-        const char *e_m = getenv("JCH_NIPALS_DEFER");
-        defer_m = std::max(1, std::min(e_m ? atoi(e_m) : JCH_NIPALS_DEFER_DEFAULT, jch_nipals_lazy_capacity(ldr, q)));
+        defer_m = std::max(1, std::min(jch_knob("JCH_NIPALS_DEFER", JCH_NIPALS_DEFER_DEFAULT), jch_nipals_lazy_capacity(ldr, q)));
         if (defer_m > 1) pend_p = cv.take((size_t)defer_m * jch_nipals_lazy_pitch(ldr));
     }
 
@@ -332,11 +331,10 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     if (onepass) { zero16 = cv.take(16); JCH_HIP(ctx, hipMemsetAsync(zero16, 0, sizeof(double) * 16, ctx->stream)); s.variant = 3; }
     if (s.dbg) JCH_HIP(ctx, hipMemsetAsync(s.dbg, 0, sizeof(double) * (512 + 16 * (nlv_cap + 2)), ctx->stream));
     if (d.dtype == JCH_BF16) {   // bf16 storage mode (plskern only): its own prologue + sweep, same small-state kernels
-        const bool fastb = q <= 16 && p <= JCH_SWEEP_MAXP && jch_lv_fast_lds_bytes(p, q, qpad, ldr, nlv_cap) <= 150 * 1024 && !getenv("JCH_SMALLSTATE_GENERIC");
+        const bool fastb = q <= 16 && p <= JCH_SWEEP_MAXP && jch_lv_fast_lds_bytes(p, q, qpad, ldr, nlv_cap) <= 150 * 1024;
         {   // split small-state path (see the f64 loop below); the fused inbox exchange keeps the one-kernel path
-            const char *e_sp = getenv("JCH_LV_SPLIT");
-            const bool fuse_b = ctx->p2p.ready && !ctx->loop && !getenv("JCH_P2P_UNFUSED");
-            if (fastb && (!fuse_b || jch_lv_split_p2p_ok(ctx, p)) && !(e_sp && atoi(e_sp) == 0) && jch_lv_solve_lds_bytes(p, q, ldr, nlv_cap) <= 150 * 1024) {
+            const bool fuse_b = ctx->p2p.ready && !ctx->loop;
+            if (fastb && (!fuse_b || jch_lv_split_p2p_ok(ctx, p)) && jch_knob("JCH_LV_SPLIT", 1) != 0 && jch_lv_solve_lds_bytes(p, q, ldr, nlv_cap) <= 150 * 1024) {
                 s.kr = cv.take(16); JCH_TRY(jch_lv_split_begin_fit(ctx, s, cv.take(jch_lv_split_doubles(p, nlv_cap)), p, nlv_cap));
             }
         }
@@ -376,16 +374,16 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     }
     const int nlv = (int)std::min<int64_t>(std::min<int64_t>(n_total, p), d.nlv);
     // small-state fast path (smallstate_fast.hip): everything in LDS, q <= 16
-    const bool fast = q <= 16 && nlv <= 1024 && p <= JCH_SWEEP_MAXP && jch_lv_fast_lds_bytes(p, q, qpad, ldr, nlv) <= 150 * 1024 && !getenv("JCH_SMALLSTATE_GENERIC");
+    const bool fast = q <= 16 && nlv <= 1024 && p <= JCH_SWEEP_MAXP && jch_lv_fast_lds_bytes(p, q, qpad, ldr, nlv) <= 150 * 1024;
     // the fast small-state kernel sums the second-stage slices itself; with several GPUs the [slices][ldz] block is
     // all-reduced as one message (still latency-bound at 32 KB) instead of being collapsed by an extra launch
     // plssimp / plswold: their fast kernels (siblings.hip) need the p x q state in LDS; outside that envelope the generic
     // small-state kernel (K in global memory, q <= 64, any p) takes over
     const bool sib = algo == ALGO_SIMP || algo == ALGO_WOLD;
-    const bool sib_fast = sib && jch_sibling_supported(p, q, ldr, nlv) && !getenv("JCH_SMALLSTATE_GENERIC");
+    const bool sib_fast = sib && jch_sibling_supported(p, q, ldr, nlv);
     const bool all_fast = sib ? (sib_fast && (algo == ALGO_SIMP || fast)) : fast;   // every small-state kernel of this fit is a fast one
     const int max_slices = all_fast ? JCH_ZT_SLICES : 1;
-    const bool fuse_inbox = all_fast && ctx->p2p.ready && !ctx->loop && !getenv("JCH_P2P_UNFUSED") &&
+    const bool fuse_inbox = all_fast && ctx->p2p.ready && !ctx->loop &&
                             (size_t)(ldr + 1 + qpad) <= ctx->p2p.cap;   // the fused kernel writes one whole message into one inbox slot
     int nslice = 1;
     // ---- K1 means (+ two-pass std), K2 centre/scale + row-major copy + XtY
@@ -396,8 +394,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     // instead of two).  The sweeps then use t_i = x_i.r - mu.r and zp = zp_raw - mu * sum_i d_i t_i (sweep.hip,
     // smallstate_fast.hip); T, P, C, TT, xmeans are the same quantities as in the centred formulation.
     const bool raw_mode = (((algo == ALGO_KERN || algo == ALGO_ROSA) && fast) || (algo == ALGO_SIMP && all_fast)) && !ext_scales && !inplace &&
-                          q <= 15 && (d.reserved & ~JCH_REUSE_XCOPY) == 0 && p <= JCH_SWEEP_MAXP && allow_raw && !getenv("JCH_CENTRED_COPY") &&
-                          !(d.scal && getenv("JCH_CENTRED_COPY_SCAL"));
+                          q <= 15 && (d.reserved & ~JCH_REUSE_XCOPY) == 0 && p <= JCH_SWEEP_MAXP && allow_raw && !jch_knob_set("JCH_CENTRED_COPY");
     if (raw_mode) {
         // (mshift and the pivot-quality word were zeroed by the weights launch above; the divisor slots `s.mom` handed to K2
         // as `scl` are never read with SCAL = false; k_extract_means moves the Y means and resets s.scl to ones)
@@ -464,8 +461,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         // SPLIT small-state path (smallstate_split.hip; round 4): per LV a p-parallel kernel on (p + 15) / 16 CUs (slice sums, c,
         // K update, P / W / R columns, partial Gram / Z sums) + a single-workgroup kernel that starts at the eigenvector.  plskern /
         // plsrosa on the fast path; not with the inbox all-reduce fused into the one-kernel path.  JCH_LV_SPLIT=0: the one-kernel path.
-        const char *e_sp = getenv("JCH_LV_SPLIT");
-        split = (algo == ALGO_KERN || algo == ALGO_ROSA) && fast && !(e_sp && atoi(e_sp) == 0) &&
+        split = (algo == ALGO_KERN || algo == ALGO_ROSA) && fast && jch_knob("JCH_LV_SPLIT", 1) != 0 &&
                 jch_lv_solve_lds_bytes(p, q, ldr, nlv) <= 150 * 1024 && (!fuse_inbox || jch_lv_split_p2p_ok(ctx, p));
         if (split) { s.kr = cv.take(16); JCH_TRY(jch_lv_split_begin_fit(ctx, s, cv.take(jch_lv_split_doubles(p, nlv)), p, nlv)); }
         JCH_TRY(jch_launch_lv_update(ctx, s, p, q, qpad, ldr, -1, nlv, kern_like ? 0 : 1, 1, ldz, fast));

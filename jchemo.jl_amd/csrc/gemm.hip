@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_affine_gemm32(const double *__restrict_
 {
     __shared__ double bl[G32_CH * 33];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // row tiles of 128 rows, interleaved over a persistent grid (JCH_GEMM_BPC blocks per CU; 0 = one block per tile)
+    // row tiles of 128 rows, interleaved over a persistent grid (the launcher passes one block per tile)
     for (int64_t tile = blockIdx.x; tile * 128 < m; tile += gridDim.x) {
     const int64_t i0 = tile * 128 + 32 * wv;
     const int64_t irow = i0 + 2 * (lane & 15);        // this lane's row pair
@@ -224,14 +224,17 @@ __global__ __launch_bounds__(256) void k_affine_gemm32s(const double *__restrict
 // is co-bound, and what matters is that neither pipe waits for the other.
 // PAIRED (round 4): the tile TRANSPOSED (operands swapped: the same registers) and rows 2 cl, 2 cl + 1 of a column stored as one
 // 16-byte piece — see k_affine_gemm_wideout.
-template <int NT, int NW, int RT, bool PAIRED>   // NW waves per workgroup share the one LDS copy of the coefficients; RT row tiles of 32 per wave-tile
+template <int NT, int NW, bool PAIRED>   // NW waves per workgroup share the one LDS copy of the coefficients
 __global__ __launch_bounds__(64 * NW) void k_affine_gemm32p(const double *__restrict__ Xc, int64_t m, int p, int64_t ldx,
                                                          const double *__restrict__ Bs, int kpad, const double *__restrict__ bias,
                                                          int k, double *__restrict__ out, int64_t ldo)
 {
     extern __shared__ __attribute__((aligned(16))) double blp[];   // [nksp * 4][PB], zero rows beyond p
     // RT (round 4): a wave's tile is 32 RT rows — per column RT back-to-back 256-B pieces = one 256 RT-byte run of the column-major
-    // X instead of 256 B (the DRAM access granularity of this kernel); the prefetch window holds the same bytes (PD k-steps x RT)
+    // X instead of 256 B (the DRAM access granularity of this kernel); the prefetch window holds the same bytes (PD k-steps x RT).
+    // Measured at cfg2 (tools/bench_accessors.py, whole call): transform (32 columns) RT = 1 / 2 / 4: 0.905 / 0.877 / 0.846 ms;
+    // predict at one nlv (16 columns): 0.839 / 0.769 / 0.768 ms
+    constexpr int RT = 4;
     constexpr int PB = 16 * NT + 1, PD = 16 / RT;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int nksp = ((p + 3) / 4 + 15) / 16 * 16;                  // k-steps, padded to the largest prefetch window
@@ -341,12 +344,13 @@ __global__ __launch_bounds__(64 * NW) void k_affine_gemm32p(const double *__rest
 // piece: 16 lanes write a contiguous 256-byte run of a column.  Untransposed, a store instruction scattered 64 8-byte pieces over
 // 16 columns x 4 rows 16 bytes apart, and the pieces of a line met in L2 from eight instructions (2.08 GB of output at 2.4 TB/s).
 // Needs out 16-byte aligned and ldo even (the launcher checks); the values are the same sums in the same order.
-template <int KS, int RT, bool PAIRED>   // KS k-steps of 4 input columns held in registers (p <= 4 KS); RT row tiles of 32 per wave-tile
+template <int KS, bool PAIRED>   // KS k-steps of 4 input columns held in registers (p <= 4 KS)
 __global__ __launch_bounds__(256) void k_affine_gemm_wideout(const double *__restrict__ Xc, int64_t m, int p, int64_t ldx,
                                                            const double *__restrict__ Bs, int kpad, const double *__restrict__ bias,
-                                                           int k, double *__restrict__ out, int64_t ldo, int nt)
+                                                           int k, double *__restrict__ out, int64_t ldo)
 {
     extern __shared__ __attribute__((aligned(16))) double blw[];   // [4 KS][kpad + 1], zero rows beyond p
+    constexpr int RT = 2;   // row tiles of 32 per wave-tile (round 4, with the paired stores: 64-row wave tiles 1.50 ms, 128-row 1.65)
     const int PB = kpad + 1;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     for (int e = tid; e < 4 * KS * kpad; e += 256) {
@@ -401,7 +405,7 @@ __global__ __launch_bounds__(256) void k_affine_gemm_wideout(const double *__res
                             if (i + 1 < m) {
                                 const v2f64 val = {acc[rt][0][reg] + bv, acc[rt][1][reg] + bv};
                                 v2f64 *dst = reinterpret_cast<v2f64 *>(out + (size_t)i + (size_t)col * (size_t)ldo);
-                                if (nt) __builtin_nontemporal_store(val, dst); else *dst = val;
+                                *dst = val;   // (plain stores, as below)
                             }
                         }
                     }
@@ -428,77 +432,59 @@ __global__ __launch_bounds__(256) void k_affine_gemm_wideout(const double *__res
 int32_t jch_launch_affine_gemm(jch_ctx *ctx, const double *Xc, int64_t m, int p, int64_t ldx, const double *Bs, int k, int kpad,
                                const double *bias, double *out, int64_t ldo)
 {
-    if (kpad <= 32 && !getenv("JCH_GEMM_GENERIC")) {
+    if (kpad <= 32) {
         // long inputs: persistent kernel with the whole coefficient matrix in LDS (JCH_GEMM_PERSIST=0: the tiled kernel below)
         const size_t ldsp = sizeof(double) * (size_t)(((p + 3) / 4 + 15) / 16 * 64) * (kpad + 1);
-        const char *ep = getenv("JCH_GEMM_PERSIST");
-        if (!(ep && atoi(ep) == 0) && ldsp <= 150 * 1024 && m >= 64 * 1024 && m % 2 == 0 && ldx % 2 == 0 && (((uintptr_t)Xc) & 15) == 0) {
+        if (jch_knob("JCH_GEMM_PERSIST", 1) != 0 && ldsp <= 150 * 1024 && m >= 64 * 1024 && m % 2 == 0 && ldx % 2 == 0 && (((uintptr_t)Xc) & 15) == 0) {
             // two waves per SIMD, so that one wave's MFMAs cover the other's wait for its loads: two workgroups of 4 waves per CU
             // while two copies of the coefficients fit in LDS (kpad = 16 at cfg2), else ONE workgroup of 8 waves sharing one copy
             // (measured at cfg2, kernel time: nlv = 25 -> 32 columns: 4 waves 0.96 ms, 8 waves 0.87, 12 waves 0.87, tiled kernel 1.03;
-            // 10 -> 16 columns: 2 x 4 waves 0.71 ms, 8 waves 0.73, 12 waves 0.75, tiled kernel 0.73.  JCH_GEMM_NW = 4 / 8 overrides.)
-            const char *enw = getenv("JCH_GEMM_NW"), *ert = getenv("JCH_GEMM_RT");
-            const int nw = enw ? (atoi(enw) == 4 ? 4 : 8) : (kpad == 16 ? 4 : 8);
-            // row tiles per wave-tile = 256 rt bytes per column piece.  Measured at cfg2 (round 4, tools/bench_accessors.py, whole call):
-            // transform (32 columns) rt = 1 / 2 / 4: 0.905 / 0.877 / 0.846 ms; predict at one nlv (16 columns): 0.839 / 0.769 / 0.768 ms
-            const int rt = ert ? (atoi(ert) == 1 ? 1 : (atoi(ert) == 2 ? 2 : 4)) : 4;
-            const char *ep32 = getenv("JCH_GEMM_PAIRED");          // (=0: the untransposed tile with 8-byte stores — A/B runs)
-            const bool paired32 = !(ep32 && atoi(ep32) == 0) && ldo % 2 == 0 && (((uintptr_t)out) & 15) == 0;
+            // 10 -> 16 columns: 2 x 4 waves 0.71 ms, 8 waves 0.73, 12 waves 0.75, tiled kernel 0.73)
+            const int nw = kpad == 16 ? 4 : 8;
+            const int rows = 32 * 4 * nw;   // rows per workgroup-tile: 4 row tiles of 32 per wave (RT of the kernel)
+            const bool paired32 = ldo % 2 == 0 && (((uintptr_t)out) & 15) == 0;   // (else the untransposed tile with 8-byte stores)
             const int bpc = std::max(1, std::min((int)((158 * 1024) / ldsp), 8 / nw));
-            const unsigned nb = (unsigned)std::min<int64_t>((m + 32 * rt * nw - 1) / (32 * rt * nw), (int64_t)ctx->cus * bpc);
-#define JCH_G32P(NT, NW, RT) do { \
+            const unsigned nb = (unsigned)std::min<int64_t>((m + rows - 1) / rows, (int64_t)ctx->cus * bpc);
+#define JCH_G32P(NT, NW) do { \
                 static jch_per_device_once once_; \
-                if (!once_.done(ctx->device)) { JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_affine_gemm32p<NT, NW, RT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                    JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_affine_gemm32p<NT, NW, RT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once_.mark(ctx->device); } \
-                if (paired32) hipLaunchKernelGGL((k_affine_gemm32p<NT, NW, RT, true>), dim3(nb), dim3(64 * NW), ldsp, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo); \
-                else hipLaunchKernelGGL((k_affine_gemm32p<NT, NW, RT, false>), dim3(nb), dim3(64 * NW), ldsp, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo); } while (0)
-#define JCH_G32P_RT(NT, NW) do { if (rt == 1) JCH_G32P(NT, NW, 1); else if (rt == 2) JCH_G32P(NT, NW, 2); else JCH_G32P(NT, NW, 4); } while (0)
-            if (kpad == 16) { if (nw == 4) JCH_G32P_RT(1, 4); else JCH_G32P_RT(1, 8); }
-            else { if (nw == 4) JCH_G32P_RT(2, 4); else JCH_G32P_RT(2, 8); }
-#undef JCH_G32P_RT
+                if (!once_.done(ctx->device)) { JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_affine_gemm32p<NT, NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+                    JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_affine_gemm32p<NT, NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once_.mark(ctx->device); } \
+                if (paired32) hipLaunchKernelGGL((k_affine_gemm32p<NT, NW, true>), dim3(nb), dim3(64 * NW), ldsp, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo); \
+                else hipLaunchKernelGGL((k_affine_gemm32p<NT, NW, false>), dim3(nb), dim3(64 * NW), ldsp, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo); } while (0)
+            if (kpad == 16) JCH_G32P(1, 4); else JCH_G32P(2, 8);
 #undef JCH_G32P
             JCH_HIP(ctx, hipGetLastError());
             return JCH_OK;
         }
-        // short inputs: 32 rows per workgroup, the columns of X split over its waves (JCH_GEMM_SMALL=0: the tiled kernel)
-        const char *es = getenv("JCH_GEMM_SMALL");
-        if (!(es && atoi(es) == 0) && m <= 32 * (int64_t)ctx->cus && p >= 64) {
+        // short inputs: 32 rows per workgroup, the columns of X split over its waves
+        if (m <= 32 * (int64_t)ctx->cus && p >= 64) {
             hipLaunchKernelGGL(k_affine_gemm32s, dim3((unsigned)((m + 31) / 32)), dim3(256), 0, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo);
             JCH_HIP(ctx, hipGetLastError());
             return JCH_OK;
         }
-        const char *eb = getenv("JCH_GEMM_BPC");
-        const int bpc = eb ? atoi(eb) : 0;
-        const int64_t ntile = (m + 127) / 128;
-        const unsigned nb = (unsigned)(bpc > 0 ? std::min<int64_t>(ntile, (int64_t)ctx->cus * bpc) : ntile);
-        hipLaunchKernelGGL(k_affine_gemm32, dim3(nb), dim3(256), 0, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias,
+        hipLaunchKernelGGL(k_affine_gemm32, dim3((unsigned)((m + 127) / 128)), dim3(256), 0, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias,
                            k, out, ldo);
         JCH_HIP(ctx, hipGetLastError());
         return JCH_OK;
     }
-    {   // short rows, wide output (JCH_GEMM_WIDEOUT=0: the general kernel; JCH_GEMM_WIDEOUT_RT=2: 64-row wave tiles).  predict over
+    {   // short rows, wide output (JCH_GEMM_WIDEOUT=0: the general kernel).  predict over
         // nlv = 0..25 at cfg2 (1e6 x 25 scores -> 260 columns), whole call: general kernel 1.93 ms, this kernel with plain stores
         // 1.77 (64-row tiles); with NON-TEMPORAL stores 4.14 — the 8-B pieces of an output line come from eight store instructions
         // and must meet in L2.
-        const char *ew = getenv("JCH_GEMM_WIDEOUT"), *er = getenv("JCH_GEMM_WIDEOUT_RT");
         const int ks = (p + 3) / 4;
-        const int rtw = er ? (atoi(er) == 1 ? 1 : atoi(er) == 4 ? 4 : 2) : 2;   // (round 4, with the paired stores: 64-row wave tiles 1.50 ms, 128-row 1.65)
         const size_t ldsw = sizeof(double) * (size_t)(4 * (ks <= 4 ? 4 : ks <= 8 ? 8 : 16)) * (kpad + 1);
-        if (!(ew && atoi(ew) == 0) && p <= 64 && kpad > 32 && ldsw <= 150 * 1024 && m >= 4096 && m % 2 == 0 && ldx % 2 == 0 && (((uintptr_t)Xc) & 15) == 0) {
-            const unsigned nb = (unsigned)std::min<int64_t>((m + 32 * rtw * 4 - 1) / (32 * rtw * 4), (int64_t)ctx->cus * 2);
-            const char *epair = getenv("JCH_GEMM_WIDEOUT_PAIRED");     // (=0: the untransposed tile with 8-byte stores — A/B runs)
-            const bool paired = !(epair && atoi(epair) == 0) && ldo % 2 == 0 && (((uintptr_t)out) & 15) == 0;
-            const char *ent = getenv("JCH_GEMM_WIDEOUT_NT");
-            const int nt_ = ent ? atoi(ent) : 0;
-#define JCH_GW(KS, RT) do { \
+        if (jch_knob("JCH_GEMM_WIDEOUT", 1) != 0 && p <= 64 && kpad > 32 && ldsw <= 150 * 1024 && m >= 4096 && m % 2 == 0 && ldx % 2 == 0 && (((uintptr_t)Xc) & 15) == 0) {
+            const int rows = 32 * 2 * 4;   // rows per workgroup-tile: 2 row tiles of 32 per wave (RT of the kernel), 4 waves
+            const unsigned nb = (unsigned)std::min<int64_t>((m + rows - 1) / rows, (int64_t)ctx->cus * 2);
+            // (JCH_GEMM_WIDEOUT_PAIRED=0: the untransposed tile with 8-byte stores — A/B runs)
+            const bool paired = jch_knob("JCH_GEMM_WIDEOUT_PAIRED", 1) != 0 && ldo % 2 == 0 && (((uintptr_t)out) & 15) == 0;
+#define JCH_GW(KS) do { \
                 static jch_per_device_once once_; \
-                if (!once_.done(ctx->device)) { JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_affine_gemm_wideout<KS, RT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                    JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_affine_gemm_wideout<KS, RT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once_.mark(ctx->device); } \
-                if (paired) hipLaunchKernelGGL((k_affine_gemm_wideout<KS, RT, true>), dim3(nb), dim3(256), ldsw, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo, nt_); \
-                else hipLaunchKernelGGL((k_affine_gemm_wideout<KS, RT, false>), dim3(nb), dim3(256), ldsw, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo, 0); } while (0)
-            if (ks <= 4) { if (rtw == 1) JCH_GW(4, 1); else if (rtw == 2) JCH_GW(4, 2); else JCH_GW(4, 4); }
-            else if (ks <= 8) { if (rtw == 1) JCH_GW(8, 1); else if (rtw == 2) JCH_GW(8, 2); else JCH_GW(8, 4); }
-            else { if (rtw == 1) JCH_GW(16, 1); else JCH_GW(16, 2); }
+                if (!once_.done(ctx->device)) { JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_affine_gemm_wideout<KS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+                    JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_affine_gemm_wideout<KS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once_.mark(ctx->device); } \
+                if (paired) hipLaunchKernelGGL((k_affine_gemm_wideout<KS, true>), dim3(nb), dim3(256), ldsw, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo); \
+                else hipLaunchKernelGGL((k_affine_gemm_wideout<KS, false>), dim3(nb), dim3(256), ldsw, ctx->stream, Xc, m, p, ldx, Bs, kpad, bias, k, out, ldo); } while (0)
+            if (ks <= 4) JCH_GW(4); else if (ks <= 8) JCH_GW(8); else JCH_GW(16);
 #undef JCH_GW
             JCH_HIP(ctx, hipGetLastError());
             return JCH_OK;
@@ -673,8 +659,7 @@ static int32_t jch_launch_predict_prefix(jch_ctx *ctx, const double *T, int64_t 
                                          int lo, int hi, double *out, int64_t ldo)
 {
     const bool v2 = m % 2 == 0 && ldt % 2 == 0 && ldo % 2 == 0 && (((uintptr_t)T) & 15) == 0 && (((uintptr_t)out) & 15) == 0;
-    const char *ent = getenv("JCH_PREDICT_NT");                 // (=0: plain stores — A/B runs)
-    const bool nt = !(ent && atoi(ent) == 0);
+    const bool nt = jch_knob("JCH_PREDICT_NT", 1) != 0;                 // (=0: plain stores — A/B runs)
     const int qc = q <= 4 ? 4 : (q <= 8 ? 8 : 16);
     const int64_t thr = v2 ? m / 2 : m;
     dim3 grid((unsigned)((thr + 255) / 256), (unsigned)((q + qc - 1) / qc));
@@ -698,8 +683,7 @@ extern "C" int32_t jch_predict(jch_ctx *ctx, int32_t loc, const double *X, int64
     const int64_t le = (int64_t)nlv_hi - nlv_lo + 1, kcols = le * q;
     // Three levels or more on a long input: the scores once (one pass over X: m x nlv_hi), then the prediction blocks as running
     // sums over the score columns (k_predict_prefix).  JCH_PREDICT_PREFIX=0: the one-GEMM path below for every range.
-    const char *epp = getenv("JCH_PREDICT_PREFIX");
-    if (le > 2 && m >= 4096 && !(epp && atoi(epp) == 0)) {
+    if (le > 2 && m >= 4096 && jch_knob("JCH_PREDICT_PREFIX", 1) != 0) {
         if (!X || !pred || p < 1 || ldx < m || ldo < m) return jch_fail(ctx, JCH_EINVAL, "jch_predict: bad arguments");
         if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "jch_predict: bad loc");
         JCH_HIP(ctx, hipSetDevice(ctx->device));

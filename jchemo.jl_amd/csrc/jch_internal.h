@@ -69,6 +69,8 @@ struct jch_ctx {
     bool xcopy_valid = false;
     long long xcopy_reused = 0;   // fits that took their kernel matrix from it
     unsigned sweep_seq = 0;   // launches of the plskern-shaped sweep so far (JCH_SWEEP_ALT: alternating walk direction)
+    int sweep_alt = 0;                 // JCH_SWEEP_ALT and JCH_SWEEP_FUSED_REDUCE=1 as read when the current fit started
+    bool sweep_fused_reduce = false;
     jch_buf gram, xr, yr, xstage, ystage, wstage, tbuf, dnorm, part, kpart, small, colpart, gemm_b, gemm_out, xq, tickets, qz, lw_work, lw_xrm, lvws, lw_flags, lw_screen;
     jch_buf kg_ws, dk_x, dk_y, dk_k, dk_q, dk_o, dk_s;   // Gram kernel workspace (kgram.hip), dkplsr staging (dkplsr.hip)
     jch_buf kp_ws;   // kplsr panels and small state (kplsr.hip)
@@ -93,8 +95,6 @@ struct jch_ctx {
     // second stream + event (created on first use): result copies that may run beside the last kernel of a call (lwplsr.hip)
     hipStream_t aux_stream = nullptr;
     hipEvent_t aux_event = nullptr;
-    // tuning knobs (env JCH_SWEEP_BLOCKS_PER_CU etc.)
-    int sweep_blocks_per_cu = 0;
     // diagnostics
     long long pivot_refits = 0;      // raw-mode fits repeated on the centred copy because the sampled pivot was poor
     long long knn_screened = 0, knn_screen_redone = 0;   // kNN-LWPLSR queries done by the screened search / redone by the exact selection behind it
@@ -123,6 +123,10 @@ int32_t jch_fail(jch_ctx *ctx, int32_t code, const char *fmt, ...);
         int32_t s__ = (expr);         \
         if (s__ != JCH_OK) return s__; \
     } while (0)
+
+// environment switches (ctx.hip: the only place of the library that reads the environment): presence, and integer value or dflt when unset
+bool jch_knob_set(const char *name);
+int jch_knob(const char *name, int dflt);
 
 int32_t jch_reserve(jch_ctx *ctx, jch_buf &b, size_t bytes);
 int32_t jch_reserve_host(jch_ctx *ctx, size_t bytes);   // ctx->hstage (pinned)
@@ -226,7 +230,7 @@ struct jch_small {  // device-resident replicated small state of one fit
     double *niter;      // [nlv] plswold: inner iterations per LV (src/plswold.jl:93); null otherwise
     double *kr;         // [16] split small-state path (smallstate_split.hip): K' r of the current LV; null otherwise
     double *gpart;      // [blocks][gld] split path: per-block partials of K_new'K_new, zp'K_new and P_i'K_new; null otherwise
-    unsigned *lvctr;    // split path, merged kernel: arrival counter of the fit's blocks (zeroed when a fit starts); null otherwise
+    unsigned *lvctr;    // split path: arrival counter of the fit's blocks, non-null iff the fit runs the merged kernel (JCH_LV_MERGED=1, decided and zeroed in jch_lv_split_begin_fit)
 };
 
 int32_t jch_launch_lv_update(jch_ctx *ctx, const jch_small &s, int p, int q, int qpad, int ldr, int a /*-1: init*/,

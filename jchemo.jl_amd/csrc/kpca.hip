@@ -500,11 +500,8 @@ int32_t svqb(jch_ctx *ctx, const pc_state &s, const double *Z, double *out)
 // default oversampling of the block (b = min(n, roundup16(nlv + oversample))); JCH_KPCA_OVERSAMPLE overrides it (measurement knob)
 int oversample()
 {
-    if (const char *e = getenv("JCH_KPCA_OVERSAMPLE")) {
-        const long v = atol(e);
-        if (v >= 0 && v <= 4096) return (int)v;
-    }
-    return 7;
+    const int v = jch_knob("JCH_KPCA_OVERSAMPLE", 7);
+    return v >= 0 && v <= 4096 ? v : 7;
 }
 
 bool psd_kernel(int kind, double gamma, double coef0, int degree)

@@ -323,11 +323,7 @@ int32_t launch_pass_r(jch_ctx *ctx, const double *K, int64_t n, const double *V,
 {
     constexpr int CB = R <= 2 ? 8 : R <= 4 ? 4 : R <= 8 ? 2 : 1;
     const int64_t ngroups = (n + CB - 1) / CB;
-    int64_t nb = std::min<int64_t>(ngroups, (int64_t)ctx->cus * 8);
-    if (const char *e = getenv("JCH_KPLSR_NB")) {   // measurement knob
-        const long long v = atoll(e);
-        if (v >= 1) nb = std::min<int64_t>(ngroups, v);
-    }
+    const int64_t nb = std::min<int64_t>(ngroups, (int64_t)ctx->cus * 8);
     const bool vec = (n % 2) == 0 && (ldv % 2) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)V % 16) == 0;
     if (vec)
         hipLaunchKernelGGL((k_kp_pass<R, CB, true>), dim3((unsigned)nb), dim3(KP_NT), 0, ctx->stream, K, n, V, ldv, rr, out, ldo, ngroups);
@@ -409,10 +405,8 @@ int32_t d2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t l
 // rows of new data per Gram block: JCH_KPLSR_QBLOCK, else 1 GiB of Gram (2^27 doubles)
 int64_t qblock(int64_t n)
 {
-    if (const char *e = getenv("JCH_KPLSR_QBLOCK")) {
-        const long long v = atoll(e);
-        if (v >= 1) return v;
-    }
+    const int v = jch_knob("JCH_KPLSR_QBLOCK", 0);
+    if (v >= 1) return v;
     return std::max<int64_t>(1, ((int64_t)1 << 27) / n);
 }
 

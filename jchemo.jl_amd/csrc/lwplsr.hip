@@ -117,13 +117,14 @@ __device__ __forceinline__ int knn_pow2_at_least(int v) { int c = 64; while (c <
 
 // (struct knn_args: lwplsr_dev.h)
 
-// NT threads per workgroup, QB queries per workgroup (every loaded training value serves QB queries).  <256, 4>: two workgroups
-// per CU (default); <512, 8> (round 3, JCH_KNN_WIDE=1): ONE workgroup of eight waves per CU — the same waves in flight, half the
-// L2 traffic (the kernel reads the whole score matrix once per query group: 16 MB x 250 groups at cfg5) — measured SLOWER, see the
-// launcher.
-template <int NT, int QB>
-__global__ __launch_bounds__(NT) void k_knn_scan(knn_args g)
+// NT threads per workgroup, QB queries per workgroup (every loaded training value serves QB queries): two workgroups per CU.
+// (Round 3, measured SLOWER: ONE workgroup of 512 threads and eight queries per CU — the same waves in flight, half the L2 traffic
+// (the kernel reads the whole score matrix once per query group: 16 MB x 250 groups at cfg5): 1.62 ms with 3 row segments, 1.05 with
+// 2, against 0.87 — the scan is not bound by the L2 bytes but by its dependent steps (threshold tests, LDS appends, barriers,
+// sorts), which eight waves share one candidate bookkeeping for.)
+__global__ __launch_bounds__(256) void k_knn_scan(knn_args g)
 {
+    constexpr int NT = 256, QB = KNN_QB;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *bkey = lds;                                            // [QB][CAP]
     int *bidx = reinterpret_cast<int *>(bkey + QB * KNN_CAP);  // [QB][CAP]
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(NT) void k_knn_scan(knn_args g)
         const int qq = e / g.dd, c = e - qq * g.dd;
         zq[e] = qq < nq ? g.Zq[(size_t)(q0 + qq) + (size_t)c * (size_t)g.ldzq] : 0.0;
     }
-    if (tid < QB) { tau[tid] = (g.dbg & 1) ? -__builtin_inf() : __builtin_inf(); cnt[tid] = 0; }
+    if (tid < QB) { tau[tid] = __builtin_inf(); cnt[tid] = 0; }
     __syncthreads();
     const int k = g.k;
     // KNN_RB chunks of NT training rows per trip: all their loads go out together (the kernel is bound by the latency of the
@@ -741,8 +742,7 @@ static int32_t launch_locw_q(jch_ctx *ctx, locw_args &g)
         if (jch_locw_kspace_feasible(g)) return jch_launch_locw_kspace(ctx, g);
         return jch_fail(ctx, JCH_EINVAL, "jch_lwplsr_predict: k / p / q too large for the batched local-PLS kernels (k = %d, p = %d, q = %d)", g.k, g.p, g.q);
     }
-    const char *e_bpc = getenv("JCH_LOCW_BPC");   // (measurement knob) blocks per CU of the local-fit kernel
-    int nb = std::min(g.m, ctx->cus * ((e_bpc && atoi(e_bpc) > 0) ? atoi(e_bpc) : 2));
+    const int nb = std::min(g.m, ctx->cus * 2);
     g.slab = ((size_t)g.k * g.ldr + 2 * (size_t)g.nlv_hi * g.ldr + 31) & ~(size_t)31;
     if (ctx->xcopy.host) ctx->xcopy_valid = false;   // (the staging buffer of a host-array fit is re-used for the slabs)
     JCH_TRY(jch_reserve(ctx, ctx->xstage, sizeof(double) * g.slab * nb));
@@ -805,18 +805,10 @@ void jch_lw_to_rowmajor(jch_ctx *ctx, const double *dX, int64_t ldxd, int64_t n,
     hipLaunchKernelGGL(k_to_rowmajor, dim3(nbx, ptiles), dim3(256), 0, ctx->stream, dX, ldxd, n, p, Xrm, ldr);
 }
 
-// LDS bytes of the scan for this shape (its envelope: <= 150 KB); wide_out: the JCH_KNN_WIDE=1 measurement variant applies
-size_t jch_knn_scan_lds(int k, int dd, int m, bool *wide_out)
+// LDS bytes of the scan for this score-space width (its envelope: <= 150 KB)
+size_t jch_knn_scan_lds(int dd)
 {
-    // JCH_KNN_WIDE=1 (measurement knob, round 3): eight queries per 512-thread workgroup — half the L2 traffic, the same waves per
-    // CU.  Measured at cfg5: 1.62 ms with 3 row segments, 1.05 with 2, against 0.87 for four queries per 256-thread workgroup:
-    // the scan is not bound by the L2 bytes but by its dependent steps (threshold tests, LDS appends, barriers, sorts), which
-    // eight waves share one candidate bookkeeping for.  Default: off.
-    const char *e_w = getenv("JCH_KNN_WIDE");
-    const bool wide = k <= KNN_CAP - 512 && e_w && atoi(e_w) == 1 && m > 4;
-    if (wide_out) *wide_out = wide;
-    const int qb = wide ? 8 : KNN_QB;
-    return (sizeof(double) + sizeof(int)) * qb * KNN_CAP + sizeof(double) * (qb * (size_t)dd + qb) + sizeof(int) * qb + 64;
+    return (sizeof(double) + sizeof(int)) * KNN_QB * KNN_CAP + sizeof(double) * (KNN_QB * (size_t)dd + KNN_QB) + sizeof(int) * KNN_QB + 64;
 }
 
 // The exact scan + finish (K9 / K9b) for a.m queries; a.only_flags: null, or device flags — only the groups of KNN_QB queries with a
@@ -825,17 +817,14 @@ int32_t jch_launch_knn_scan(jch_ctx *ctx, knn_args a, jch_buf &cbuf)
 {
     const int64_t n = a.n;
     const int m = a.m, k = a.k;
-    bool wide = false;
-    const size_t lds = jch_knn_scan_lds(k, a.dd, m, &wide);
-    if (a.only_flags) wide = false;
-    const int nt = wide ? 512 : 256;
+    const size_t lds = jch_knn_scan_lds(a.dd);
+    const int nt = 256;
     {
         // row segments: as many as keep every segment at >= 4 trips and the merged candidate lists inside one sort (nseg * k <= KNN_CAP)
         // (measured at cfg5, 1000 queries: 1 segment 1.38 ms, 2: 1.00, 3: 0.88, 5: 1.21 — every (query group, segment) block pays
         // its own compaction sorts)
         // (round 3, with the sort-free compactions: 2 segments 0.60 ms, 3: 0.51, 4: 0.59, 5: 0.57, 6: 0.56, 8: 0.59)
         int nseg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(3, KNN_FCAP / k), n / (4 * nt * KNN_RB)));
-        if (const char *e = getenv("JCH_KNN_SEGMENTS")) nseg = std::max(1, std::min(atoi(e), KNN_FCAP / k));
         // behind the screened search: ONE segment and no separate finishing kernel — two launches whose workgroups find nothing
         // flagged and leave cost 9.8 us per call at cfg5, one launch of a third as many workgroups 3
         if (a.only_flags) nseg = 1;
@@ -844,8 +833,7 @@ int32_t jch_launch_knn_scan(jch_ctx *ctx, knn_args a, jch_buf &cbuf)
         a.ckey = (double *)cbuf.ptr; a.cidx = (int *)(a.ckey + (size_t)m * nseg * k);
         static jch_per_device_once attr;
         if (!attr.done(ctx->device)) {
-            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_knn_scan<256, KNN_QB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_knn_scan<512, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_knn_scan, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr.mark(ctx->device);
         }
         // (round 4, measured and removed: eight queries per 256-thread workgroup with 512-entry candidate buffers — half the score
@@ -853,8 +841,7 @@ int32_t jch_launch_knn_scan(jch_ctx *ctx, knn_args a, jch_buf &cbuf)
         // the scan is NOT bound by its L2 / Infinity Cache traffic; with a dot-product screen |z|^2 + |zq|^2 - 2 z.zq in front of the
         // exact distance — half the arithmetic per pair — 1.78 ms: the ~1000 survivors per query and segment each pay a divergent
         // 20-load recomputation.  Results were identical in both.  What bounds the scan is the dependent chain of a wave's trip.)
-        if (wide) hipLaunchKernelGGL((k_knn_scan<512, 8>), dim3((unsigned)((m + 7) / 8) * nseg), dim3(512), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((k_knn_scan<256, KNN_QB>), dim3((unsigned)((m + KNN_QB - 1) / KNN_QB) * nseg), dim3(256), lds + (a.only_flags ? sizeof(double) * (KNN_CAP + 16) : 0), ctx->stream, a);
+        hipLaunchKernelGGL(k_knn_scan, dim3((unsigned)((m + KNN_QB - 1) / KNN_QB) * nseg), dim3(256), lds + (a.only_flags ? sizeof(double) * (KNN_CAP + 16) : 0), ctx->stream, a);
         if (!a.only_flags) hipLaunchKernelGGL(k_knn_finish, dim3((unsigned)m), dim3(256), 0, ctx->stream, a);
     }
     JCH_HIP(ctx, hipGetLastError());
@@ -880,19 +867,13 @@ static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64
         knn_args a;
         a.Zt = dZt; a.ldzt = ldztd; a.n = n; a.Zq = dZq; a.ldzq = ldzqd; a.m = (int)m; a.dd = (int)dd; a.k = k;
         a.h = h; a.cri = 4.0; a.tol = tol; a.ind = dind; a.dist = ddist; a.w = dw;
-        { const char *e = getenv("JCH_KNN_DBG"); a.dbg = e ? atoi(e) : 0; }
-        // JCH_KNN_WIDE=1 (measurement knob, round 3): eight queries per 512-thread workgroup — half the L2 traffic, the same waves per
-        // CU.  Measured at cfg5: 1.62 ms with 3 row segments, 1.05 with 2, against 0.87 for four queries per 256-thread workgroup:
-        // the scan is not bound by the L2 bytes but by its dependent steps (threshold tests, LDS appends, barriers, sorts), which
-        // eight waves share one candidate bookkeeping for.  Default: off.
-        const size_t lds = jch_knn_scan_lds(k, (int)dd, (int)m, nullptr);
+        const size_t lds = jch_knn_scan_lds((int)dd);
         // outside the scan's envelope (k beyond the candidate buffers, a search space too wide for its LDS, 2^29 rows): the generic
         // selection, one workgroup per query (lwplsr_generic.hip); JCH_KNN_GENERIC=1 forces it (tests)
-        const char *e_g = getenv("JCH_KNN_GENERIC");
+        const bool knn_generic = jch_knob("JCH_KNN_GENERIC", 0) == 1;
         // the screened kNN (lwplsr_screen.hip: all pairs in f32 on the matrix cores, exact distances for the survivors only) when the
         // shape is inside its envelope; JCH_KNN_SCREEN=0 selects the exact scan below (A/B runs, tests)
-        const char *e_s = getenv("JCH_KNN_SCREEN");
-        const bool screen = !(e_g && atoi(e_g) == 1) && !(e_s && atoi(e_s) == 0) && !a.dbg && !(screen_off && *screen_off) && jch_knn_screen_shape_ok(n, (int)dd, k);
+        const bool screen = !knn_generic && jch_knob("JCH_KNN_SCREEN", 1) != 0 && !(screen_off && *screen_off) && jch_knn_screen_shape_ok(n, (int)dd, k);
         if (screen) {
             knn_screen local;
             if (!scr) {   // one-shot call: the model-constant operand copy is rebuilt in the ctx workspace
@@ -905,7 +886,7 @@ static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64
             sflags = (int *)ctx->lw_flags.ptr + (size_t)m;
             JCH_TRY(jch_launch_knn_screen(ctx, a, *scr, sflags));
         } else
-        if (k > KNN_CAP - 256 || lds > 150 * 1024 || n >= ((int64_t)1 << 29) || (e_g && atoi(e_g) == 1)) {
+        if (k > KNN_CAP - 256 || lds > 150 * 1024 || n >= ((int64_t)1 << 29) || knn_generic) {
             JCH_TRY(jch_launch_knn_generic(ctx, a));
         } else {
         JCH_TRY(jch_launch_knn_scan(ctx, a, ctx->gemm_b));
@@ -914,51 +895,13 @@ static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64
     ev2 = jch_ev(ctx);
     // neighbours, distances and weights are final here: their copies to the host (3.2 MB at cfg5, into pages of the caller's
     // fresh arrays that have never been touched) run on a second stream BESIDE the local fits instead of after them
-    // JCH_LW_LISTS_STAGED=1 (round 4, measured, NOT the default): the neighbour lists go to pinned staging through copies queued on
-    // the main stream IN FRONT of the local fits, and the host moves them on to the caller's arrays while the local fits run.  Why
-    // it was tried: under rocprofv3 two of the three list copies of the default arrangement (second stream, beside the local fits)
-    // show up AFTER the local-fit launch.  Without the tracer they do not (JCH_LW_HOST_DBG=1 host stamps: the lists are on the
-    // host 250 us after the kNN launches, the main stream's wait ends at 1036 us; staged: 1100-1115 us, the copies delay the local
-    // fits by their 75 us): 1.20-1.25 ms per call against 1.17-1.18 on the same box.  Kept for stacks where the copies do starve.
-    const size_t list_bytes = (ind_out ? sizeof(int) : 0) * (size_t)m * k + ((dist_out ? 1 : 0) + (w_out ? 1 : 0)) * sizeof(double) * (size_t)m * k;
-    const size_t pred_bytes_ = sizeof(double) * (size_t)m * le * q + sizeof(int) * 2 * (size_t)m + 64;
-    const char *e_ls = getenv("JCH_LW_LISTS_STAGED");
-    const bool lists_staged = e_ls && atoi(e_ls) == 1 && list_bytes > 0 && list_bytes + pred_bytes_ <= ((size_t)64 << 20);
-    char *hl_d = nullptr, *hl_w = nullptr, *hl_i = nullptr;   // pinned staging of dist / w / ind
-    if (lists_staged) {
-        JCH_TRY(jch_reserve_host(ctx, list_bytes + pred_bytes_ + 256));
-        char *hb = (char *)ctx->hstage + ((pred_bytes_ + 63) & ~(size_t)63);
-        if (dist_out) { hl_d = hb; hb += sizeof(double) * (size_t)m * k; }
-        if (w_out) { hl_w = hb; hb += sizeof(double) * (size_t)m * k; }
-        if (ind_out) { hl_i = hb; }
-        if (dist_out && w_out) JCH_HIP(ctx, hipMemcpyAsync(hl_d, ddist, 2 * sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, ctx->stream));   // (adjacent on both sides)
-        else {
-            if (dist_out) JCH_HIP(ctx, hipMemcpyAsync(hl_d, ddist, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, ctx->stream));
-            if (w_out) JCH_HIP(ctx, hipMemcpyAsync(hl_w, dw, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (ind_out) JCH_HIP(ctx, hipMemcpyAsync(hl_i, dind, sizeof(int) * (size_t)m * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (!ctx->aux_event && hipEventCreateWithFlags(&ctx->aux_event, hipEventDisableTiming) != hipSuccess) { ctx->aux_event = nullptr; return jch_fail(ctx, JCH_EHIP, "jch_lwplsr_predict: event creation failed"); }
-        JCH_HIP(ctx, hipEventRecord(ctx->aux_event, ctx->stream));
-    }
-    // the lists are on the host as soon as their event is: on to the caller's arrays (beside the batched local fits; BEFORE per-query
-    // fits, which use the pinned staging themselves)
-    bool lists_drained = !lists_staged;
-    const bool host_dbg = getenv("JCH_LW_HOST_DBG") != nullptr;
+    // (Round 4, measured and NOT adopted: the lists to pinned staging through copies queued on the main stream IN FRONT of the local
+    // fits, moved on to the caller's arrays by the host while the local fits run — 1.20-1.25 ms per call against 1.17-1.18 on the
+    // same box: the copies delay the local fits by their 75 us.  JCH_LW_HOST_DBG=1 prints the host stamps of the wait below.)
+    const bool host_dbg = jch_knob_set("JCH_LW_HOST_DBG");
     const auto t_host0 = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_host0).count(); };
-    auto drain_lists = [&]() -> int32_t {
-        if (lists_drained) return JCH_OK;
-        lists_drained = true;
-        const double t0 = since();
-        JCH_HIP(ctx, hipEventSynchronize(ctx->aux_event));
-        const double t1 = since();
-        if (dist_out) memcpy(dist_out, hl_d, sizeof(double) * (size_t)m * k);
-        if (w_out) memcpy(w_out, hl_w, sizeof(double) * (size_t)m * k);
-        if (ind_out) memcpy(ind_out, hl_i, sizeof(int) * (size_t)m * k);
-        if (host_dbg) fprintf(stderr, "[jch] lists staged: wait for the event %.0f .. %.0f us after the kNN launches, host copy until %.0f\n", t0, t1, since());
-        return JCH_OK;
-    };
-    bool side_copies = !lists_staged && (ind_out || dist_out || w_out) && !getenv("JCH_LW_SIDE_COPY_OFF");
+    bool side_copies = ind_out || dist_out || w_out;
     if (side_copies) {
         if (!ctx->aux_stream && hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess) { ctx->aux_stream = nullptr; side_copies = false; }
         if (side_copies && !ctx->aux_event && hipEventCreateWithFlags(&ctx->aux_event, hipEventDisableTiming) != hipSuccess) { ctx->aux_event = nullptr; side_copies = false; }
@@ -972,14 +915,12 @@ static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64
         g.Xrm = Xrm; g.ldr = ldr; g.p = (int)p; g.Y = dY; g.ldy = ldyd; g.q = (int)q; g.Xq = dXq; g.ldxq = ldxqd; g.m = (int)m;
         g.ind = dind; g.w = dw; g.k = k; g.scal = scal; g.nlv_lo = nlv_lo; g.nlv_hi = nlv_hi; g.pred = dpred;
         g.scratch = nullptr; g.slab = 0; g.flags = nullptr;
-        { const char *e = getenv("JCH_LOCW_DBG"); g.dbg = e ? atoi(e) : 0; }
+        g.dbg = jch_knob("JCH_LOCW_DBG", 0);
         // neighbour-space kernel (lwplsr_kspace.hip: the gathered rows are read ONCE, the fit runs on their Gram matrix held in
         // registers) when the shape fits it; the p-space kernel (one sweep of the slab per LV) otherwise
-        const char *e_lg = getenv("JCH_LOCW_GENERIC");
-        if (!locw_batched_fits(g) || (e_lg && atoi(e_lg) == 1)) {   // outside the batched kernels' envelope: one fit per query (lwplsr_generic.hip)
+        if (!locw_batched_fits(g) || jch_knob("JCH_LOCW_GENERIC", 0) == 1) {   // outside the batched kernels' envelope: one fit per query (lwplsr_generic.hip)
             const hipError_t pe = hipMemsetAsync(dpred, 0, sizeof(double) * (size_t)m * le * q, ctx->stream);
             if (pe != hipSuccess) return jch_fail(ctx, JCH_EHIP, "jch_lwplsr_predict: %s", hipGetErrorString(pe));
-            JCH_TRY(drain_lists());
             JCH_TRY(jch_lw_generic_fits(ctx, g, n));
             generic_fits = true;
         } else
@@ -1003,21 +944,19 @@ static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64
     // before the host waits for anything (round 4; three copies into pageable memory issued after the wait for the neighbour lists
     // left the device idle for 65 us and cost 30 + 18 + 34 us of turn-around: 0.15 of a 1.17 ms call at cfg5)
     const size_t pred_bytes = sizeof(double) * (size_t)m * le * q, flag_bytes = (kflags || sflags) ? sizeof(int) * 2 * (size_t)m : 0;
-    const bool staged = lists_staged || pred_bytes + flag_bytes <= ((size_t)64 << 20);
+    const bool staged = pred_bytes + flag_bytes <= ((size_t)64 << 20);
     char *hs = nullptr;
     if (staged) {
-        if (lists_drained) JCH_TRY(jch_reserve_host(ctx, pred_bytes + flag_bytes + 64));   // (lists still in the staging: reserved above, they lie behind this part)
+        JCH_TRY(jch_reserve_host(ctx, pred_bytes + flag_bytes + 64));
         hs = (char *)ctx->hstage;
         if (flag_bytes) JCH_HIP(ctx, hipMemcpyAsync(hs, ctx->lw_flags.ptr, flag_bytes, hipMemcpyDeviceToHost, ctx->stream));   // [pivot flags m][screen flags m]
         JCH_HIP(ctx, hipMemcpyAsync(hs + flag_bytes, dpred, pred_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
-    JCH_TRY(drain_lists());
     hipStream_t cs = side_copies ? ctx->aux_stream : ctx->stream;
     hipError_t ce = hipSuccess;
-    if (lists_staged) { /* done */ } else
     if (ind_out && ce == hipSuccess) ce = hipMemcpyAsync(ind_out, dind, sizeof(int) * (size_t)m * k, hipMemcpyDeviceToHost, cs);
-    if (!lists_staged && dist_out && ce == hipSuccess) ce = hipMemcpyAsync(dist_out, ddist, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, cs);
-    if (!lists_staged && w_out && ce == hipSuccess) ce = hipMemcpyAsync(w_out, dw, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, cs);
+    if (dist_out && ce == hipSuccess) ce = hipMemcpyAsync(dist_out, ddist, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, cs);
+    if (w_out && ce == hipSuccess) ce = hipMemcpyAsync(w_out, dw, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, cs);
     if (side_copies) { const hipError_t se = hipStreamSynchronize(cs); if (ce == hipSuccess) ce = se; }   // (before any return: the buffers are the caller's)
     if (ce != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return jch_fail(ctx, JCH_EHIP, "jch_lwplsr_predict: copy of the neighbour lists failed: %s", hipGetErrorString(ce)); }
     std::vector<int> hf, hsf;

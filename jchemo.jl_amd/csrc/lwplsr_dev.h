@@ -35,7 +35,6 @@ struct knn_args {
     int nseg;      // the training rows are scanned in nseg segments by different workgroups (block b: segment b % nseg, query group b / nseg)
     double *ckey;  // [m][nseg][k] squared distances of every segment's k best (ascending; +inf beyond the segment's rows)
     int *cidx;     // [m][nseg][k]
-    int dbg;       // measurement switch (JCH_KNN_DBG; results then wrong by design): 1 = the bar starts at -inf (no candidate is ever kept: the bare scan)
     const int *only_flags = nullptr;   // null, or [m] device flags — only the queries with a non-zero flag are done (k_knn_scan: only their groups of qb)
 };
 
@@ -62,7 +61,7 @@ int32_t jch_launch_knn_screen(jch_ctx *ctx, const knn_args &a, const knn_screen 
 // lwplsr.hip: row-major copy Xrm [n][ldr] of a column-major n x p matrix (columns p .. ldr - 1 zero), on the ctx stream
 void jch_lw_to_rowmajor(jch_ctx *ctx, const double *dX, int64_t ldxd, int64_t n, int p, double *Xrm, int ldr);
 // lwplsr.hip: the exact scan (k <= 768, LDS for the score space: jch_knn_scan_lds <= 150 KB)
-size_t jch_knn_scan_lds(int k, int dd, int m, bool *wide_out);
+size_t jch_knn_scan_lds(int dd);
 int32_t jch_launch_knn_scan(jch_ctx *ctx, knn_args a, jch_buf &cbuf);
 
 // lwplsr_generic.hip: the paths WITHOUT shape limits (any k <= n, any p, q, nlv) behind the batched kernels' envelope.
@@ -105,7 +104,7 @@ __device__ __forceinline__ void knn_wavesync()
 }
 // The same network run by ONE wave (no workgroup barrier between the passes: a wave's LDS operations complete in order): the four
 // waves of a scan workgroup sort the four queries' buffers side by side — 7 us per 1024 entries against 14 us x 4 queries with
-// the workgroup-wide sort, which was half of the scan's time (JCH_KNN_DBG=1 measures the scan without any candidate kept).
+// the workgroup-wide sort, which was half of the scan's time.
 template <int PP>   // PP = pairs per lane and pass = cap / 128 (1 for cap <= 128): all of a pass's loads go out together
 __device__ __forceinline__ void bitonic_sort_wave_pp(double *key, int *idx, int cap)
 {

@@ -633,7 +633,7 @@ __global__ __launch_bounds__(KS_NT, 1) void k_locw_kspace(locw_args g)
 // the shape fits the neighbour-space kernel at all
 bool jch_locw_kspace_feasible(const locw_args &g)
 {
-    if (const char *e = getenv("JCH_LOCW_KSPACE")) { if (atoi(e) == 0) return false; }   // 0: never
+    if (jch_knob("JCH_LOCW_KSPACE", 1) == 0) return false;   // 0: never
     if (g.k > KS_KP || g.k < 2 || g.q > 8 || g.nlv_hi > KS_MAXNLV || g.nlv_hi < 1 || g.ldr > JCH_SWEEP_MAXP || g.ldr < 2) return false;
     const int Q = g.q <= 1 ? 1 : (g.q <= 2 ? 2 : (g.q <= 4 ? 4 : 8));
     return sizeof(double) * (size_t)ks_layout(Q, g.nlv_hi).total + 64 <= 159 * 1024;
@@ -642,7 +642,7 @@ bool jch_locw_kspace_feasible(const locw_args &g)
 bool jch_locw_kspace_supported(const locw_args &g)
 {
     if (!jch_locw_kspace_feasible(g)) return false;
-    if (const char *e = getenv("JCH_LOCW_KSPACE")) { if (atoi(e) == 2) return true; }    // 2: whenever the shape fits (tests)
+    if (jch_knob("JCH_LOCW_KSPACE", 1) == 2) return true;    // 2: whenever the shape fits (tests)
     // the Gram pass costs 208^2 p / 2 matrix flops per query whatever k is (smaller k is zero-padded to 13 row blocks): it pays
     // against nlv sweeps of a k x p slab when k is most of those 208 rows and the row is wide
     return g.k >= 128 && g.p >= 128 && g.nlv_hi >= 3;

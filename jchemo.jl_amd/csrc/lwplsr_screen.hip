@@ -67,7 +67,7 @@ struct ks_args {
                         // written by the pair's one wave on every call (32 contiguous bytes), nothing to clear, no count to read
     int *flags;         // [m]
     int nqt, nslots, T;
-    int gpw, nchunks, qw;      // k_knn_survive: group slots per row chunk, chunks, tiles of 32 queries per wave item (1, 2)
+    int gpw, nchunks;          // k_knn_survive: group slots per row chunk, chunks (one tile of 32 queries per wave item)
     int gpw_g, nchunks_g, qw_g;   // k_knn_gmin: the same (its own split of the work: it writes per group slot, not per chunk)
     double cfac;
 };
@@ -443,9 +443,10 @@ __device__ __noinline__ void ks_place(int *cand, int *cnt, int m, const unsigned
 }
 
 // (five waves per SIMD forced through amdgpu_waves_per_eu: 96 registers + 11 spilled, 32 -> 41 us)
-template <int KS, int QW>
+template <int KS>
 __global__ __launch_bounds__(256) void k_knn_survive(ks_args g)
 {
+    constexpr int QW = 1;   // tiles of 32 queries per wave item (two were measured slower here: 36.4-40.7 against 31.2 us at cfg5)
     __shared__ int wcnt[4][32 * QW];
     __shared__ int wslots[4][32 * QW * KS_S];
     __shared__ unsigned wlist[4][KS_LCAP];
@@ -552,11 +553,8 @@ __global__ __launch_bounds__(256) void k_knn_finish_screen(ks_args g)
     __syncthreads();
     // gather: the chunks' own slots (one contiguous read of the query's nchunks x 32 bytes), then the overflow list (any order: the
     // entries are put in (distance, index) order below)
-    const int dbg = g.a.dbg;   // JCH_KNN_SCREEN_DBG (measurement; results then wrong by design): 2 no distances, 4 no ordering, 8 no tail, 16 no gather
     const int oc = g.cnt[qi];
     const int4 *sl = reinterpret_cast<const int4 *>(g.scand + (size_t)qi * g.nchunks * KS_S);
-    if (dbg & 16) { for (int e = tid; e < k + 20; e += 256) idx[e] = e * 37; if (tid == 0) tot = k + 20; }
-    else
     for (int ch = tid; ch < g.nchunks; ch += 256) {
         int v[KS_S];
 #pragma unroll
@@ -590,7 +588,6 @@ __global__ __launch_bounds__(256) void k_knn_finish_screen(ks_args g)
         if (e < c) {
             row = idx[e];
             acc = 0.0;
-            if (dbg & 2) { acc = (double)((row * 2654435761u) >> 8); key[e] = acc; continue; }
             // (the expression and column order of k_knn_scan: the same bits; the row from the row-major copy: 8 dd contiguous bytes
             // in whole 64-byte sectors instead of dd sectors 8 n bytes apart — those were 40 of this kernel's 66 us at cfg5)
             const double2 *zr = reinterpret_cast<const double2 *>(g.sc.Zr + (size_t)row * g.sc.ldzr);
@@ -608,8 +605,6 @@ __global__ __launch_bounds__(256) void k_knn_finish_screen(ks_args g)
         key[e] = acc; idx[e] = row;
     }
     __syncthreads();
-    if (dbg & 4) { for (int e = tid; e < k; e += 256) { okey[e] = key[e]; oidx[e] = idx[e]; } }
-    else
     if (c <= 512) {
         // segments of 64 entries (four, or eight: two per wave), each put in order by one wave on its registers, then MERGED BY RANK: an
         // entry's place is its place in its own segment plus, for every other segment, the number of entries there that come before
@@ -644,7 +639,6 @@ __global__ __launch_bounds__(256) void k_knn_finish_screen(ks_args g)
         for (int e = tid; e < k; e += 256) { okey[e] = key[e]; oidx[e] = idx[e]; }
     }
     __syncthreads();
-    if (dbg & 8) { for (int e = tid; e < k; e += 256) { g.a.ind[(size_t)qi * k + e] = oidx[e] < 0 || oidx[e] >= g.a.n ? e : oidx[e]; g.a.dist[(size_t)qi * k + e] = okey[e]; g.a.w[(size_t)qi * k + e] = 1.0; } return; }
     knn_finish_tail(g.a, qi, k, key, okey, oidx, sred, smed, snn);
 }
 
@@ -731,8 +725,7 @@ static void ks_launch_passes(jch_ctx *ctx, const ks_args &g)
     else if (G <= 512) hipLaunchKernelGGL((k_knn_bar<8>), dim3(nbq), dim3(256), 0, ctx->stream, g);
     else if (G <= 1024) hipLaunchKernelGGL((k_knn_bar<16>), dim3(nbq), dim3(256), 0, ctx->stream, g);
     else hipLaunchKernelGGL((k_knn_bar<32>), dim3(nbq), dim3(256), 0, ctx->stream, g);
-    if (g.qw == 2 && QWmax == 2) hipLaunchKernelGGL((k_knn_survive<KS, QWmax>), dim3(grid(2, g.nchunks)), dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL((k_knn_survive<KS, 1>), dim3(grid(1, g.nchunks)), dim3(256), 0, ctx->stream, g);
+    hipLaunchKernelGGL((k_knn_survive<KS>), dim3(grid(1, g.nchunks)), dim3(256), 0, ctx->stream, g);
 }
 
 int32_t jch_launch_knn_screen(jch_ctx *ctx, const knn_args &a, const knn_screen &sc, int *flags)
@@ -752,11 +745,8 @@ int32_t jch_launch_knn_screen(jch_ctx *ctx, const knn_args &a, const knn_screen 
     g.nchunks_g = (g.nslots + g.gpw_g - 1) / g.gpw_g;
     // k_knn_survive: at most 256 chunks (a query's slots, chunks x 32 bytes, are read in one trip by its finishing workgroup), and
     // at most 1 GB of them (m x chunks x KS_S ints)
-    g.qw = 1;
-    if (const char *e = getenv("JCH_KNN_SCREEN_QW")) g.qw = (atoi(e) == 2 && g.nqt >= 2 && sc.KS <= 6) ? 2 : 1;
-    g.gpw = (int)std::max<int64_t>(1, ((int64_t)g.nslots * ((g.nqt + g.qw - 1) / g.qw)) / ((int64_t)ctx->cus * 4 * 6));
+    g.gpw = (int)std::max<int64_t>(1, ((int64_t)g.nslots * g.nqt) / ((int64_t)ctx->cus * 4 * 6));
     g.gpw = std::max(g.gpw, (g.nslots + 255) / 256);
-    if (const char *e = getenv("JCH_KNN_SCREEN_GPW")) g.gpw = std::max(1, atoi(e));
     g.gpw = (int)std::max<int64_t>(g.gpw, ((int64_t)a.m * g.nslots * KS_S * 4 + ((int64_t)1 << 30) - 1) >> 30);
     g.nchunks = (g.nslots + g.gpw - 1) / g.gpw;
     g.cfac = ks_cfac(a.dd);
@@ -779,23 +769,6 @@ int32_t jch_launch_knn_screen(jch_ctx *ctx, const knn_args &a, const knn_screen 
     switch (sc.KS) { KS_PASSES(1); KS_PASSES(2); KS_PASSES(3); KS_PASSES(4); KS_PASSES(5); KS_PASSES(6); KS_PASSES(7); KS_PASSES(8); KS_PASSES(9);
     KS_PASSES(10); KS_PASSES(11); default: ks_launch_passes<12>(ctx, g); break; }
 #undef KS_PASSES
-    if (const char *e = getenv("JCH_KNN_SCREEN_DBG")) {
-        g.a.dbg = atoi(e);
-        if (g.a.dbg & 1) {   // survivors per query (host sync; measurement only)
-            std::vector<int> hc(mpad), hs((size_t)a.m * g.nchunks * KS_S);
-            JCH_HIP(ctx, hipMemcpyAsync(hc.data(), g.cnt, sizeof(int) * mpad, hipMemcpyDeviceToHost, ctx->stream));
-            JCH_HIP(ctx, hipMemcpyAsync(hs.data(), g.scand, sizeof(int) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
-            JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            long long tot = 0, ovf = 0; int mx = 0, over256 = 0;
-            for (int i = 0; i < a.m; ++i) {
-                int c = hc[i];
-                for (size_t e = 0; e < (size_t)g.nchunks * KS_S; ++e) c += hs[(size_t)i * g.nchunks * KS_S + e] >= 0 ? 1 : 0;
-                tot += c; ovf += hc[i]; mx = std::max(mx, c); over256 += c > 256;
-            }
-            fprintf(stderr, "[jch] screened kNN: m=%d k=%d T=%d slots=%d gpw=%d chunks=%d survivors mean %.1f max %d, %d lists > 256, %lld through the overflow lists\n", a.m, a.k,
-                    g.T, g.nslots, g.gpw, g.nchunks, (double)tot / a.m, mx, over256, ovf);
-        }
-    }
     hipLaunchKernelGGL(k_knn_finish_screen, dim3((unsigned)a.m), dim3(256), sizeof(double) * (size_t)a.dd, ctx->stream, g);
     JCH_HIP(ctx, hipGetLastError());
     // the flagged queries (the exception): the exact scan, for the groups of four queries with a flagged member

@@ -69,10 +69,10 @@ extern "C" int32_t jch_ctx_p2p_export(jch_ctx *ctx, int32_t nranks, void *handle
     jch_p2p &t = ctx->p2p;
     if (t.local) return jch_fail(ctx, JCH_EINVAL, "jch_ctx_p2p_export: inbox already allocated");
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    t.cap = 16384;
-    // never below the widest fused per-LV message (the fused kernels of smallstate_fast.hip / bf16.hip write ldr + 1 + 16
+    // above the widest fused per-LV message (the fused kernels of smallstate_fast.hip / bf16.hip write ldr + 1 + 16
     // resp. bf_ldr + 2 doubles into one slot without chunking; jch_p2p_allreduce chunks by cap)
-    if (const char *e = getenv("JCH_P2P_CAP")) t.cap = (size_t)std::max(JCH_SWEEP_MAXP + 64, atoi(e));
+    t.cap = 16384;
+    static_assert(16384 >= JCH_SWEEP_MAXP + 64, "inbox slot narrower than the widest fused message");
     t.nranks = nranks;
     const size_t bytes = p2p_bytes(nranks, t.cap);
     JCH_HIP(ctx, hipExtMallocWithFlags(&t.local, bytes, hipDeviceMallocFinegrained));
@@ -136,9 +136,8 @@ extern "C" int32_t jch_ctx_p2p_import(jch_ctx *ctx, const void *handles, int32_t
         t.opened[r] = true;
     }
     JCH_HIP(ctx, hipHostGetDevicePointer((void **)&t.host_status_dev, t.host_status, 0));
-    double ms = 10000.0;   // generous: a spurious timeout would abort a fit; a lost peer still cannot hang the GPU
-    if (const char *e = getenv("JCH_P2P_TIMEOUT_MS")) ms = atof(e);
-    t.timeout_ticks = (long long)(ms * 1e5);   // wall_clock64 runs at 100 MHz
+    const int ms = jch_knob("JCH_P2P_TIMEOUT_MS", 10000);   // generous: a spurious timeout would abort a fit; a lost peer still cannot hang the GPU
+    t.timeout_ticks = (long long)ms * 100000;   // wall_clock64 runs at 100 MHz
     if (!ctx->comm) { ctx->rank = rank; ctx->nranks = nranks; }
     // ---- self-test (collective: every rank is inside this call): both parities, exact small-integer sums
     const int cnt = 1000;

@@ -157,7 +157,7 @@ int32_t jch_launch_moments(jch_ctx *ctx, const double *Xc, int64_t ldx, const do
     double *colpart = (double *)ctx->colpart.ptr;
     // 16-B loads need every column start 16-B aligned (chunk is a multiple of 256 rows)
     const int al16 = (ldx % 2 == 0) && ((uintptr_t)Xc % 16 == 0) && (q == 0 || ((ldy % 2 == 0) && ((uintptr_t)Yc % 16 == 0))) &&
-                     ((uintptr_t)d % 16 == 0) && !getenv("JCH_K1_V1");
+                     ((uintptr_t)d % 16 == 0);
     if (means)
         hipLaunchKernelGGL(k_moments<true>, dim3(m, S), dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, d, n, p, q, chunk,
                            means, colpart, al16);
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void k_center_xty(double *__restrict__ Xc, int
                                                      int64_t ldy, const double *__restrict__ d, int64_t n, int p, int q,
                                                      const double *__restrict__ mom, const double *__restrict__ scl,
                                                      double *__restrict__ Xr, int ldr, double *__restrict__ Yr, int qpad,
-                                                     double *__restrict__ Kpart, int kp_rows, int dbg_skip, int ones_col)
+                                                     double *__restrict__ Kpart, int kp_rows, int ones_col)
 {
     __shared__ double xt[64 * XT_LD];
     __shared__ double yt[64 * YT_LD];
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256) void k_center_xty(double *__restrict__ Xc, int
         // ---- prefetch the next chunk
         if (c + gridDim.x < nchunks) prefetch(c + gridDim.x);
         // ---- row-major store (y group 0 only): (row wv+4k, col lane)
-        if (yg == 0 && !(dbg_skip & 2)) {
+        if (yg == 0) {
 #pragma unroll 4
             for (int k = 0; k < 16; ++k) {
                 const int row = wv + 4 * k, j = j0 + lane;
@@ -259,14 +259,12 @@ __global__ __launch_bounds__(256) void k_center_xty(double *__restrict__ Xc, int
         }
         // ---- XtY on the matrix cores: wave wv owns columns j0+16wv .. +15
         //      A[m = x column][k = row] , B[k = row][n = y column]; lane l: (k = l>>4, m|n = l&15)
-        if (!(dbg_skip & 1)) {
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             const int row = 4 * kk + (lane >> 4);
             const double a = xt[row * XT_LD + 16 * wv + (lane & 15)];
             const double b = yt[row * YT_LD + (lane & 15)];
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-        }
         }
         __syncthreads();
     }
@@ -281,7 +279,7 @@ __global__ __launch_bounds__(256) void k_center_xty(double *__restrict__ Xc, int
 
 // ---------------------------------------------------------------- K2p: row-panel version of K2 (q <= 16, 16-B aligned columns)
 // Same outputs as k_center_xty (row-major copy, Yr, XtY partials).  What round 2 measured about this pass
-// (profiles/r02_k2_notes.md; tools/k2_modes.py compares variants inside one process, on the same buffers):
+// (profiles/r02_k2_notes.md):
 //   * the tile kernel below is NOT short of TLB reach (99.9 % UTCL1 hits) or starved by latency (1.2 k cycles per read
 //     request, like the sweep); its 8.4 GB move at 3.9 TB/s;
 //   * reading alone (stores compiled out) runs at 5 TB/s whatever the block mapping; the stores add ~1.05 ms for their 4 GB
@@ -303,7 +301,12 @@ __global__ __launch_bounds__(256) void k_center_xty(double *__restrict__ Xc, int
 // rate == f64 vector rate): 0.21 ms of matrix-pipe time per cfg2 prologue, 3 % of the pass when compiled out.
 typedef double v2f64p __attribute__((ext_vector_type(2)));
 // TH rows x TW columns per LDS tile (TW = 64 or 128: the row pieces written to the copy are TW * 8 bytes); the tile is
-// filled and multiplied in 64-column halves, stored as whole TW-wide rows.
+// filled and multiplied in 64-column halves, stored as whole TW-wide rows.  Only <64, 64> is instantiated: the measured best of
+// 64 / 128 rows x 64 / 128 columns and a whole-row 32 x 512 tile (retired switches).
+// `dbg_skip` is ALWAYS 0 (the launcher passes the literal; the switch that fed it is retired) and the branches on it are dead.
+// They are still here because the kernel is not neutral to their removal: with the argument folded to a constant the
+// compiler allocates 242 instead of 224 VGPRs and the pass takes 1.95 instead of 1.83 ms at cfg2 (same-run A/B on MI355X).
+// Removing them belongs to a change that re-tunes this kernel.
 template <int TH, int TW, bool WRITEBACK, bool SCAL>
 __global__ __launch_bounds__(256, 2) void k_center_xty_panel(double *__restrict__ Xc, int64_t ldx, const double *__restrict__ Yc,
                                                              int64_t ldy, const double *__restrict__ d, int64_t n, int p, int q,
@@ -747,44 +750,21 @@ int32_t jch_launch_center_xty(jch_ctx *ctx, double *Xc, int64_t ldx, double *Yc,
                               const double *spread2, double *qual, double *ones_out)
 {
     const int ones_col = means_out ? q : -1;   // raw mode: needs a free pad column in y group 0 (q <= 15)
-    // Row-panel kernel (k_center_xty_panel): q <= 16 and 16-B aligned columns; defaults (64-row x 64-column pieces, one block
-    // per CU) are the measured best.  JCH_K2_PANEL=0 keeps the tile kernel below; JCH_K2_TH / JCH_K2_TW / JCH_K2_BPC / JCH_K2_NB
-    // select tile height / piece width / blocks per CU / block count, JCH_K2_SKIP bits compile parts out for timing.
-    // (read on every call, not cached: tools/k2_modes.py compares the variants inside one process, on the same buffers —
-    // the run time of this pass depends on where the buffers happen to live)
-    auto env_int = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-    const int dbg_skip = env_int("JCH_K2_SKIP", 0);
-    const int panel_sel = env_int("JCH_K2_PANEL", 1), th_sel = env_int("JCH_K2_TH", 64);
-    if (panel_sel && qpad == 16 && ldx % 2 == 0 && ((uintptr_t)Xc) % 16 == 0) {
+    // Row-panel kernel (k_center_xty_panel): q <= 16 and 16-B aligned columns, one block per CU; otherwise the tile kernel below
+    if (qpad == 16 && ldx % 2 == 0 && ((uintptr_t)Xc) % 16 == 0) {
         const int groups = (ldr + 511) / 512;
         const int kp_rows = groups * 512;
         const int64_t nunits = (n + 31) / 32;
-        const int bpc_sel = env_int("JCH_K2_BPC", 1);
-        int nbx = std::max(1, (ctx->cus * bpc_sel) / groups);
-        if (env_int("JCH_K2_NB", 0) > 0) nbx = env_int("JCH_K2_NB", 0);
+        int nbx = std::max(1, ctx->cus / groups);
         if (nbx > nunits) nbx = (int)nunits;
         JCH_TRY(jch_reserve(ctx, ctx->kpart, sizeof(double) * (size_t)nbx * kp_rows * 16));
         double *Kpart = (double *)ctx->kpart.ptr;
         dim3 grid(nbx, groups);
-        const bool wholerow = th_sel == 32;                     // TH = 32 x TW = 512: complete rows leave the LDS tile (experiment)
-        const int th = wholerow ? 32 : (th_sel == 128 ? 128 : 64);
-        const int tw = wholerow ? 512 : (env_int("JCH_K2_TW", 64) == 128 ? 128 : 64);
-        const size_t lds = sizeof(double) * ((size_t)th * (tw + 2) + 1024 + (th > 64 ? (size_t)th * 16 : 0));
-        static jch_per_device_once attr_once;
-        if (!attr_once.done(ctx->device)) {
-#define JCH_K2P_ATTR(TH, TW, WB, SC) JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_center_xty_panel<TH, TW, WB, SC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-#define JCH_K2P_ATTR4(TH, TW) JCH_K2P_ATTR(TH, TW, false, false); JCH_K2P_ATTR(TH, TW, false, true); JCH_K2P_ATTR(TH, TW, true, false); JCH_K2P_ATTR(TH, TW, true, true)
-            JCH_K2P_ATTR4(128, 64); JCH_K2P_ATTR4(64, 64); JCH_K2P_ATTR4(64, 128); JCH_K2P_ATTR4(128, 128); JCH_K2P_ATTR4(32, 512);
-#undef JCH_K2P_ATTR4
-#undef JCH_K2P_ATTR
-            attr_once.mark(ctx->device);
-        }
-#define JCH_K2P(TH, TW, WB, SC) hipLaunchKernelGGL((k_center_xty_panel<TH, TW, WB, SC>), grid, dim3(256), lds, ctx->stream, Xc, ldx, Yc, ldy, d, n, p, q, \
-                                                   mom, scl, Xr, ldr, Yr, Kpart, kp_rows, ones_col, dbg_skip)
-#define JCH_K2P_TH(TH, TW) do { if (writeback && scal) JCH_K2P(TH, TW, true, true); else if (writeback) JCH_K2P(TH, TW, true, false); \
-                                else if (scal) JCH_K2P(TH, TW, false, true); else JCH_K2P(TH, TW, false, false); } while (0)
-        if (wholerow) JCH_K2P_TH(32, 512); else if (th == 128 && tw == 128) JCH_K2P_TH(128, 128); else if (th == 128) JCH_K2P_TH(128, 64); else if (tw == 128) JCH_K2P_TH(64, 128); else JCH_K2P_TH(64, 64);
-#undef JCH_K2P_TH
+        const size_t lds = sizeof(double) * (64 * (64 + 2) + 1024);   // the tile [64][66] + column shifts and divisors
+#define JCH_K2P(WB, SC) hipLaunchKernelGGL((k_center_xty_panel<64, 64, WB, SC>), grid, dim3(256), lds, ctx->stream, Xc, ldx, Yc, ldy, d, n, p, q, \
+                                           mom, scl, Xr, ldr, Yr, Kpart, kp_rows, ones_col, /*dbg_skip =*/0)
+        if (writeback && scal) JCH_K2P(true, true); else if (writeback) JCH_K2P(true, false);
+        else if (scal) JCH_K2P(false, true); else JCH_K2P(false, false);
 #undef JCH_K2P
         hipLaunchKernelGGL(k_reduce_kpart_wide, dim3((p * 16 + 63) / 64), dim3(256), 0, ctx->stream, Kpart, nbx, kp_rows, p, 16, K);
         JCH_TRY(jch_allreduce_f64(ctx, K, (size_t)p * qpad));
@@ -812,7 +792,7 @@ int32_t jch_launch_center_xty(jch_ctx *ctx, double *Xc, int64_t ldx, double *Yc,
     dim3 grid(nbx, ptiles, ygroups);
     const bool wb_fused = writeback && ygroups == 1;
 #define JCH_K2(WB, SC) hipLaunchKernelGGL((k_center_xty<WB, SC>), grid, dim3(256), 0, ctx->stream, Xc, ldx, Yc, ldy, d, n, p, q, \
-                                          mom, scl, Xr, ldr, Yr, qpad, Kpart, kp_rows, dbg_skip, ones_col)
+                                          mom, scl, Xr, ldr, Yr, qpad, Kpart, kp_rows, ones_col)
     if (wb_fused && scal) JCH_K2(true, true);
     else if (wb_fused) JCH_K2(true, false);
     else if (scal) JCH_K2(false, true);

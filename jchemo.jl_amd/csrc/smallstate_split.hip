@@ -444,15 +444,17 @@ int jch_lv_split_blocks(int p) { return (p + 15) / 16; }
 int jch_lv_split_gld(int nlv) { return (SP_GP + 16 * nlv + 7) & ~7; }
 // doubles of jch_small::gpart: the block partials + 8 for the merged kernel's arrival counter (jch_small::lvctr)
 size_t jch_lv_split_doubles(int p, int nlv) { return (size_t)jch_lv_split_blocks(p) * jch_lv_split_gld(nlv) + 8; }
-// carve the split path's buffers out of `gbuf` (jch_lv_split_doubles(p, nlv) doubles); the arrival counter starts every fit at zero
-// (enqueued on the fit's stream before its first LV)
+// carve the split path's buffers out of `gbuf` (jch_lv_split_doubles(p, nlv) doubles).  JCH_LV_MERGED=1 is decided here, once per
+// fit: s.lvctr is non-null exactly when this fit runs the merged kernel, and its arrival counter then starts at zero (enqueued on
+// the fit's stream before its first LV; the default path saves the launch)
 int32_t jch_lv_split_begin_fit(jch_ctx *ctx, jch_small &s, double *gbuf, int p, int nlv)
 {
     s.gpart = gbuf;
-    s.lvctr = reinterpret_cast<unsigned *>(gbuf + jch_lv_split_doubles(p, nlv) - 8);
-    // (only the opt-in merged kernel reads the counter: the default path saves the launch)
-    const char *e_mg = getenv("JCH_LV_MERGED");
-    if (e_mg && atoi(e_mg) == 1) JCH_HIP(ctx, hipMemsetAsync(s.lvctr, 0, 64, ctx->stream));
+    s.lvctr = nullptr;
+    if (jch_knob("JCH_LV_MERGED", 0) == 1) {
+        s.lvctr = reinterpret_cast<unsigned *>(gbuf + jch_lv_split_doubles(p, nlv) - 8);
+        JCH_HIP(ctx, hipMemsetAsync(s.lvctr, 0, 64, ctx->stream));
+    }
     return JCH_OK;
 }
 
@@ -479,9 +481,9 @@ int32_t jch_launch_lv_split(jch_ctx *ctx, const jch_small &s, int p, int q, int 
     g.px = p2p_dev{};
     g.ctr = s.lvctr;
     g.ctr_target = (unsigned)(a + 1) * (unsigned)g.nblk;     // LV a is the fit's (a + 1)-th launch of the merged kernel
-    // default: two launches per LV (k_lv_spread, k_lv_solve); JCH_LV_MERGED=1: one (k_lv_merged) wherever an LV has a solve half
-    const char *e_mg = getenv("JCH_LV_MERGED");
-    const bool merged = solve && s.lvctr && e_mg && atoi(e_mg) == 1;
+    // default: two launches per LV (k_lv_spread, k_lv_solve); JCH_LV_MERGED=1 (s.lvctr non-null): one (k_lv_merged) wherever an LV
+    // has a solve half
+    const bool merged = solve && s.lvctr;
     if (fuse_p2p) {
         if (!jch_lv_split_p2p_ok(ctx, p)) return jch_fail(ctx, JCH_EINVAL, "internal: per-block inbox exchange outside its envelope");
         jch_p2p_next(ctx, &g.px);

@@ -21,7 +21,7 @@
 
 typedef double v2f64 __attribute__((ext_vector_type(2)));
 
-template <int KC, int R, bool NIPALS, bool NT, bool PF>
+template <int KC, int R, bool NIPALS, bool PF>
 __global__ __launch_bounds__(256) void k_sweep(const double *__restrict__ Xr, int64_t n, int ldr,
                                                const double *__restrict__ dw, const double *__restrict__ rvec,
                                                const double *__restrict__ Yr, int qpad, double *__restrict__ tcol,
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void k_sweep(const double *__restrict__ Xr, in
             const v2f64 *rp = reinterpret_cast<const v2f64 *>(Xr + (size_t)(r0 + rr) * (size_t)ldr) + lane;
 #pragma unroll
             for (int k = 0; k < KC; ++k)
-                xn[rr][k] = (live && in[k]) ? (NT ? __builtin_nontemporal_load(rp + 64 * k) : rp[64 * k]) : v2f64{0.0, 0.0};
+                xn[rr][k] = (live && in[k]) ? __builtin_nontemporal_load(rp + 64 * k) : v2f64{0.0, 0.0};
             dwn[rr] = live ? dw[r0 + rr] : 0.0;
         }
     };
@@ -496,7 +496,7 @@ int32_t jch_launch_reduce_part8(jch_ctx *ctx, const double *part, int nb, int ld
     return JCH_OK;
 }
 
-template <int KC, int R, bool NT = true, bool PF = false>
+template <int KC, int R, bool PF>
 static int32_t launch_sweep_t(jch_ctx *ctx, const double *Xr, int64_t n, int ldr, const double *d, const double *rvec,
                               const double *Yr, int qpad, bool nipals, double *tcol, double *zt, int ldz, int max_slices,
                               int *nslice_out, int m, const double *mu)
@@ -506,14 +506,16 @@ static int32_t launch_sweep_t(jch_ctx *ctx, const double *Xr, int64_t n, int ldr
     // per CU at KC = 4); rows are interleaved over all waves of the grid.  (One 768-thread block per CU was tried:
     // __launch_bounds__(1024) caps the kernel at 128 VGPRs and the sweep ran 1.55x slower.)
     static int bpc_cache[2] = {0, 0};
+    static jch_per_device_once once[2];
     const size_t lds = sizeof(double) * (4 * KC * 128 + 16 + 256);
-    if (bpc_cache[nipals] == 0) {
+    if (!once[nipals].done(ctx->device)) {
         int nblk = 0;
-        hipError_t e = nipals ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep<KC, R, true, NT, PF>, 256, lds)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep<KC, R, false, NT, PF>, 256, lds);
+        hipError_t e = nipals ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep<KC, R, true, PF>, 256, lds)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep<KC, R, false, PF>, 256, lds);
         bpc_cache[nipals] = (e == hipSuccess && nblk > 0) ? nblk : 2;
+        once[nipals].mark(ctx->device);
     }
-    const int bpc = ctx->sweep_blocks_per_cu > 0 ? ctx->sweep_blocks_per_cu : bpc_cache[nipals];
+    const int bpc = bpc_cache[nipals];
     const int wpb = 4;
     int64_t nb64 = (ngroups + wpb - 1) / wpb;
     if (nb64 > (int64_t)ctx->cus * bpc) nb64 = (int64_t)ctx->cus * bpc;
@@ -524,10 +526,10 @@ static int32_t launch_sweep_t(jch_ctx *ctx, const double *Xr, int64_t n, int ldr
     double *part = (double *)ctx->part.ptr;
     (void)jch_ev(ctx);  // profiling span of the dominant kernel (begin)
     if (nipals)
-        hipLaunchKernelGGL((k_sweep<KC, R, true, NT, PF>), dim3(nb), dim3(64 * wpb), lds, ctx->stream, Xr, n, ldr, d, rvec, Yr, qpad,
+        hipLaunchKernelGGL((k_sweep<KC, R, true, PF>), dim3(nb), dim3(64 * wpb), lds, ctx->stream, Xr, n, ldr, d, rvec, Yr, qpad,
                            tcol, part, ldpart, mu);
     else
-        hipLaunchKernelGGL((k_sweep<KC, R, false, NT, PF>), dim3(nb), dim3(64 * wpb), lds, ctx->stream, Xr, n, ldr, d, rvec, Yr, qpad,
+        hipLaunchKernelGGL((k_sweep<KC, R, false, PF>), dim3(nb), dim3(64 * wpb), lds, ctx->stream, Xr, n, ldr, d, rvec, Yr, qpad,
                            tcol, part, ldpart, mu);
     (void)jch_ev(ctx);  // (end)
     int nslice = std::max(1, std::min(JCH_ZT_SLICES, nb / 8));
@@ -560,26 +562,25 @@ static int32_t launch_sweep_v2_t(jch_ctx *ctx, const double *Xr, int64_t n, int 
 {
     const int64_t ngroups = (n + R - 1) / R;
     const size_t lds = sizeof(double) * (4 * KC * 128 + 16);
-    static int bpc_cache = 0;
-    if (bpc_cache == 0) {
+    static int bpc = 0;
+    static jch_per_device_once once;
+    if (!once.done(ctx->device)) {
         int nblk = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_v2<KC, R, NBUF, true>, 256, lds);
-        bpc_cache = (e == hipSuccess && nblk > 0) ? nblk : 1;
+        bpc = (e == hipSuccess && nblk > 0) ? nblk : 1;
+        once.mark(ctx->device);
     }
-    const int bpc = ctx->sweep_blocks_per_cu > 0 ? ctx->sweep_blocks_per_cu : bpc_cache;
     int64_t nb64 = (ngroups + 3) / 4;
     // FEWER blocks than CUs (round 4, last session; profiles/r04c_sweep_grid_scan.log): at one 4-wave block per CU the 500-column sweep
     // is faster with 13/16 of the CUs streaming — 208 of 256: 581 us per launch against 593-598 at 1e6 rows (6.91 TB/s against 6.75),
     // 293.5 / 298.9 at 500 k, 147.7 / 151.1 at 250 k — and with 7/8 of them on short shards (224: 77.6 / 79.0 us at 125 k rows; 208: 77.9);
     // 232 / 240 / 248 lie in between, 192 is slower again at 125 k rows, counts that are not a multiple of the 8 XCDs (245, 250, 253)
     // are slower than their neighbours.  The pass is bound by HBM, not by the CUs: fewer concurrent streams reach the stacks in a
-    // better order.  Not so for the other streaming kernels (JCH_CUS scan: the 2000-column NIPALS passes, the bf16 sweep, K2p and
+    // better order.  Not so for the other streaming kernels (scan of every persistent grid: the 2000-column NIPALS passes, the bf16 sweep, K2p and
     // the local fits of lwplsr want every CU; nor for the narrow sweeps: p = 250 / 120 lose 5-10 % per 32 blocks taken away).  1000-column
     // rows (KC = 8) behave like 500-column ones: 569 us per launch at 192-208 blocks against 582.6 at 256 (n = 500 k).
-    // JCH_SWEEP_NB=<blocks> overrides (=256: the former grid).
     int64_t cap = (int64_t)ctx->cus * bpc;
     if ((KC == 4 || KC == 8) && bpc == 1) cap = std::max<int64_t>(8, (((int64_t)ctx->cus * (n < (int64_t)1280 * ctx->cus ? 14 : 13)) / 16) & ~(int64_t)7);
-    if (const char *e_nb = getenv("JCH_SWEEP_NB")) { const int v = atoi(e_nb); if (v > 0) cap = std::min<int64_t>(v, (int64_t)ctx->cus * bpc); }
     if (nb64 > cap) nb64 = cap;
     if (nb64 < 1) nb64 = 1;
     const int nb = (int)nb64;
@@ -592,15 +593,13 @@ static int32_t launch_sweep_v2_t(jch_ctx *ctx, const double *Xr, int64_t n, int 
     // adds to every sweep — store acknowledged at the memory side, ticket, re-read through sc1 loads: three dependent
     // memory-side round trips — costs 16 us (82.9 -> 99.0 us per launch at 125 k rows, 590 -> 601-614 at 1e6 rows); with
     // agent-scope fences instead of sc1 accesses 60 us (every wave writes back / invalidates its XCD's L2).
-    const char *e_fr = getenv("JCH_SWEEP_FUSED_REDUCE");
-    const bool fused = e_fr && atoi(e_fr) == 1;
+    const bool fused = ctx->sweep_fused_reduce;
     int *tickets = nullptr;
     if (fused) JCH_TRY(jch_sweep_tickets(ctx, &tickets));
     const bool timed = jch_prof_sample(ctx);
     if (timed) (void)jch_ev(ctx);  // profiling span of the dominant kernel (begin)
     // JCH_SWEEP_ALT=1: default-policy loads + the row groups walked in alternating directions, launch by launch (see k_sweep_v2)
-    const char *e_alt = getenv("JCH_SWEEP_ALT");
-    const int alt = e_alt ? atoi(e_alt) : 0;
+    const int alt = ctx->sweep_alt;
     if (alt) {
         const int rev = alt == 2 ? 0 : (int)(ctx->sweep_seq++ & 1u);   // (=2: default-policy loads, one direction — A/B runs)
         hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, false>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
@@ -610,15 +609,10 @@ static int32_t launch_sweep_v2_t(jch_ctx *ctx, const double *Xr, int64_t n, int 
     // cache: walked forwards it takes 0.65 ms at cfg2 against 0.573 for the other 24, walked BACKWARDS — it starts with what the prologue wrote
     // last — 0.60 (profiles/r04d_first_sweep_reversed_ab.log: -50 us per cfg2 fit, -3..6 us at 125 k rows).  Same arithmetic, another order of
     // the row groups within a block's partial sums for that one LV; every fit and every rank does the same, so repeated fits and the replicated
-    // state stay bit-identical.  JCH_SWEEP_FIRST_REV=0: forwards as before; =2: backwards with default-policy loads (measured SLOWER than either).
-    static const int first_rev_mode = [] { const char *e = getenv("JCH_SWEEP_FIRST_REV"); return e ? atoi(e) : 1; }();
+    // state stay bit-identical.  (Backwards with default-policy loads was measured SLOWER than either direction with streaming loads.)
     const bool first = ctx->sweep_seq++ == 0u;
-    if (first && first_rev_mode == 2)
-        hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, false>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
-                           tickets, zt, ldz, fused ? nslice : 0, 1);
-    else
     hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
-                       tickets, zt, ldz, fused ? nslice : 0, first && first_rev_mode == 1 ? 1 : 0);
+                       tickets, zt, ldz, fused ? nslice : 0, first ? 1 : 0);
     }
     if (timed) (void)jch_ev(ctx);  // (end)
     if (pv && !fused) {   // split small-state path: k_lv_spread sums the block partials itself (no k_reduce_part launch)
@@ -784,8 +778,7 @@ static int32_t launch_sweep_lazy_t(jch_ctx *ctx, const double *Xr, int64_t n, in
         once.mark(ctx->device);
     }
     // (LDS and grid are sized for the fit's largest pending count, not the current one: one partial-row layout per fit)
-    int use_bpc = ctx->sweep_blocks_per_cu > 0 ? ctx->sweep_blocks_per_cu : bpc;
-    use_bpc = std::max(1, std::min<int>(use_bpc, (int)((160 * 1024) / std::max<size_t>(lds, 1))));
+    const int use_bpc = std::max(1, std::min<int>(bpc, (int)((160 * 1024) / std::max<size_t>(lds, 1))));
     int64_t nb64 = std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * use_bpc);
     const int nb = (int)std::max<int64_t>(nb64, 1);
     const int m = ldr + 1 + qpad, ldpart = (m + 7) & ~7;
@@ -814,7 +807,7 @@ int jch_nipals_lazy_capacity(int ldr, int q)
     const int lds_cap = std::min((int)((144 * 1024) / (sizeof(double) * jch_nipals_lazy_pitch(ldr))), 16);   // 16 x R <= 64 lanes of scores
     const bool stream = q <= 4 && !(ldr > 1024 && q > 2);     // the envelope of the streaming pass; otherwise the MFMA tile pass
     if (stream) return lds_cap;
-    if (getenv("JCH_KPASS_TILE") || ldr > 1024) return std::min(lds_cap, 8);   // LDS tile pass: JCH_TILE_MP loadings per lane
+    if (ldr > 1024) return std::min(lds_cap, 8);   // LDS tile pass: JCH_TILE_MP loadings per lane
     return ldr <= 512 ? 6 : 3;                                // direct-operand MFMA pass: loadings of 2 NS columns in registers
 }
 
@@ -842,55 +835,34 @@ int32_t jch_launch_sweep(jch_ctx *ctx, const double *Xr, int64_t n, int p, int l
     if (pv) *pv = jch_part_view{};
     if (mu && (nip || ldr > JCH_SWEEP_MAXP)) return jch_fail(ctx, JCH_EINVAL, "internal: raw-mode sweep is for plskern-shaped fits with p <= %d", JCH_SWEEP_MAXP);
     const int m = ldr + 1 + (nip ? qpad : (mu ? 1 : 0));
-    // Default: software-prefetched kernels with 8 rows x 4 KB (32 KB) per wave in flight ahead of the 32 KB being reduced
-    // (measured at cfg2 on one box: R = 4 no prefetch 0.629 ms, R = 8 no prefetch 0.633, R = 8 prefetch 0.605).
-    // JCH_SWEEP_PF=0 selects the previous kernels, JCH_SWEEP_R / JCH_SWEEP_NT keep working for the p <= 512 shape.
-    static int pfsel = -1, rsel = -1, ntsel = -1;
-    if (pfsel < 0) { const char *e = getenv("JCH_SWEEP_PF"); pfsel = e ? atoi(e) : 1; }
-    if (rsel < 0) { const char *e = getenv("JCH_SWEEP_R"); rsel = e ? atoi(e) : 0; }
-    if (ntsel < 0) { const char *e = getenv("JCH_SWEEP_NT"); ntsel = e ? atoi(e) : 1; }
-    // v2 kernels (k_sweep_v2: permlane/DPP row sums, branch-free loads, rotating buffers) for the plskern-shaped sweep;
-    // JCH_SWEEP_V2=0 selects the round-1 kernels below, JCH_SWEEP_NBUF=3 a three-buffer rotation (read per call: A/B runs)
-    {
-        const char *e2 = getenv("JCH_SWEEP_V2"), *eb = getenv("JCH_SWEEP_NBUF");
-        const int v2 = e2 ? atoi(e2) : 1, nbuf = eb ? atoi(eb) : 2;
-        if (v2 && !nip && ldr >= 2) {
+    // plskern-shaped sweep: the v2 kernels (k_sweep_v2: permlane/DPP row sums, branch-free loads, rotating buffers)
+    if (!nip) {
 #define JCH_SWEEP_V2_CASE(KC, R, NB) return launch_sweep_v2_t<KC, R, NB>(ctx, Xr, n, ldr, d, rvec, tcol, zt, ldz, max_slices, nslice_out, m, mu, pv)
-            if (ldr <= 128) JCH_SWEEP_V2_CASE(1, 8, 2);
-            if (ldr <= 256) JCH_SWEEP_V2_CASE(2, 8, 2);
-            if (ldr <= 512) {
-                // short shards (a 1/8 or 1/4 share of cfg2): 4-row groups leave a finer last round, and a third buffer in the
-                // rotation keeps two groups in flight behind the one being reduced (round 4, three A/B pairs on one box: 125 k rows
-                // 79.0-80.3 against 80.2-81.6 us per launch, 250 k rows 151.4 against 153.9); JCH_SWEEP_NBUF=2 / =3 force either
-                const bool shortshard = n < (int64_t)1280 * ctx->cus;
-                // (measured, round 4: <4, 8, 3> — two 32 KB row groups in flight per wave, 256 + 254 registers — 589.0-589.4 us per launch
-                // at n = 1e6 against 587.6 for <4, 8, 2>: the sweep is not short of bytes in flight)
-                if (nbuf == 3 || (!eb && v2 != 8 && v2 != 4 && shortshard)) JCH_SWEEP_V2_CASE(4, 4, 3);
-                if (v2 == 4 || (v2 != 8 && n < (int64_t)640 * ctx->cus)) JCH_SWEEP_V2_CASE(4, 4, 2);
-                JCH_SWEEP_V2_CASE(4, 8, 2);
-            }
-            if (ldr <= 1024) { if (nbuf == 3) JCH_SWEEP_V2_CASE(8, 4, 3); JCH_SWEEP_V2_CASE(8, 4, 2); }
-#undef JCH_SWEEP_V2_CASE
+        if (ldr <= 128) JCH_SWEEP_V2_CASE(1, 8, 2);
+        if (ldr <= 256) JCH_SWEEP_V2_CASE(2, 8, 2);
+        if (ldr <= 512) {
+            // short shards (a 1/8 or 1/4 share of cfg2): 4-row groups leave a finer last round, and a third buffer in the
+            // rotation keeps two groups in flight behind the one being reduced (round 4, three A/B pairs on one box: 125 k rows
+            // 79.0-80.3 against 80.2-81.6 us per launch, 250 k rows 151.4 against 153.9)
+            // (measured, round 4: <4, 8, 3> — two 32 KB row groups in flight per wave, 256 + 254 registers — 589.0-589.4 us per launch
+            // at n = 1e6 against 587.6 for <4, 8, 2>: the sweep is not short of bytes in flight)
+            if (n < (int64_t)1280 * ctx->cus) JCH_SWEEP_V2_CASE(4, 4, 3);
+            JCH_SWEEP_V2_CASE(4, 8, 2);
         }
+        if (ldr <= 1024) JCH_SWEEP_V2_CASE(8, 4, 2);
+#undef JCH_SWEEP_V2_CASE
     }
-#define JCH_SWEEP_CASE(KC, R, NT, PF) return launch_sweep_t<KC, R, NT, PF>(ctx, Xr, n, ldr, d, rvec, Yr, qpad, nip, tcol, zt, ldz, max_slices, nslice_out, m, mu)
-    // narrow rows keep the plain kernels: 16 rows per wave-iteration with prefetch were measured 1.5-1.8x SLOWER at
-    // p = 100 / 200 (the per-row butterfly dominates); p = 1000: +6.8 % (7.06 TB/s), p = 2000: +1.7 %
-    if (ldr <= 128) JCH_SWEEP_CASE(1, 4, true, false);
-    if (ldr <= 256) JCH_SWEEP_CASE(2, 4, true, false);
-    if (ldr <= 512) {
-        if (pfsel && rsel == 2) JCH_SWEEP_CASE(4, 2, true, true);
-        if (pfsel && rsel == 4) JCH_SWEEP_CASE(4, 4, true, true);
-        if (pfsel) JCH_SWEEP_CASE(4, 8, true, true);
-        if (rsel == 2 && !ntsel) JCH_SWEEP_CASE(4, 2, false, false);
-        if (rsel == 2 && ntsel) JCH_SWEEP_CASE(4, 2, true, false);
-        if (rsel == 8 && !ntsel) JCH_SWEEP_CASE(4, 8, false, false);
-        if (rsel == 8 && ntsel) JCH_SWEEP_CASE(4, 8, true, false);
-        if (!ntsel) JCH_SWEEP_CASE(4, 4, false, false);
-        JCH_SWEEP_CASE(4, 4, true, false);
-    }
-    if (ldr <= 1024) { if (pfsel) JCH_SWEEP_CASE(8, 4, true, true); JCH_SWEEP_CASE(8, 2, true, false); }
-    if (ldr <= 2048) { if (pfsel) JCH_SWEEP_CASE(16, 2, true, true); JCH_SWEEP_CASE(16, 1, true, false); }
+    // NIPALS-shaped sweeps (c_raw = Y'Dt accumulated with the rows) and 1024 < ldr <= 2048: the round-1 kernels.  From 512-column
+    // rows on they are software-prefetched, 8 rows x 4 KB (32 KB) per wave in flight ahead of the 32 KB being reduced (measured at
+    // cfg2 on one box: R = 4 no prefetch 0.629 ms, R = 8 no prefetch 0.633, R = 8 prefetch 0.605); p = 1000: +6.8 %
+    // (7.06 TB/s), p = 2000: +1.7 %.  Narrow rows keep the plain kernels: 16 rows per wave-iteration with prefetch were measured
+    // 1.5-1.8x SLOWER at p = 100 / 200 (the per-row butterfly dominates).
+#define JCH_SWEEP_CASE(KC, R, PF) return launch_sweep_t<KC, R, PF>(ctx, Xr, n, ldr, d, rvec, Yr, qpad, nip, tcol, zt, ldz, max_slices, nslice_out, m, mu)
+    if (ldr <= 128) JCH_SWEEP_CASE(1, 4, false);
+    if (ldr <= 256) JCH_SWEEP_CASE(2, 4, false);
+    if (ldr <= 512) JCH_SWEEP_CASE(4, 8, true);
+    if (ldr <= 1024) JCH_SWEEP_CASE(8, 4, true);
+    if (ldr <= 2048) JCH_SWEEP_CASE(16, 2, true);
 #undef JCH_SWEEP_CASE
     // wider rows: two-pass fallback (sweep_wide.hip), single reduced vector
     *nslice_out = 1;

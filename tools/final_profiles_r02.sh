@@ -23,5 +23,4 @@ python tools/bench_lwplsr.py 2>/dev/null | tail -1 > $O/lwplsr_cfg5.json
 JCH_BENCH_REHEARSAL=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 3 --master-addr 127.0.0.1 --master-port 29517 tools/bench_lwplsr.py 2>/dev/null | tail -1 > $O/lwplsr_cfg5_3replicas_one_gpu.json
 python tools/bench_gridcv.py 2>/dev/null | tail -1 > $O/gridcv.json
 python tools/bench_accessors.py 2>/dev/null | tail -1 > $O/accessors.json
-K2_VARIANTS="JCH_K2_PANEL=0;JCH_K2_PANEL=1" python tools/k2_modes.py 2>/dev/null > $O/k2_tile_vs_panel.log
 ls -la $O

@@ -22,7 +22,6 @@ JCH_LV_SPLIT=0 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host
 python bench.py --scal --steps 5 --warmup 2 --no-cpu-baseline --no-host-path > $O/bench_scal.json 2>/dev/null
 for a in plssimp plsrosa plswold plskern2; do python bench.py --algo $a --steps 5 --warmup 2 --no-cpu-baseline --no-host-path > $O/bench_$a.json 2>/dev/null; done
 python bench.py --algo plsnipals --steps 5 --warmup 2 --no-cpu-baseline --no-host-path > $O/bench_plsnipals_q10.json 2>/dev/null
-JCH_KPASS_NW=4 python bench.py --algo plsnipals --steps 5 --warmup 2 --no-cpu-baseline --no-host-path > $O/bench_plsnipals_q10_four_waves.json 2>/dev/null
 python tools/bench_lwplsr.py 2>/dev/null | tail -1 > $O/lwplsr_cfg5.json
 python tools/bench_gridcv.py 2>/dev/null | tail -1 > $O/gridcv.json
 python tools/bench_accessors.py 2>/dev/null | tail -1 > $O/accessors.json

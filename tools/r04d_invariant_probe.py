@@ -1,5 +1,4 @@
-"""T'DT = diag(TT) drift of the split small-state test's shapes, first sweep walked forwards / backwards (JCH_SWEEP_FIRST_REV is read once per process:
-run this script once per mode)."""
+"""T'DT = diag(TT) drift of the split small-state test's shapes (the first sweep of a fit is walked backwards)."""
 import os, sys, numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "jchemo.jl_amd")); sys.path.insert(0, ROOT)
@@ -18,4 +17,4 @@ for variant in ("raw", "scal_w", "centred", "rosa"):
         fm = fn(X, Y, w, nlv=nlv, scal=variant == "scal_w", ctx=ctx)
         G = (fm.T * fm.weights[:, None]).T @ fm.T
         row.append(np.abs(G - np.diag(fm.TT)).max() / np.abs(fm.TT).max())
-    print(f"FIRST_REV={os.environ.get('JCH_SWEEP_FIRST_REV', '1')} {variant:8s}", " ".join(f"{v:.2e}" for v in row))
+    print(f"{variant:8s}", " ".join(f"{v:.2e}" for v in row))
