@@ -49,6 +49,12 @@ struct jch_p2p {   // P2P inbox transport (p2p.hip)
     unsigned long long *stats = nullptr;       // device [2 phases][4]: ticks in the exchange, ticks polling flags, calls, -
 };
 
+// The memory-side Infinity Cache of the MI355X (not a queryable attribute; the library runs on gfx950 only), and the slice of a
+// working copy the plskern sweep keeps in it by default: the best point of the scan in DESIGN.md §4 (the cache also carries the
+// T column, the weights and the small state between two sweeps).
+constexpr int JCH_INFINITY_CACHE_MIB = 256;
+constexpr int JCH_RESIDENT_DEFAULT_MIB = 128;
+
 struct jch_ctx {
     int device = 0;
     int cus = 256;
@@ -71,6 +77,7 @@ struct jch_ctx {
     unsigned sweep_seq = 0;   // launches of the plskern-shaped sweep so far (JCH_SWEEP_ALT: alternating walk direction)
     int sweep_alt = 0;                 // JCH_SWEEP_ALT and JCH_SWEEP_FUSED_REDUCE=1 as read when the current fit started
     bool sweep_fused_reduce = false;
+    int sweep_resident_mb = -1;        // JCH_SWEEP_RESIDENT_MB, read with them: MiB of the working copy the sweep keeps in the Infinity Cache (< 0: by shape)
     jch_buf gram, xr, yr, xstage, ystage, wstage, tbuf, dnorm, part, kpart, small, colpart, gemm_b, gemm_out, xq, tickets, qz, lw_work, lw_xrm, lvws, lw_flags, lw_screen;
     jch_buf kg_ws, dk_x, dk_y, dk_k, dk_q, dk_o, dk_s;   // Gram kernel workspace (kgram.hip), dkplsr staging (dkplsr.hip)
     jch_buf kp_ws;   // kplsr panels and small state (kplsr.hip)

@@ -206,15 +206,21 @@ __device__ __forceinline__ void jch_slice_sum_by_last_block(const double *__rest
     }
 }
 
-// NT = false, rev alternating launch by launch (JCH_SWEEP_ALT=1, round 4): default-policy loads leave the rows in the 256 MiB
-// Infinity Cache, and a sweep that walks the row groups in the OPPOSITE order of the previous one starts with what that one read
-// last — measured in DESIGN.md §4 / §8.
-template <int KC, int R, int NBUF, bool NT = true>
+// Load policy of the row stream.  NT = true (the default path): non-temporal loads, which stream fastest from HBM, hit lines that are
+// in the 256 MiB Infinity Cache and leave nothing behind in it.  NT = false, rev alternating launch by launch (JCH_SWEEP_ALT=1, round 4):
+// default-policy loads leave the rows in the cache, and a sweep that walks the row groups in the OPPOSITE order of the previous one
+// starts with what that one read last — measured slower, DESIGN.md §4 / §9.  MIX (JCH_SWEEP_RESIDENT_MB > 0): `nres` of the grid's
+// waves, spread evenly over the global wave index (hence over blocks and XCDs), read THEIR row groups with default-policy loads and
+// every other wave with non-temporal ones.  A wave's groups are the same in every sweep of a fit, so that fixed slice of the working
+// copy stays in the cache from sweep to sweep while the rest streams past it, its hits served beside the HBM stream and not in
+// front of it.  The choice is wave-uniform and fixed for the launch: one scalar branch selects between two copies of the row
+// loop.  Which wave reads which rows, and every order of summation, are those of the NT kernel: the same bits come out.
+template <int KC, int R, int NBUF, bool NT = true, bool MIX = false>
 __global__ __launch_bounds__(256) void k_sweep_v2(const double *__restrict__ Xr, int64_t n, int ldr,
                                                   const double *__restrict__ dw, const double *__restrict__ rvec,
                                                   double *__restrict__ tcol, double *__restrict__ part, int ldpart,
                                                   const double *__restrict__ mu, int *__restrict__ tickets,
-                                                  double *__restrict__ zt, int ldz, int nslice, int rev = 0)
+                                                  double *__restrict__ zt, int ldz, int nslice, int rev = 0, int nres = 0)
 {
     extern __shared__ __attribute__((aligned(16))) double red[];  // [nw][KC*128] + [16] tt, st
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -231,7 +237,7 @@ __global__ __launch_bounds__(256) void k_sweep_v2(const double *__restrict__ Xr,
     v2f64 X[NBUF][R][KC];
     double D[NBUF][R];
     const int64_t gbase = rev ? ngroups - 1 : 0, gsign = rev ? -1 : 1;   // group gg of the walk is row group gbase + gsign gg
-    auto fetch = [&](v2f64 (&xb)[R][KC], double (&db)[R], int64_t gg) {
+    auto fetch = [&](auto nt, v2f64 (&xb)[R][KC], double (&db)[R], int64_t gg) {   // nt: std::true_type = non-temporal loads
         const int64_t r0 = (gbase + gsign * gg) * R;
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) {
@@ -239,30 +245,26 @@ __global__ __launch_bounds__(256) void k_sweep_v2(const double *__restrict__ Xr,
             const double *rp = Xr + (size_t)row * (size_t)ldr;
 #pragma unroll
             for (int k = 0; k < KC; ++k) {
-                if constexpr (NT) xb[rr][k] = __builtin_nontemporal_load(reinterpret_cast<const v2f64 *>(rp + coff[k]));
+                if constexpr (decltype(nt)::value) xb[rr][k] = __builtin_nontemporal_load(reinterpret_cast<const v2f64 *>(rp + coff[k]));
                 else xb[rr][k] = *reinterpret_cast<const v2f64 *>(rp + coff[k]);
             }
             db[rr] = dw[row];
         }
     };
-    // the first row groups are requested BEFORE the coefficients (r, mu): one memory latency at the head of every launch
-    // instead of two (the head and tail of a launch are what does not shrink with the rows per GPU)
-    int64_t g = (int64_t)blockIdx.x * nw + wv;
-#pragma unroll
-    for (int b = 0; b < NBUF - 1; ++b)
-        if (g + b * gstride < ngroups) fetch(X[b], D[b], g + b * gstride);
-#pragma unroll
-    for (int k = 0; k < KC; ++k) rf[k] = 2 * lane + 128 * k < ldr ? *reinterpret_cast<const v2f64 *>(rvec + 2 * lane + 128 * k) : v2f64{0.0, 0.0};
     double tt = 0.0, st = 0.0, off = 0.0;
-    if (mu) {   // raw mode: t = x.r - mu.r (see k_sweep)
-        double o = 0.0;
+    auto coefficients = [&] {
 #pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            const v2f64 m2 = *reinterpret_cast<const v2f64 *>(mu + coff[k]);
-            o += m2.x * rf[k].x + m2.y * rf[k].y;                       // rf is zero past the row end
+        for (int k = 0; k < KC; ++k) rf[k] = 2 * lane + 128 * k < ldr ? *reinterpret_cast<const v2f64 *>(rvec + 2 * lane + 128 * k) : v2f64{0.0, 0.0};
+        if (mu) {   // raw mode: t = x.r - mu.r (see k_sweep)
+            double o = 0.0;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                const v2f64 m2 = *reinterpret_cast<const v2f64 *>(mu + coff[k]);
+                o += m2.x * rf[k].x + m2.y * rf[k].y;                       // rf is zero past the row end
+            }
+            off = jch_wave_sum(o);
         }
-        off = jch_wave_sum(o);
-    }
+    };
     auto process = [&](v2f64 (&x)[R][KC], double (&dv)[R], int64_t gg) {
         const int64_t row0 = (gbase + gsign * gg) * R;
         double s[R];
@@ -293,16 +295,36 @@ __global__ __launch_bounds__(256) void k_sweep_v2(const double *__restrict__ Xr,
             if (lane < R && row0 + lane < n) tcol[row0 + lane] = tl;
         }
     };
-    while (g < ngroups) {
+    auto stream = [&](auto nt) {   // this wave's row groups, all with one load policy
+        // the first row groups are requested BEFORE the coefficients (r, mu): one memory latency at the head of every launch
+        // instead of two (the head and tail of a launch are what does not shrink with the rows per GPU)
+        int64_t g = (int64_t)blockIdx.x * nw + wv;
 #pragma unroll
-        for (int b = 0; b < NBUF; ++b) {
-            if (g < ngroups) {   // wave-uniform
-                const int64_t ahead = g + (NBUF - 1) * gstride;
-                if (ahead < ngroups) fetch(X[(b + NBUF - 1) % NBUF], D[(b + NBUF - 1) % NBUF], ahead);
-                process(X[b], D[b], g);
-                g += gstride;
+        for (int b = 0; b < NBUF - 1; ++b)
+            if (g + b * gstride < ngroups) fetch(nt, X[b], D[b], g + b * gstride);
+        coefficients();
+        while (g < ngroups) {
+#pragma unroll
+            for (int b = 0; b < NBUF; ++b) {
+                if (g < ngroups) {   // wave-uniform
+                    const int64_t ahead = g + (NBUF - 1) * gstride;
+                    if (ahead < ngroups) fetch(nt, X[(b + NBUF - 1) % NBUF], D[(b + NBUF - 1) % NBUF], ahead);
+                    process(X[b], D[b], g);
+                    g += gstride;
+                }
             }
         }
+    };
+    if constexpr (MIX) {
+        // wave w of W is resident iff floor((w + 1) nres / W) > floor(w nres / W): nres waves, evenly spaced (nres <= W < 2^16)
+        // A backward walk (the first sweep of a fit) hands this wave the groups that wave (ngroups - 1 - w) mod W reads in the forward
+        // walks: it takes that wave's policy, so the first sweep already leaves the slice of all the later ones behind.
+        const unsigned W = gridDim.x * nw, wme = blockIdx.x * nw + __builtin_amdgcn_readfirstlane(wv);
+        const unsigned w = rev ? (unsigned)((ngroups - 1) % W + W - wme) % W : wme;
+        if (((w + 1u) * (unsigned)nres) / W > (w * (unsigned)nres) / W) stream(std::false_type{});
+        else stream(std::true_type{});
+    } else {
+        stream(std::integral_constant<bool, NT>{});
     }
     // ---- combine the waves of the block in wave order, then one partial row per block
     double *zred = red;                     // [nw][KC*128]
@@ -611,8 +633,29 @@ static int32_t launch_sweep_v2_t(jch_ctx *ctx, const double *Xr, int64_t n, int 
     // the row groups within a block's partial sums for that one LV; every fit and every rank does the same, so repeated fits and the replicated
     // state stay bit-identical.  (Backwards with default-policy loads was measured SLOWER than either direction with streaming loads.)
     const bool first = ctx->sweep_seq++ == 0u;
-    hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
-                       tickets, zt, ldz, fused ? nslice : 0, first ? 1 : 0);
+    // JCH_SWEEP_RESIDENT_MB: the waves that read with default-policy loads (see k_sweep_v2) — as many as it takes for their row groups
+    // to make up the slice at this launch's n, ldr and grid (at least one), so every rank derives the set from its own shard, and every
+    // sweep of a fit and every fit on the ctx keep the same rows.  The slice never exceeds the cache; a copy that fits the slice
+    // altogether is read with default-policy loads by every wave.  Unset: 128 MiB for 500-column rows (KC = 4) and a copy of at least
+    // 7 x the cache, nothing otherwise — measured (profiles/resident_slice_scan.log): sweeps of a fit 14.53 -> 14.26 ms at
+    // 1e6 rows and 7.39 -> 7.17 at 500 k, nothing beyond the run-to-run spread at 250 k and 125 k rows, and at 1000 columns the sweeps'
+    // gain (14.15 -> 13.86 ms at 500 k rows) is less than what the small-state kernels lose beside the occupied cache (3.4 -> 4.0 ms).
+    int resident_mb = ctx->sweep_resident_mb;
+    if (resident_mb < 0)
+        resident_mb = KC == 4 && (double)n * ldr * sizeof(double) >= 7.0 * JCH_INFINITY_CACHE_MIB * 1048576.0 ? JCH_RESIDENT_DEFAULT_MIB : 0;
+    int nres = 0;
+    if constexpr (KC == 4 || KC == 8)   // (the narrow sweeps run several blocks per CU and have no second copy of the loop)
+    if (resident_mb > 0 && bpc == 1) {
+        const int64_t W = (int64_t)nb * 4;
+        const double wave_bytes = (double)ngroups / (double)W * R * ldr * sizeof(double);
+        nres = (int)std::max<int64_t>(1, std::min<int64_t>(W, (int64_t)(std::min(resident_mb, JCH_INFINITY_CACHE_MIB) * 1048576.0 / wave_bytes)));
+    }
+    if (nres > 0)
+        hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true, KC == 4 || KC == 8>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
+                           tickets, zt, ldz, fused ? nslice : 0, first ? 1 : 0, nres);
+    else
+        hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
+                           tickets, zt, ldz, fused ? nslice : 0, first ? 1 : 0);
     }
     if (timed) (void)jch_ev(ctx);  // (end)
     if (pv && !fused) {   // split small-state path: k_lv_spread sums the block partials itself (no k_reduce_part launch)
