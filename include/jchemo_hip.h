@@ -416,6 +416,38 @@ JCH_API int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double gam
                              double *P, double *vtot, double *weights_norm, double *xscales, double *sv, double *eig, double *sstot,
                              int32_t *niter, double *resid, int32_t *nlv_out);
 
+/* ---- kernel ridge regression (src/krr.jl:1-202, LS-SVM) by a device Cholesky of the Gram -------------------------------------
+ * The reference takes svd(Kd) of Kd = sqrtD Kc sqrtD (src/krr.jl:152) and keeps U (n x n), UtDY and sv.  Its outputs do not need
+ * them: coef(lb).A = U diag(1 / (eig + lb^2)) U' sqrtD Y = (Kd + lb^2 I)^-1 sqrtD Y (:170-172) and coef(lb).df = 1 + sum eig /
+ * (eig + lb^2) = 1 + n - lb^2 trace((Kd + lb^2 I)^-1) (:175-176).  Kd + lb^2 I is symmetric positive definite for a PSD kernel
+ * and lb > 0, so the fit keeps Kd and every lb is one blocked Cholesky factorisation on the f64 matrix cores.
+ * Deviation: there are no U, UtDY and sv outputs.
+ *
+ * jch_krr_fit — `krr!` / `krr` (src/krr.jl:128-159) up to the SVD: w = mweight(weights) (:135); with scal xscales = colstd(X, w) and
+ * X DIVIDED by them in place (:136-140; X is not centred, Y is not touched); ymeans = colmean(Y, w) (:141); K = kern(X, X) (:143),
+ * vtot = K w (:145-146), Kc = K - vtot' - vtot + w'vtot (:147) by the launches of jch_kplsr_fit / jch_kpca_fit (same bits);
+ * Kd = sqrtD Kc sqrtD (:150-151); B = sqrtD Y (Y raw, as `U' * sqrtD * Y` :156).
+ *   X n x p (ldx), Y n x q (ldy), weights n or NULL [loc]; kind / gamma / coef0 / degree as jch_kernel_gram.
+ *   Outputs: Kd a caller-owned DEVICE n x n buffer (ld n; required); K_out a DEVICE n x n buffer that receives the UNcentred Gram
+ *   (the reference's Krr.K), or NULL; B n x q (ld n), vtot n, weights_norm n [loc]; xscales p (ones without scal), ymeans q HOST;
+ *   any of the last five may be NULL.  Float64 only; one GPU (a communicator of more than one rank: JCH_EINVAL). */
+JCH_API int32_t jch_krr_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, double coef0, int32_t degree, double *X, int64_t n, int64_t p,
+                            int64_t ldx, const double *Y, int64_t q, int64_t ldy, const double *weights, int32_t scal, double *Kd, double *K_out,
+                            double *B, double *vtot, double *weights_norm, double *xscales, double *ymeans);
+
+/* jch_krr_solve — `coef(object::Krr; lb)` (src/krr.jl:168-177): a copy of Kd in ctx workspace gets lb^2 added to its diagonal, is
+ * factored (jch_chol_factor's kernels) and A = (Kd + lb^2 I)^-1 B is solved for (:170-172); alpha = sqrtD A is what `predict`
+ * multiplies the centred Gram of the new rows with (:198): `predict(object::Krr, X; lb)` (:187-202) is jch_kplsr_transform with
+ * R = the alphas of all requested lb side by side (n x (q le_lb)), plus ymeans.  With want_df, df = 1 + n - lb^2 |L^-1|_F^2
+ * (:175-176; jch_chol_inv_fro2's kernels, one more n x n workspace: JCH_ENOMEM with a message that names df when it cannot be had).
+ *   Kd DEVICE n x n (ld n, from jch_krr_fit; not modified); B n x q (ld n), weights_norm n [loc]; lb finite and > 0 (lb = 0 is
+ *   singular by construction, Kd sqrt(w) = 0, and gives Inf / NaN in the reference): JCH_EINVAL otherwise.
+ *   Outputs: A, alpha n x q (ld n) [loc]; df 1 HOST (required with want_df); info 1 HOST: 0, or the 1-based column whose pivot was not
+ *   > 0 — then the kernel / parameter set is not PSD enough for this lb, the call returns JCH_EINVAL with that column in the message
+ *   and A, alpha, df are not written.  The next call on the ctx works as usual. */
+JCH_API int32_t jch_krr_solve(jch_ctx *ctx, int32_t loc, const double *Kd, int64_t n, const double *B, int64_t q, const double *weights_norm,
+                              double lb, int32_t want_df, double *A, double *alpha, double *df, int32_t *info);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in
@@ -426,6 +458,20 @@ JCH_API int32_t jch_fill_uniform(jch_ctx *ctx, double *dev_out, int64_t n, int64
 /* out (n x b, ld ldo) = Kc V, Kc n x n (ld n), V n x b (ld ldv), all DEVICE pointers: the panel product of jch_kpca_fit on the
  * f64 matrix cores (any b >= 1, in chunks of 64 columns).  Every output is one workgroup's fixed-order sum. */
 JCH_API int32_t jch_kc_panel(jch_ctx *ctx, const double *Kc, int64_t n, const double *V, int64_t ldv, int32_t b, double *out, int64_t ldo);
+
+/* The dense direct solver under jch_krr_solve on its own, DEVICE pointers, column-major.
+ * jch_chol_factor: A (n x n, ld lda >= n, any n >= 1) = L L' in place on the f64 matrix cores; only the lower triangle of A is read
+ *   and written.  *info (HOST) = 0, or the 1-based index of the first column whose pivot was not > 0 (negative, zero, NaN): a
+ *   result, not an error — the call returns JCH_OK, A is then partly overwritten and there is no factor to solve with.  The
+ *   inverses of the 128 x 128 diagonal blocks stay in ctx workspace, keyed to (A, n, lda).
+ * jch_chol_solve: B (n x q, ld ldb, any q >= 1) = (L L')^-1 B in place with the factor the LAST jch_chol_factor of this ctx left in
+ *   L; any other L, n or ldl is JCH_EINVAL, not a wrong answer.
+ * jch_chol_inv_fro2: *out (HOST) = |L^-1|_F^2 = trace((L L')^-1) for that same factor; n^3/3 flop and an n x n workspace in the ctx
+ *   (JCH_ENOMEM when it cannot be had).
+ * Every output element is a fixed-order sum: two runs give identical bits. */
+JCH_API int32_t jch_chol_factor(jch_ctx *ctx, double *A, int64_t n, int64_t lda, int32_t *info);
+JCH_API int32_t jch_chol_solve(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *B, int64_t q, int64_t ldb);
+JCH_API int32_t jch_chol_inv_fro2(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *out);
 
 typedef struct jch_profile {
     double fit_ms;        /* device time of the last fit, first kernel -> last kernel (HIP events)   */

@@ -82,6 +82,9 @@ struct jch_ctx {
     jch_buf kg_ws, dk_x, dk_y, dk_k, dk_q, dk_o, dk_s;   // Gram kernel workspace (kgram.hip), dkplsr staging (dkplsr.hip)
     jch_buf kp_ws;   // kplsr panels and small state (kplsr.hip)
     jch_buf kc_vt, pc_ws;   // panel operand of the Kc pass, kpca panels and small state (kpca.hip)
+    jch_buf chol_inv, chol_a, chol_w, chol_s, kr_ws;   // inv(L_kk) blocks of the last factor, krr's working copy of Kd, the L^-T workspace of df, info / partial sums (chol.hip); krr staging (krr.hip)
+    const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
+    int64_t chol_n = 0, chol_ld = 0;
     // profiling
     bool profiling = false;
     int prof_stride = 1;        // jch_ctx_set_profiling(ctx, N > 1): event pairs around every N-th launch of the sampled dominant kernels only
@@ -289,6 +292,13 @@ int32_t jch_launch_kp_centred_gram(jch_ctx *ctx, int kind, double gamma, double 
 // kpca.hip: out (n x b, ld ldo) = Kc (diag(d) V) on the f64 matrix cores (d: device n-vector or null); any b, chunks of 64 columns
 int32_t jch_launch_kc_panel(jch_ctx *ctx, const double *Kc, int64_t n, int64_t ldk, const double *V, int64_t ldv, int b, const double *d,
                             double *out, int64_t ldo);
+// chol.hip: blocked Cholesky of the lower triangle of A (n x n, ld lda, in place), everything on ctx->stream, no host sync.  info_dev: a device
+// int that ends up 0 or the 1-based index of the first pivot that is not > 0.  The solves and jch_launch_chol_inv_fro2 need the factor the
+// last jch_launch_chol_factor produced (its inv(L_kk) blocks live in ctx->chol_inv).
+int32_t jch_launch_chol_factor(jch_ctx *ctx, double *A, int64_t n, int64_t lda, int *info_dev);
+int32_t jch_launch_chol_solve(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *B, int64_t q, int64_t ldb, const int *info_dev);
+int32_t jch_launch_chol_inv_fro2(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *out_dev, const int *info_dev);
+int32_t jch_chol_info_word(jch_ctx *ctx, int **info_dev);   // the ctx's own device info word
 // util.hip
 int32_t jch_launch_fill(jch_ctx *ctx, double *out, int64_t n, int64_t p, int64_t ld, int64_t row0, int64_t n_total,
                         uint64_t seed);

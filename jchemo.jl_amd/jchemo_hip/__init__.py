@@ -4,3 +4,4 @@ from ._lib import Context, JchError, LIB_PATH, SYMBOLS, default_context, load, u
 from .plsr import (Lwplsr, LwplsrPred, Plsr, coef, lwplsr, lwplsr_predict, query_shard, colmajor_empty, ensure_mat, plskern, plskern_, plsnipals, plsnipals_, plssimp, plssimp_, plsrosa, plsrosa_, plswold, plswold_, predict,  # noqa: F401
                    summary, transform, vip, xfit, xresid, msep, rmsep, ssr, bias, r2, cor2, segmkf, segmts, gridscorelv, gridcvlv, mpar, Plsrda, dummy, plsrda, plsrda_predict, Plslda, plslda, plsqda, plslda_predict, Mbplsr, mbplsr, mbplsr_transform, mbplsr_predict,
                    Dkplsr, dkplsr, dkplsr_, krbf, kpol, Kplsr, kplsr, kplsr_, Kpca, kpca, kpca_transform, kpca_summary)
+from .krr import Krr, Krrda, gridscorelb, krr, krr_, krr_coef, krr_predict, krrda, krrda_predict  # noqa: F401

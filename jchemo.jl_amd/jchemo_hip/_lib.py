@@ -31,6 +31,7 @@ SYMBOLS = (
     "jch_ctx_get_counter", "jch_ctx_allreduce_probe", "jch_lwplsr_prepare", "jch_lwplsr_predict_prepared", "jch_lwplsr_release", "jch_lwplsr_add_query_map",
     "jch_kernel_gram", "jch_dkplsr_fit", "jch_dkplsr_transform", "jch_dkplsr_predict",
     "jch_kplsr_fit", "jch_kplsr_transform", "jch_kplsr_predict", "jch_kpca_fit", "jch_kc_panel",
+    "jch_krr_fit", "jch_krr_solve", "jch_chol_factor", "jch_chol_solve", "jch_chol_inv_fro2",
 )
 
 
@@ -117,6 +118,11 @@ def load():
     L.jch_kpca_fit.argtypes = [vp, i32, i32, f64, f64, i32, dp, i64, i64, i64, dp, i32, i32, f64, i32] + [dp] * 9 + [C.POINTER(i32), dp,
                                                                                                             C.POINTER(i32)]
     L.jch_kc_panel.argtypes = [vp, dp, i64, dp, i64, i32, dp, i64]
+    L.jch_krr_fit.argtypes = [vp, i32, i32, f64, f64, i32, dp, i64, i64, i64, dp, i64, i64, dp, i32] + [dp] * 7
+    L.jch_krr_solve.argtypes = [vp, i32, dp, i64, dp, i64, dp, f64, i32, dp, dp, dp, C.POINTER(i32)]
+    L.jch_chol_factor.argtypes = [vp, dp, i64, i64, C.POINTER(i32)]
+    L.jch_chol_solve.argtypes = [vp, dp, i64, i64, dp, i64, i64]
+    L.jch_chol_inv_fro2.argtypes = [vp, dp, i64, i64, C.POINTER(C.c_double)]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]
     L.jch_ctx_set_profiling.argtypes = [vp, i32]
     L.jch_ctx_get_profile.argtypes = [vp, C.POINTER(Profile)]

@@ -31,7 +31,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        lwplsr, transform, coef, predict, explvarx, JchCtx, attach!, nipals_one_pass!,
        msep, rmsep, ssr, bias, r2, cor2, mpar, segmkf, segmts, gridscorelv, gridcvlv,
        Plsrda, dummy, plsrda, Mbplsr, mbplsr, vip, xfit, xresid,
-       Dkplsr, dkplsr, dkplsr!, krbf, kpol, Kplsr, kplsr, kplsr!, Kpca, kpca
+       Dkplsr, dkplsr, dkplsr!, krbf, kpol, Kplsr, kplsr, kplsr!, Kpca, kpca,
+       Krr, krr, krr!, gridscorelb, Krrda, krrda
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -1132,6 +1133,156 @@ function Base.summary(object::Kpca; ctx = default_ctx())
     tt = st.stds .^ 2 .+ st.means .^ 2
     pvar = tt ./ object.sstot
     (explvarx = _table((lv = collect(1:length(tt)), var = tt, pvar = pvar, cumpvar = cumsum(pvar))),)
+end
+
+# ---- kernel ridge regression (src/krr.jl, src/krrda.jl, gridscorelb of src/gridscore.jl:235-284): Kd stays on the device and every lb
+# is one Cholesky factorisation of Kd + lb^2 I there (include/jchemo_hip.h jch_krr_fit / jch_krr_solve; DESIGN.md §13) ------------------
+struct Krr                        # the reference's struct (src/krr.jl:1-17) without U, UtDY and sv (no SVD is taken): Kd = sqrtD Kc sqrtD
+    X                             # (n x n, always a device array) and B = sqrtD Y take their place; `solved` caches per lb what coef
+    Kd                            # computed (A, alpha = sqrtD A, df)
+    B
+    vtot
+    lb::Float64
+    xscales::Vector{Float64}
+    ymeans::Vector{Float64}
+    weights
+    kern
+    dots
+    solved::Dict{Float64, Any}
+end
+
+_check_lb(lb) = (isfinite(lb) && lb > 0) ? Float64(lb) : throw(ArgumentError("lb = $lb must be finite and > 0 (Kd is singular by construction)"))
+
+# an n x n device matrix next to X: for a host X through AMDGPU.jl, which must be loaded (Kd never goes to the host)
+function _device_square(X, n)
+    X isa Array || return _similar(X, n, n)
+    for (id, m) in Base.loaded_modules
+        id.name == "AMDGPU" && return Base.invokelatest(getfield(m, :ROCArray){Float64}, undef, n, n)
+    end
+    error("krr: Kd (n x n) stays on the device; load AMDGPU.jl first (`using AMDGPU`) or pass device arrays")
+end
+
+function _krr_fit!(X, Y, weights, lb, kern, scal, ctx, kwargs)
+    kind, gamma, coef0, degree = _kern_args(kern, kwargs)
+    lb = _check_lb(lb)
+    n, p = size(X); q = size(Y, 2)
+    size(Y, 1) == n || throw(DimensionMismatch("X has $n rows, Y has $(size(Y, 1))"))
+    weights = _w(weights, X)
+    weights === nothing || length(weights) == n || throw(DimensionMismatch("weights has $(length(weights)) entries, X has $n rows"))
+    Kd = _device_square(X, n)
+    B = _similar(X, n, q); vt = _similar(X, 1, n); wn = _similar(X, n)
+    xs = ones(p); ym = zeros(q)
+    GC.@preserve X Y weights Kd B vt wn check(ctx, ccall((:jch_krr_fit, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), n, p, stride(X, 2), pointer(Y), q, max(stride(Y, 2), n),
+        weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights), Int32(scal ? 1 : 0), pointer(Kd), Ptr{Float64}(C_NULL),
+        pointer(B), pointer(vt), pointer(wn), xs, ym))
+    Krr(X, Kd, B, vt, lb, xs, ym, wn, kern, kwargs, Dict{Float64, Any}())
+end
+
+"""`krr(X, Y, weights; lb, kern = "krbf", scal = false, kwargs...)` — src/krr.jl:122-126 on copies (X and Y are left untouched).  No
+SVD is taken: the record keeps Kd on the device instead of U, UtDY and sv, and `coef` / `predict` solve per lb by Cholesky."""
+function krr(X, Y, weights = nothing; lb, kern = "krbf", scal = false, ctx = default_ctx(), kwargs...)
+    X = copy(_in(X))
+    _krr_fit!(X, _colocate_mat(_in(Y), X), weights, lb, kern, scal, ctx, kwargs)
+end
+"`krr!(X, Y, weights; lb, kern, scal, kwargs...)` — src/krr.jl:128-159: with `scal`, X is divided by its column stds in place; Y is not touched."
+function krr!(X, Y, weights = nothing; lb, kern = "krbf", scal = false, ctx = default_ctx(), kwargs...)
+    _krr_fit!(X, Y, weights, lb, kern, scal, ctx, kwargs)
+end
+
+function _krr_solve(object::Krr, lb, want_df, ctx)
+    hit = get(object.solved, lb, nothing)
+    hit === nothing || (want_df && hit.df === nothing) || return hit
+    n, q = size(object.B)
+    A = _similar(object.X, n, q); al = _similar(object.X, n, q)
+    Kd = object.Kd; B = object.B; wn = object.weights
+    df = Ref{Float64}(NaN); info = Ref{Int32}(0)
+    GC.@preserve Kd B wn A al check(ctx, ccall((:jch_krr_solve, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
+         Ref{Int32}),
+        ctx.h, _loc(object.X), pointer(Kd), n, pointer(B), q, pointer(wn), lb, Int32(want_df ? 1 : 0), pointer(A), pointer(al), df, info))
+    hit = (A = A, alpha = al, df = want_df ? df[] : nothing)
+    object.solved[lb] = hit
+    hit
+end
+
+"""`coef(object::Krr; lb = nothing)` — src/krr.jl:168-177: `(A, int, df)` with A = (Kd + lb^2 I)^-1 sqrtD Y and df = 1 + sum eig /
+(eig + lb^2), computed as 1 + n - lb^2 |L^-1|_F^2 from the Cholesky factor."""
+function coef(object::Krr; lb = nothing, ctx = default_ctx())
+    lb = lb === nothing ? object.lb : _check_lb(lb)
+    z = _krr_solve(object, lb, true, ctx)
+    (A = z.A, int = reshape(object.ymeans, 1, :), df = z.df)
+end
+
+"""`predict(object::Krr, X; lb = nothing)` — src/krr.jl:187-202: ymeans + Kc_new sqrtD A(lb); one lb gives a matrix, a collection a
+vector of matrices, all from ONE pass over the Gram blocks of the new rows (jch_kplsr_transform with the alphas side by side)."""
+function predict(object::Krr, X; lb = nothing, ctx = default_ctx())
+    lbs = lb === nothing ? [object.lb] : [_check_lb(v) for v in lb]
+    kind, gamma, coef0, degree = _kern_args(object.kern, object.dots)
+    X = _in(X); Xt = object.X; m, p = size(X); n = size(Xt, 1); q = size(object.B, 2)
+    size(Xt, 2) == p || throw(DimensionMismatch("X has $p columns, the model has $(size(Xt, 2))"))
+    R = reduce(hcat, [Matrix{Float64}(Array(_krr_solve(object, v, false, ctx).alpha)) for v in lbs])
+    k = size(R, 2)
+    T = _similar(X, m, k)
+    xs = Vector{Float64}(object.xscales); w = Vector{Float64}(vec(object.weights)); vt = Vector{Float64}(vec(object.vtot))
+    GC.@preserve X Xt T R xs w vt check(ctx, ccall((:jch_kplsr_transform, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), kind, gamma, coef0, degree, pointer(X), m, p, stride(X, 2), pointer(xs), pointer(Xt), n, stride(Xt, 2),
+        pointer(w), pointer(vt), pointer(R), k, pointer(T), max(m, 1)))
+    out = _affine(T, nothing, nothing, Matrix{Float64}(I, k, k), repeat(object.ymeans, length(lbs)), ctx)   # + ymeans (:198)
+    pred = [out[:, (i - 1) * q + 1:i * q] for i in 1:length(lbs)]
+    (pred = length(lbs) == 1 ? pred[1] : pred,)
+end
+
+"""
+    gridscorelb(Xtrain, Ytrain, X, Y; score, fun, lb, pars = nothing, verbose = false)
+
+src/gridscore.jl:235-284: one fit (at `maximum(lb)`) per parameter combination and ONE `predict` over all lb (`mlev(lb)`: the sorted
+distinct values).  Returns the reference's table: the columns `<pars...>, lb, y1 ... yq`, one row per (combination, lb),
+combination-major (a `DataFrame` when DataFrames is loaded).  `pars` must not contain `lb`.
+"""
+function gridscorelb(Xtrain, Ytrain, X, Y; score, fun, lb, pars = nothing, verbose = false, ctx = default_ctx())
+    pars === nothing || !(:lb in keys(pars)) || error("Argument `pars` must not contain `lb`")
+    lbs = sort(unique([_check_lb(v) for v in lb]))
+    rows = _pars_rows(pars)
+    verbose && println(pars === nothing ? "-- Nb. combinations = 0." : "-- Nb. combinations = $(length(rows))")
+    blocks = Matrix{Float64}[]
+    for kw in rows
+        verbose && pars !== nothing && println(pairs(kw)...)
+        fm = fun(Xtrain, Ytrain; lb = maximum(lbs), kw...)
+        pr = predict(fm, X; lb = lbs).pred
+        pr = length(lbs) == 1 ? [pr] : pr
+        push!(blocks, reduce(vcat, [reshape(collect(score(z, Y)), 1, :) for z in pr]))
+    end
+    verbose && println("-- End.")
+    res = reduce(vcat, blocks)
+    cols = NamedTuple()
+    if pars !== nothing
+        cols = NamedTuple{keys(pars)}(Tuple([r[nm] for r in rows for _ in lbs] for nm in keys(pars)))
+    end
+    cols = merge(cols, (lb = repeat(lbs, length(rows)),))
+    _table(merge(cols, NamedTuple{_ynames(size(res, 2))}(Tuple(res[:, j] for j in 1:size(res, 2)))))
+end
+
+struct Krrda                      # what the reference's `krrda` returns (its Rrda, src/krrda.jl:65)
+    fm; lev; ni
+end
+"`krrda(X, y, weights; lb, kern = \"krbf\", scal = false, kwargs...)` — src/krrda.jl:59-66: `krr` on `dummy(y)`."
+function krrda(X, y, weights = nothing; lb, kern = "krbf", scal = false, ctx = default_ctx(), kwargs...)
+    res = dummy(y); yv = vec(Array(y))
+    ni = [count(==(l), yv) for l in res.lev]
+    X = _in(X)
+    Krrda(krr(X, _colocate_mat(res.Y, X), weights; lb = lb, kern = kern, scal = scal, ctx = ctx, kwargs...), res.lev, ni)
+end
+"`predict(object::Krrda, X; lb)` — src/rrda.jl:79-97: `(pred, posterior)`, pred the level of the largest posterior (the first on ties)."
+function predict(object::Krrda, X; lb = nothing, ctx = default_ctx())
+    post = predict(object.fm, X; lb = lb, ctx = ctx).pred
+    posts = post isa AbstractMatrix ? [post] : post
+    preds = [reshape(object.lev[[argmax(view(Array(z), i, :)) for i in 1:size(z, 1)]], :, 1) for z in posts]
+    post isa AbstractMatrix ? (pred = preds[1], posterior = posts[1]) : (pred = preds, posterior = posts)
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
