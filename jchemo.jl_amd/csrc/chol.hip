@@ -27,23 +27,19 @@
 #include <algorithm>
 
 #include "jch_internal.h"
+#include "tile128_dev.h"
 
-typedef double ch_v2d __attribute__((ext_vector_type(2)));
-typedef double ch_v4d __attribute__((ext_vector_type(4)));
-
-#define CH_NB 128    // block width of the factorisation = tile edge
-#define CH_KB 16     // k-columns per staged chunk
-#define CH_LD 144    // LDS row stride (doubles) of a staged chunk, as k_gram
+#define CH_NB T128_T // block width of the factorisation = tile edge
 #define CH_QC 8      // columns of B per workgroup of the solve kernels
 #define CH_SUMSQ_WG 1024
 
 // two consecutive rows r, r + 1 of column k of a column-major panel; zero beyond nvalid rows / kdim columns
-__device__ __forceinline__ ch_v2d ch_ld2(const double *P, int64_t ld, int64_t r, int64_t nvalid, int k, int kdim, bool vec)
+__device__ __forceinline__ t128_v2d ch_ld2(const double *P, int64_t ld, int64_t r, int64_t nvalid, int k, int kdim, bool vec)
 {
-    ch_v2d v{0.0, 0.0};
+    t128_v2d v{0.0, 0.0};
     if (k >= kdim) return v;
     const double *c = P + (size_t)k * (size_t)ld;
-    if (vec && r + 1 < nvalid) return *reinterpret_cast<const ch_v2d *>(c + r);
+    if (vec && r + 1 < nvalid) return *reinterpret_cast<const t128_v2d *>(c + r);
     if (r < nvalid) v.x = c[r];
     if (r + 1 < nvalid) v.y = c[r + 1];
     return v;
@@ -58,68 +54,21 @@ __global__ __launch_bounds__(256, 2) void k_chol_tile(const double *R, int64_t l
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (*info != 0) return;
-    double *As = lds;                            // [2][CH_KB][CH_LD]  Q tile (output columns j: the MFMA's rows)
-    double *Bs = lds + 2 * CH_KB * CH_LD;        // [2][CH_KB][CH_LD]  R tile (output rows i: the MFMA's columns, the contiguous direction)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int64_t ti, tj;
-    if (MODE == 1) {   // linear index -> (tj <= ti): ti (ti + 1) / 2 <= b < (ti + 1)(ti + 2) / 2
-        const int64_t b = blockIdx.x;
-        int64_t t = (int64_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-        while (t * (t + 1) / 2 > b) --t;
-        while ((t + 1) * (t + 2) / 2 <= b) ++t;
-        ti = t; tj = b - t * (t + 1) / 2;
+    if (MODE == 1) {
+        t128_tri(blockIdx.x, tj, ti);   // tj <= ti
     } else {
         ti = blockIdx.x % tiles_i; tj = blockIdx.x / tiles_i;
     }
     const int64_t i0 = ti * CH_NB, j0 = tj * CH_NB;
     const int qj = wv >> 1, qi = wv & 1;
-    ch_v4d acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = ch_v4d{0.0, 0.0, 0.0, 0.0};
-    ch_v2d va[4], vb[4];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int k = k0 + wv * 4 + it;
-            va[it] = ch_ld2(Q, ldq, j0 + 2 * lane, ncol, k, kdim, vq);
-            vb[it] = ch_ld2(R, ldr, i0 + 2 * lane, nrow, k, kdim, vr);
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int row = wv * 4 + it;
-            *reinterpret_cast<ch_v2d *>(As + (buf * CH_KB + row) * CH_LD + 2 * lane) = va[it];
-            *reinterpret_cast<ch_v2d *>(Bs + (buf * CH_KB + row) * CH_LD + 2 * lane) = vb[it];
-        }
-    };
-    const int nch = (kdim + CH_KB - 1) / CH_KB;
-    load(0);
-    stage(0);
-    __syncthreads();
-    for (int ch = 0; ch < nch; ++ch) {
-        const int buf = ch & 1;
-        if (ch + 1 < nch) load((ch + 1) * CH_KB);
-        const double *A = As + buf * CH_KB * CH_LD, *B = Bs + buf * CH_KB * CH_LD;
-#pragma unroll
-        for (int kk = 0; kk < CH_KB / 4; ++kk) {
-            const int krow = 4 * kk + (lane >> 4);
-            double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[u] = A[krow * CH_LD + 64 * qj + 16 * u + (lane & 15)];
-                b[u] = B[krow * CH_LD + 64 * qi + 16 * u + (lane & 15)];
-            }
-#pragma unroll
-            for (int mj = 0; mj < 4; ++mj)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mj][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mj], b[ni], acc[mj][ni], 0, 0, 0);
-        }
-        if (ch + 1 < nch) stage(buf ^ 1);
-        __syncthreads();
-    }
+    t128_v4d acc[4][4];   // A = Q tile (output columns j: the MFMA's rows), B = R tile (output rows i: the MFMA's columns, the contiguous direction)
+    t128_mma(
+        lds, (kdim + T128_KB - 1) / T128_KB,
+        [&](int k, int c) { return ch_ld2(Q, ldq, j0 + c, ncol, k, kdim, vq); },
+        [&](int k, int c) { return ch_ld2(R, ldr, i0 + c, nrow, k, kdim, vr); },
+        acc);
     // acc[mj][ni][reg] = sum_t Q[j, t] R[i, t], j = j0 + 64 qj + 16 mj + (lane >> 4) + 4 reg, i = i0 + 64 qi + 16 ni + (lane & 15):
     // every load / store instruction touches 128-byte pieces of columns of C
 #pragma unroll
@@ -308,7 +257,6 @@ __global__ __launch_bounds__(256) void k_chol_sum1(const double *__restrict__ pa
 
 namespace {
 
-constexpr size_t CH_TILE_LDS = sizeof(double) * 4 * CH_KB * CH_LD;                  // 73 728 B: two workgroups per CU
 constexpr size_t CH_DIAG_LDS = sizeof(double) * (CH_NB * CH_NB + CH_NB + 256);      // 134 144 B
 
 bool ch_vec(const double *P, int64_t ld) { return ((uintptr_t)P % 16) == 0 && (ld % 2) == 0; }
@@ -334,7 +282,7 @@ int32_t launch_tile(jch_ctx *ctx, const double *R, int64_t ldr, int64_t nrow, co
     const int64_t ti = (nrow + CH_NB - 1) / CH_NB, tj = (ncol + CH_NB - 1) / CH_NB;
     const int64_t nblocks = MODE == 1 ? ti * (ti + 1) / 2 : ti * tj;
     if (nblocks > 0x7fffffffLL) return jch_fail(ctx, JCH_EINVAL, "cholesky: shape too large (%lld x %lld tiles)", (long long)ti, (long long)tj);
-    hipLaunchKernelGGL(k_chol_tile<MODE>, dim3((unsigned)nblocks), dim3(256), CH_TILE_LDS, ctx->stream, R, ldr, nrow, ch_vec(R, ldr), Q, ldq, ncol,
+    hipLaunchKernelGGL(k_chol_tile<MODE>, dim3((unsigned)nblocks), dim3(256), T128_LDS_BYTES, ctx->stream, R, ldr, nrow, ch_vec(R, ldr), Q, ldq, ncol,
                        ch_vec(Q, ldq), kdim, C, ldc, (int)ti, info);
     JCH_HIP(ctx, hipGetLastError());
     return JCH_OK;

@@ -7,53 +7,7 @@
 
 #include "jch_internal.h"
 
-// A[:, k] /= s[k]  (`scale!`, src/utility.jl: X ./ xscales')
-__global__ __launch_bounds__(256) void k_dk_divcols(double *__restrict__ A, int64_t lda, int64_t n, int64_t cols, const double *__restrict__ s)
-{
-    const int64_t tot = n * cols;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (int64_t)gridDim.x * 256) {
-        const int64_t k = e / n, i = e - k * n;
-        A[(size_t)i + (size_t)k * (size_t)lda] /= s[k];
-    }
-}
-
 namespace {
-
-int32_t check_kernel(jch_ctx *ctx, const char *who, int32_t kind, int32_t degree)
-{
-    if (kind != JCH_KERN_RBF && kind != JCH_KERN_POL) return jch_fail(ctx, JCH_EINVAL, "%s: unknown kernel kind %d", who, kind);
-    if (kind == JCH_KERN_POL && degree < 1) return jch_fail(ctx, JCH_EINVAL, "%s: degree = %d must be >= 1", who, degree);
-    if (ctx->nranks > 1) return jch_fail(ctx, JCH_EINVAL, "%s: the Gram matrix is not sharded: one rank only (communicator of %d)", who, ctx->nranks);
-    return JCH_OK;
-}
-
-// column-major rows x cols matrix (ld) between host and device, into / from a tight (ld = rows) or strided device buffer
-int32_t h2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols)
-{
-    JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * ldd, src, sizeof(double) * lds, sizeof(double) * rows, cols, hipMemcpyHostToDevice, ctx->stream));
-    return JCH_OK;
-}
-int32_t d2h(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols)
-{
-    JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * ldd, src, sizeof(double) * lds, sizeof(double) * rows, cols, hipMemcpyDeviceToHost, ctx->stream));
-    return JCH_OK;
-}
-
-int32_t divcols(jch_ctx *ctx, double *A, int64_t lda, int64_t n, int64_t cols, const double *sdev)
-{
-    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n * cols + 255) / 256, (int64_t)ctx->cus * 16));
-    hipLaunchKernelGGL(k_dk_divcols, dim3(nb), dim3(256), 0, ctx->stream, A, lda, n, cols, sdev);
-    JCH_HIP(ctx, hipGetLastError());
-    return JCH_OK;
-}
-
-// rows of new data per Gram block: JCH_DKPLSR_QBLOCK, else 1 GiB of Gram (2^27 doubles)
-int64_t qblock(int64_t n)
-{
-    const int v = jch_knob("JCH_DKPLSR_QBLOCK", 0);
-    if (v >= 1) return v;
-    return std::max<int64_t>(1, ((int64_t)1 << 27) / n);
-}
 
 // transform (pred == false) or predict over the new rows, block by block
 struct dk_model {
@@ -65,47 +19,15 @@ int32_t dk_apply(jch_ctx *ctx, const char *who, int32_t loc, int32_t kind, doubl
                  int64_t p, int64_t ldx, const double *xscale, const double *Xt, int64_t n, int64_t ldxt, const dk_model &md, bool pred,
                  int64_t ncols, double *out, int64_t ldo)
 {
-    if (!ctx) return JCH_EINVAL;
-    JCH_TRY(check_kernel(ctx, who, kind, degree));
-    if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "%s: bad loc %d", who, loc);
-    if (!X || !Xt || !out || m < 0 || n < 1 || p < 1 || ldx < m || ldxt < n || ldo < m)
-        return jch_fail(ctx, JCH_EINVAL, "%s: bad arguments (m=%lld n=%lld p=%lld ldx=%lld ldxt=%lld ldo=%lld)", who, (long long)m, (long long)n,
-                        (long long)p, (long long)ldx, (long long)ldxt, (long long)ldo);
-    if (m == 0) return JCH_OK;
-    JCH_HIP(ctx, hipSetDevice(ctx->device));
-    const bool host = loc == JCH_LOC_HOST;
-    const int64_t mb = std::min<int64_t>(m, qblock(n));
-    const double *dXt = Xt;
-    int64_t ldxtd = ldxt;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(h2d(ctx, (double *)ctx->dk_x.ptr, n, Xt, ldxt, n, p));
-        dXt = (const double *)ctx->dk_x.ptr; ldxtd = n;
-        JCH_TRY(jch_reserve(ctx, ctx->dk_q, sizeof(double) * (size_t)mb * p));
-        JCH_TRY(jch_reserve(ctx, ctx->dk_o, sizeof(double) * (size_t)mb * ncols));
-    }
-    JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * (size_t)mb * n));
-    double *Kb = (double *)ctx->dk_k.ptr;
-    for (int64_t r0 = 0; r0 < m; r0 += mb) {
-        const int64_t rows = std::min(mb, m - r0);
-        const double *Zb = X + r0;
-        int64_t ldz = ldx;
-        double *ob = out + r0;
-        int64_t ldob = ldo;
-        if (host) {
-            JCH_TRY(h2d(ctx, (double *)ctx->dk_q.ptr, rows, X + r0, ldx, rows, p));
-            Zb = (const double *)ctx->dk_q.ptr; ldz = rows;
-            ob = (double *)ctx->dk_o.ptr; ldob = rows;
-        }
-        JCH_TRY(jch_launch_kgram(ctx, kind, Zb, rows, ldz, xscale, dXt, n, ldxtd, nullptr, p, gamma, coef0, degree, false, Kb, rows));
+    int64_t mb = 0;
+    JCH_TRY(jch_kblocks_begin(ctx, who, loc, kind, degree, X && Xt && out, m, n, p, ldx, ldxt, ldo, jch_knob("JCH_DKPLSR_QBLOCK", 0), &mb));
+    if (mb == 0) return JCH_OK;
+    return jch_kblocks_run(ctx, loc, kind, gamma, coef0, degree, X, m, p, ldx, xscale, Xt, n, ldxt, mb, ncols, out, ldo,
+                           [&](double *Kb, int64_t rows, double *ob, int64_t ldob) {
         if (pred)
-            JCH_TRY(jch_predict(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, md.xmeans, md.xscales, md.ymeans, md.yscales, md.R, md.C, md.q, md.lo, md.hi, ob, ldob));
-        else
-            JCH_TRY(jch_transform(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, md.xmeans, md.xscales, md.R, md.nlv, ob, ldob));
-        if (host) JCH_TRY(d2h(ctx, out + r0, ldo, ob, ldob, rows, ncols));
-    }
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JCH_OK;
+            return jch_predict(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, md.xmeans, md.xscales, md.ymeans, md.yscales, md.R, md.C, md.q, md.lo, md.hi, ob, ldob);
+        return jch_transform(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, md.xmeans, md.xscales, md.R, md.nlv, ob, ldob);
+    });
 }
 
 }  // namespace
@@ -116,7 +38,7 @@ extern "C" int32_t jch_kernel_gram(jch_ctx *ctx, int32_t loc, int32_t kind, cons
 {
     static const char *who = "jch_kernel_gram";
     if (!ctx) return JCH_EINVAL;
-    JCH_TRY(check_kernel(ctx, who, kind, degree));
+    JCH_TRY(jch_check_kernel(ctx, who, kind, degree));
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "%s: bad loc %d", who, loc);
     if (!Z || !X || !K || m < 1 || n < 1 || p < 1 || ldz < m || ldx < n || ldk < m)
         return jch_fail(ctx, JCH_EINVAL, "%s: bad arguments (m=%lld n=%lld p=%lld ldz=%lld ldx=%lld ldk=%lld)", who, (long long)m, (long long)n,
@@ -130,20 +52,20 @@ extern "C" int32_t jch_kernel_gram(jch_ctx *ctx, int32_t loc, int32_t kind, cons
     int64_t ldkd = ldk;
     if (loc == JCH_LOC_HOST) {
         JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(h2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p));
+        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
         dX = (const double *)ctx->dk_x.ptr; ldxd = n;
         if (sym) {
             dZ = dX; ldzd = ldxd;
         } else {
             JCH_TRY(jch_reserve(ctx, ctx->dk_q, sizeof(double) * (size_t)m * p));
-            JCH_TRY(h2d(ctx, (double *)ctx->dk_q.ptr, m, Z, ldz, m, p));
+            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_q.ptr, m, Z, ldz, m, p, hipMemcpyHostToDevice));
             dZ = (const double *)ctx->dk_q.ptr; ldzd = m;
         }
         JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * (size_t)m * n));
         dK = (double *)ctx->dk_k.ptr; ldkd = m;
     }
     JCH_TRY(jch_launch_kgram(ctx, kind, dZ, m, ldzd, zscale, dX, n, ldxd, xscale, p, gamma, coef0, degree, sym, dK, ldkd));
-    if (loc == JCH_LOC_HOST) JCH_TRY(d2h(ctx, K, ldk, dK, ldkd, m, n));
+    if (loc == JCH_LOC_HOST) JCH_TRY(jch_copy2d(ctx, K, ldk, dK, ldkd, m, n, hipMemcpyDeviceToHost));
     JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return JCH_OK;
 }
@@ -157,7 +79,7 @@ extern "C" int32_t jch_dkplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_
     if (!ctx) return JCH_EINVAL;
     if (!desc) return jch_fail(ctx, JCH_EINVAL, "%s: desc is NULL", who);
     if (desc->dtype != JCH_F64) return jch_fail(ctx, JCH_EINVAL, "%s: Float64 only (dtype %d)", who, desc->dtype);
-    JCH_TRY(check_kernel(ctx, who, kind, degree));
+    JCH_TRY(jch_check_kernel(ctx, who, kind, degree));
     const jch_pls_desc &d = *desc;
     if (d.n < 1 || d.p < 1 || d.q < 1 || d.nlv < 1) return jch_fail(ctx, JCH_EINVAL, "%s: empty input or nlv < 1", who);
     if (d.n > (1 << 20) || d.q > (1 << 12)) return jch_fail(ctx, JCH_EINVAL, "%s: n=%lld or q=%lld too large", who, (long long)d.n, (long long)d.q);
@@ -174,13 +96,12 @@ extern "C" int32_t jch_dkplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_
     int64_t ldxd = ldx, ldyd = ldy;
     if (host) {
         JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(h2d(ctx, (double *)ctx->dk_x.ptr, n, (const double *)X, ldx, n, p));
+        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, (const double *)X, ldx, n, p, hipMemcpyHostToDevice));
         dX = (double *)ctx->dk_x.ptr; ldxd = n;
     }
     if (host || !inplace) {
         JCH_TRY(jch_reserve(ctx, ctx->dk_y, sizeof(double) * (size_t)n * q));
-        if (host) JCH_TRY(h2d(ctx, (double *)ctx->dk_y.ptr, n, (const double *)Y, ldy, n, q));
-        else JCH_HIP(ctx, hipMemcpy2DAsync(ctx->dk_y.ptr, sizeof(double) * n, Y, sizeof(double) * ldy, sizeof(double) * n, q, hipMemcpyDeviceToDevice, ctx->stream));
+        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_y.ptr, n, (const double *)Y, ldy, n, q, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
         dY = (double *)ctx->dk_y.ptr; ldyd = n;
     }
     // ---- outer scales (src/dkplsr.jl:112-119): the only use of the weights
@@ -196,8 +117,8 @@ extern "C" int32_t jch_dkplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_
         JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dY, n, q, ldyd, dw, mtmp.data(), ys.data()));
         JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
         JCH_HIP(ctx, hipMemcpyAsync(ys_dev, ys.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
-        JCH_TRY(divcols(ctx, dY, ldyd, n, q, ys_dev));
-        if (inplace) JCH_TRY(divcols(ctx, dX, ldxd, n, p, xs_dev));   // dkplsr! hands X back scaled; otherwise the Gram divides on the fly
+        JCH_TRY(jch_launch_divcols(ctx, dY, ldyd, n, q, ys_dev));
+        if (inplace) JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));   // dkplsr! hands X back scaled; otherwise the Gram divides on the fly
     }
     // ---- K = kern(X, X) (src/dkplsr.jl:121), the symmetric path
     double *Kd = K_out;
@@ -219,11 +140,11 @@ extern "C" int32_t jch_dkplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_
     int32_t got = 0;
     JCH_TRY(jch_plskern_fit(ctx, &di, Kd, n, dY, ldyd, nullptr, Tdev, P, R, W, C, TT, xmeans, xscales, ymeans, yscales, wn, &got));
     if (host) {
-        if (T) JCH_TRY(d2h(ctx, T, n, Tdev, n, n, got));
+        if (T) JCH_TRY(jch_copy2d(ctx, T, n, Tdev, n, n, got, hipMemcpyDeviceToHost));
         if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         if (inplace) {
-            JCH_TRY(d2h(ctx, (double *)X, ldx, dX, ldxd, n, p));
-            JCH_TRY(d2h(ctx, (double *)Y, ldy, dY, ldyd, n, q));
+            JCH_TRY(jch_copy2d(ctx, (double *)X, ldx, dX, ldxd, n, p, hipMemcpyDeviceToHost));
+            JCH_TRY(jch_copy2d(ctx, (double *)Y, ldy, dY, ldyd, n, q, hipMemcpyDeviceToHost));
         }
     }
     JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));

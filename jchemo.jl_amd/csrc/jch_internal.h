@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -117,6 +118,13 @@ struct jch_per_device_once {
     unsigned long long mask = 0;
     bool done(int dev) const { return (mask >> (dev & 63)) & 1ull; }
     void mark(int dev) { mask |= 1ull << (dev & 63); }
+};
+
+// Consecutive pieces of one workspace buffer, counted in doubles, each rounded up to 256 bytes: take() returns the offset of the next
+// piece; `off` is the doubles taken so far (what to reserve).
+struct jch_carve {
+    size_t off = 0;
+    size_t take(size_t count) { const size_t o = off; off += (count + 31) & ~(size_t)31; return o; }
 };
 
 // ---- error plumbing --------------------------------------------------------------------------------
@@ -292,6 +300,25 @@ int32_t jch_launch_kp_centred_gram(jch_ctx *ctx, int kind, double gamma, double 
 // kpca.hip: out (n x b, ld ldo) = Kc (diag(d) V) on the f64 matrix cores (d: device n-vector or null); any b, chunks of 64 columns
 int32_t jch_launch_kc_panel(jch_ctx *ctx, const double *Kc, int64_t n, int64_t ldk, const double *V, int64_t ldv, int b, const double *d,
                             double *out, int64_t ldo);
+// kmethod.hip: what the kernel-method entry points (dkplsr.hip, kplsr.hip, kpca.hip, krr.hip) share
+int32_t jch_check_kernel(jch_ctx *ctx, const char *who, int32_t kind, int32_t degree);   // kernel kind / degree, one rank only
+// column-major rows x cols matrix from src (ld lds) to dst (ld ldd) on ctx->stream
+int32_t jch_copy2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols, hipMemcpyKind kind);
+unsigned jch_grid1(const jch_ctx *ctx, int64_t work);   // workgroups of 256 threads of a grid-stride element-wise launch
+int32_t jch_launch_divcols(jch_ctx *ctx, double *A, int64_t lda, int64_t n, int64_t cols, const double *s_dev);   // A[:, k] /= s[k]
+int32_t jch_launch_sqrt(jch_ctx *ctx, const double *w, int64_t n, double *sw);                                    // sw = sqrt(w)
+// rows of new data per Gram block of a transform / predict over n training rows: knob (the caller's JCH_*_QBLOCK) when >= 1, else 1 GiB of Gram
+int64_t jch_qblock(int knob, int64_t n);
+// Transform / predict over m new rows X against the n training rows Xt, in blocks of at most qblock rows.  jch_kblocks_begin: the
+// argument checks (ptrs_ok: every pointer the entry point needs is set), then *mb = rows per block (0: m == 0, nothing to do).
+// jch_kblocks_run: per block, Kb (rows x n, ld rows, device) = kern(X_block / xscale, Xt), then step(Kb, rows, out_block, ld_out) fills the
+// block's rows x ncols of the output on the device; host data is staged in and out; ends with a stream sync.
+typedef std::function<int32_t(double *Kb, int64_t rows, double *out_block, int64_t ld_out)> jch_kblock_step;
+int32_t jch_kblocks_begin(jch_ctx *ctx, const char *who, int32_t loc, int32_t kind, int32_t degree, bool ptrs_ok, int64_t m, int64_t n, int64_t p,
+                          int64_t ldx, int64_t ldxt, int64_t ldo, int qblock_knob, int64_t *mb);
+int32_t jch_kblocks_run(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, double coef0, int32_t degree, const double *X, int64_t m, int64_t p,
+                        int64_t ldx, const double *xscale, const double *Xt, int64_t n, int64_t ldxt, int64_t mb, int64_t ncols, double *out,
+                        int64_t ldo, const jch_kblock_step &step);
 // chol.hip: blocked Cholesky of the lower triangle of A (n x n, ld lda, in place), everything on ctx->stream, no host sync.  info_dev: a device
 // int that ends up 0 or the 1-based index of the first pivot that is not > 0.  The solves and jch_launch_chol_inv_fro2 need the factor the
 // last jch_launch_chol_factor produced (its inv(L_kk) blocks live in ctx->chol_inv).

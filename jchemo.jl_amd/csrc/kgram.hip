@@ -7,7 +7,7 @@
 // are closer to the exact distances than its own, never further).
 //
 //   k_gram_colmean  c (krbf only)
-//   k_gram_copy     scaled, shifted, zero-padded column-major copies of Z and X (rows padded to 128, columns to KG_KB)
+//   k_gram_copy     scaled, shifted, zero-padded column-major copies of Z and X (rows padded to 128, columns to T128_KB)
 //   k_gram_norms    |z_i|^2, |x_j|^2 of those copies: O((m + n) p)
 //   k_gram          128 x 128 output tile per workgroup of 4 waves (64 x 64 per wave, 4 x 4 v_mfma_f64_16x16x4_f64 tiles);
 //                   a k-column of a tile is one contiguous 1 KB read of the copy; operands staged through LDS, double-buffered
@@ -24,13 +24,8 @@
 #include <algorithm>
 
 #include "jch_internal.h"
+#include "tile128_dev.h"
 
-typedef double v2f64 __attribute__((ext_vector_type(2)));
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-#define KG_T 128     // output tile edge
-#define KG_KB 16     // k-columns per staged chunk
-#define KG_LD 144    // LDS row stride (doubles): 128 + 16 (consecutive k-rows 32 banks apart, as k_syrk)
 #define KG_WLD 66    // LDS row stride of the transposing store (64 + 2)
 
 __global__ __launch_bounds__(256) void k_gram_colmean(const double *__restrict__ X, int64_t n, int64_t ldx, const double *__restrict__ xdiv,
@@ -80,68 +75,21 @@ __global__ __launch_bounds__(256, 2) void k_gram(const double *__restrict__ Zc, 
                                                  int kind, double gamma, double coef0, int degree, double *__restrict__ K, int64_t ldk)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    double *As = lds;                            // [2][KG_KB][KG_LD]  X tile (output rows j of the MFMA)
-    double *Bs = lds + 2 * KG_KB * KG_LD;        // [2][KG_KB][KG_LD]  Z tile (output columns i of the MFMA)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int64_t ti, tj;
-    if (SYM) {   // linear index -> (ti <= tj): tj (tj + 1) / 2 <= b < (tj + 1)(tj + 2) / 2
-        const int64_t b = blockIdx.x;
-        int64_t t = (int64_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-        while (t * (t + 1) / 2 > b) --t;
-        while ((t + 1) * (t + 2) / 2 <= b) ++t;
-        tj = t; ti = b - t * (t + 1) / 2;
+    if (SYM) {
+        t128_tri(blockIdx.x, ti, tj);   // ti <= tj
     } else {
         ti = blockIdx.x % tiles_i; tj = blockIdx.x / tiles_i;
     }
-    const int64_t i0 = ti * KG_T, j0 = tj * KG_T;
+    const int64_t i0 = ti * T128_T, j0 = tj * T128_T;
     const int qj = wv >> 1, qi = wv & 1;
-    v4f64 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = v4f64{0.0, 0.0, 0.0, 0.0};
-    v2f64 va[4], vb[4];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int64_t k = k0 + wv * 4 + it;
-            va[it] = __builtin_nontemporal_load(reinterpret_cast<const v2f64 *>(Xc + (size_t)k * (size_t)ldcx + (size_t)j0 + 2 * lane));
-            vb[it] = __builtin_nontemporal_load(reinterpret_cast<const v2f64 *>(Zc + (size_t)k * (size_t)ldcz + (size_t)i0 + 2 * lane));
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int row = wv * 4 + it;
-            *reinterpret_cast<v2f64 *>(As + (buf * KG_KB + row) * KG_LD + 2 * lane) = va[it];
-            *reinterpret_cast<v2f64 *>(Bs + (buf * KG_KB + row) * KG_LD + 2 * lane) = vb[it];
-        }
-    };
-    const int nch = pp / KG_KB;
-    load(0);
-    stage(0);
-    __syncthreads();
-    for (int ch = 0; ch < nch; ++ch) {
-        const int buf = ch & 1;
-        if (ch + 1 < nch) load((ch + 1) * KG_KB);
-        const double *A = As + buf * KG_KB * KG_LD, *B = Bs + buf * KG_KB * KG_LD;
-#pragma unroll
-        for (int kk = 0; kk < KG_KB / 4; ++kk) {
-            const int krow = 4 * kk + (lane >> 4);
-            double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[u] = A[krow * KG_LD + 64 * qj + 16 * u + (lane & 15)];
-                b[u] = B[krow * KG_LD + 64 * qi + 16 * u + (lane & 15)];
-            }
-#pragma unroll
-            for (int mj = 0; mj < 4; ++mj)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mj][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mj], b[ni], acc[mj][ni], 0, 0, 0);
-        }
-        if (ch + 1 < nch) stage(buf ^ 1);
-        __syncthreads();
-    }
+    t128_v4d acc[4][4];   // A = X tile (output rows j of the MFMA), B = Z tile (output columns i)
+    t128_mma(
+        lds, pp / T128_KB,
+        [&](int k, int c) { return __builtin_nontemporal_load(reinterpret_cast<const t128_v2d *>(Xc + (size_t)k * (size_t)ldcx + (size_t)j0 + c)); },
+        [&](int k, int c) { return __builtin_nontemporal_load(reinterpret_cast<const t128_v2d *>(Zc + (size_t)k * (size_t)ldcz + (size_t)i0 + c)); },
+        acc);
     // epilogue in registers: acc[mj][ni][reg] = dot(x_j, z_i), j = j0 + 64 qj + 16 mj + (lane >> 4) + 4 reg, i = i0 + 64 qi + 16 ni + (lane & 15)
     double zn[4];
 #pragma unroll
@@ -205,29 +153,23 @@ __global__ __launch_bounds__(256, 2) void k_gram(const double *__restrict__ Zc, 
     }
 }
 
-namespace {
-struct kg_carve {
-    char *base; size_t off;
-    double *take(size_t count) { double *p = (double *)(base + off); off += ((count * sizeof(double)) + 255) & ~(size_t)255; return p; }
-};
-}  // namespace
-
 int32_t jch_launch_kgram(jch_ctx *ctx, int kind, const double *Z, int64_t m, int64_t ldz, const double *zdiv, const double *X, int64_t n,
                          int64_t ldx, const double *xdiv, int64_t p, double gamma, double coef0, int degree, bool sym, double *K, int64_t ldk)
 {
     if (m < 1 || n < 1) return JCH_OK;
-    const int64_t pp = (p + KG_KB - 1) / KG_KB * KG_KB;
-    const int64_t tiles_i = (m + KG_T - 1) / KG_T, tiles_j = (n + KG_T - 1) / KG_T;
-    const int64_t ldcz = tiles_i * KG_T, ldcx = tiles_j * KG_T;
+    const int64_t pp = (p + T128_KB - 1) / T128_KB * T128_KB;
+    const int64_t tiles_i = (m + T128_T - 1) / T128_T, tiles_j = (n + T128_T - 1) / T128_T;
+    const int64_t ldcz = tiles_i * T128_T, ldcx = tiles_j * T128_T;
     const int64_t nblocks = sym ? tiles_j * (tiles_j + 1) / 2 : tiles_i * tiles_j;
     if (nblocks > 0x7fffffffLL || pp > 0x7fffffffLL) return jch_fail(ctx, JCH_EINVAL, "jch_kernel_gram: shape too large (m=%lld n=%lld p=%lld)", (long long)m, (long long)n, (long long)p);
     const bool rbf = kind == JCH_KERN_RBF;
     const size_t need = 256 * 8 + sizeof(double) * (3 * (size_t)pp + (size_t)ldcz + (size_t)ldcx + (size_t)ldcz * pp + (sym ? 0 : (size_t)ldcx * pp));
     JCH_TRY(jch_reserve(ctx, ctx->kg_ws, need));
-    kg_carve cv{(char *)ctx->kg_ws.ptr, 0};
-    double *c = cv.take(pp), *dz = cv.take(pp), *dx = cv.take(pp);
-    double *nzv = cv.take(ldcz), *nxv = sym ? nzv : cv.take(ldcx);
-    double *Zcp = cv.take((size_t)ldcz * pp), *Xcp = sym ? Zcp : cv.take((size_t)ldcx * pp);
+    jch_carve cv;
+    double *ws = (double *)ctx->kg_ws.ptr;
+    double *c = ws + cv.take(pp), *dz = ws + cv.take(pp), *dx = ws + cv.take(pp);
+    double *nzv = ws + cv.take(ldcz), *nxv = sym ? nzv : ws + cv.take(ldcx);
+    double *Zcp = ws + cv.take((size_t)ldcz * pp), *Xcp = sym ? Zcp : ws + cv.take((size_t)ldcx * pp);
     if (zdiv) JCH_HIP(ctx, hipMemcpyAsync(dz, zdiv, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
     if (xdiv) JCH_HIP(ctx, hipMemcpyAsync(dx, xdiv, sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
     if (rbf) hipLaunchKernelGGL(k_gram_colmean, dim3((unsigned)p), dim3(256), 0, ctx->stream, X, n, ldx, xdiv ? dx : nullptr, c);
@@ -239,7 +181,6 @@ int32_t jch_launch_kgram(jch_ctx *ctx, int kind, const double *Z, int64_t m, int
     copy(Z, m, ldz, zdiv ? dz : nullptr, Zcp, ldcz, nzv);
     if (!sym) copy(X, n, ldx, xdiv ? dx : nullptr, Xcp, ldcx, nxv);
     JCH_HIP(ctx, hipGetLastError());
-    const size_t ldsb = sizeof(double) * 4 * KG_KB * KG_LD;   // 73 728 B: two workgroups per CU
     static jch_per_device_once attr;
     if (!attr.done(ctx->device)) {
         JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_gram<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -247,10 +188,10 @@ int32_t jch_launch_kgram(jch_ctx *ctx, int kind, const double *Z, int64_t m, int
         attr.mark(ctx->device);
     }
     if (sym)
-        hipLaunchKernelGGL(k_gram<true>, dim3((unsigned)nblocks), dim3(256), ldsb, ctx->stream, Zcp, ldcz, Xcp, ldcx, (int)pp, nzv, nxv, m, n,
+        hipLaunchKernelGGL(k_gram<true>, dim3((unsigned)nblocks), dim3(256), T128_LDS_BYTES, ctx->stream, Zcp, ldcz, Xcp, ldcx, (int)pp, nzv, nxv, m, n,
                            (int)tiles_i, kind, gamma, coef0, degree, K, ldk);
     else
-        hipLaunchKernelGGL(k_gram<false>, dim3((unsigned)nblocks), dim3(256), ldsb, ctx->stream, Zcp, ldcz, Xcp, ldcx, (int)pp, nzv, nxv, m, n,
+        hipLaunchKernelGGL(k_gram<false>, dim3((unsigned)nblocks), dim3(256), T128_LDS_BYTES, ctx->stream, Zcp, ldcz, Xcp, ldcx, (int)pp, nzv, nxv, m, n,
                            (int)tiles_i, kind, gamma, coef0, degree, K, ldk);
     JCH_HIP(ctx, hipGetLastError());
     return JCH_OK;

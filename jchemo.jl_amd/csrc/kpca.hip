@@ -162,11 +162,6 @@ __global__ __launch_bounds__(PC_NT) void k_kc_vt(const double *__restrict__ V, i
 
 namespace {
 
-unsigned pc_grid(jch_ctx *ctx, int64_t work)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((work + PC_NT - 1) / PC_NT, (int64_t)ctx->cus * 16));
-}
-
 template <int NB>
 int32_t launch_panel_nb(jch_ctx *ctx, const double *K, int64_t n, int64_t ldk, const double *Vt, int bc, double *out, int64_t ldo, bool vec)
 {
@@ -193,7 +188,7 @@ int32_t jch_launch_kc_panel(jch_ctx *ctx, const double *Kc, int64_t n, int64_t l
     const bool vec = n >= 2 && (n % 2) == 0 && (ldk % 2) == 0 && ((uintptr_t)Kc % 16) == 0;
     for (int c0 = 0; c0 < b; c0 += 64) {
         const int bc = std::min(64, b - c0), NB = (bc + 15) / 16;
-        hipLaunchKernelGGL(k_kc_vt, dim3(pc_grid(ctx, jpad * 16 * NB)), dim3(PC_NT), 0, ctx->stream, V + (size_t)c0 * (size_t)ldv, ldv, n, bc, d, Vt,
+        hipLaunchKernelGGL(k_kc_vt, dim3(jch_grid1(ctx, jpad * 16 * NB)), dim3(PC_NT), 0, ctx->stream, V + (size_t)c0 * (size_t)ldv, ldv, n, bc, d, Vt,
                            16 * NB, jpad);
         JCH_HIP(ctx, hipGetLastError());
         double *oc = out + (size_t)c0 * (size_t)ldo;
@@ -445,19 +440,7 @@ __global__ __launch_bounds__(PC_NT) void k_pc_out(const double *X, const double 
     }
 }
 
-// sw = sqrt(w); X[:, k] /= xs[k] (`scale!` of src/utility.jl:1090-1100, in place); sstot = sum_i w_i Kc[i, i] (one workgroup)
-__global__ __launch_bounds__(PC_NT) void k_pc_sqrt(const double *__restrict__ w, int64_t n, double *__restrict__ sw)
-{
-    for (int64_t i = (int64_t)blockIdx.x * PC_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * PC_NT) sw[i] = sqrt(w[i]);
-}
-__global__ __launch_bounds__(PC_NT) void k_pc_divcols(double *X, int64_t ldx, int64_t n, int64_t p, const double *__restrict__ xs)
-{
-    const int64_t tot = n * p;
-    for (int64_t e = (int64_t)blockIdx.x * PC_NT + threadIdx.x; e < tot; e += (int64_t)gridDim.x * PC_NT) {
-        const int64_t k = e / n, i = e - k * n;
-        X[(size_t)i + (size_t)k * (size_t)ldx] /= xs[k];
-    }
-}
+// sstot = sum_i w_i Kc[i, i] (one workgroup)
 __global__ __launch_bounds__(PC_NT) void k_pc_trace(const double *__restrict__ Kc, int64_t n, const double *__restrict__ w, double *out)
 {
     __shared__ double scr[PC_NT / 64];
@@ -519,9 +502,7 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
 {
     static const char *who = "jch_kpca_fit";
     if (!ctx) return JCH_EINVAL;
-    if (kind != JCH_KERN_RBF && kind != JCH_KERN_POL) return jch_fail(ctx, JCH_EINVAL, "%s: unknown kernel kind %d", who, kind);
-    if (kind == JCH_KERN_POL && degree < 1) return jch_fail(ctx, JCH_EINVAL, "%s: degree = %d must be >= 1", who, degree);
-    if (ctx->nranks > 1) return jch_fail(ctx, JCH_EINVAL, "%s: the Gram matrix is not sharded: one rank only (communicator of %d)", who, ctx->nranks);
+    JCH_TRY(jch_check_kernel(ctx, who, kind, degree));
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "%s: bad loc %d", who, loc);
     if (!X || n < 1 || p < 1 || ldx < n) return jch_fail(ctx, JCH_EINVAL, "%s: bad X (n=%lld p=%lld ldx=%lld)", who, (long long)n, (long long)p, (long long)ldx);
     if (nlv < 1) return jch_fail(ctx, JCH_EINVAL, "%s: nlv = %d must be >= 1", who, nlv);
@@ -538,7 +519,7 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
     int64_t ldxd = ldx;
     if (host) {
         JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * nn * p));
-        JCH_HIP(ctx, hipMemcpy2DAsync(ctx->dk_x.ptr, sizeof(double) * nn, X, sizeof(double) * ldx, sizeof(double) * nn, p, hipMemcpyHostToDevice, ctx->stream));
+        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
         dX = (double *)ctx->dk_x.ptr; ldxd = n;
     }
     // ---- workspace (doubles, ld n): Q | W | Z | X | WS | reservoir (n x b each), vectors, partials and the small state
@@ -547,14 +528,13 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
     st.nrb = (int)std::max<int64_t>(1, std::min<int64_t>(PC_RED_NB, (n + 255) / 256));
     st.chunk = (n + st.nrb - 1) / st.nrb;
     const int64_t rblk = (n + PC_NT - 1) / PC_NT;
-    size_t off = 0;
-    auto take = [&](size_t cnt) { const size_t o = off; off += (cnt + 31) & ~(size_t)31; return o; };
+    jch_carve cv;
     const size_t nb = nn * b;
-    const size_t oQ = take(nb), oW = take(nb), oZ = take(nb), oX = take(nb), oWS = take(nb), oR = take(nb), ow = take(nn), osw = take(nn),
-                 ovt = take(nn), ohdr = take(8), os = take(8), oxs = take((size_t)p), opart = take((size_t)st.nrb * b * b),
-                 ogws = take(b > PC_LDS_B ? pc_eig_doubles(b) : 0), oS = take((size_t)b * b), oth = take(b), oM = take((size_t)b * b),
-                 orf = take(b), orp = take((size_t)rblk * b), osg = take(A), otr = take(8);
-    JCH_TRY(jch_reserve(ctx, ctx->pc_ws, sizeof(double) * off));
+    const size_t oQ = cv.take(nb), oW = cv.take(nb), oZ = cv.take(nb), oX = cv.take(nb), oWS = cv.take(nb), oR = cv.take(nb), ow = cv.take(nn), osw = cv.take(nn),
+                 ovt = cv.take(nn), ohdr = cv.take(8), os = cv.take(8), oxs = cv.take((size_t)p), opart = cv.take((size_t)st.nrb * b * b),
+                 ogws = cv.take(b > PC_LDS_B ? pc_eig_doubles(b) : 0), oS = cv.take((size_t)b * b), oth = cv.take(b), oM = cv.take((size_t)b * b),
+                 orf = cv.take(b), orp = cv.take((size_t)rblk * b), osg = cv.take(A), otr = cv.take(8);
+    JCH_TRY(jch_reserve(ctx, ctx->pc_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->pc_ws.ptr;
     double *Qd = ws + oQ, *Wd = ws + oW, *Zd = ws + oZ, *Xd = ws + oX, *WSd = ws + oWS, *wn = ws + ow, *sw = ws + osw, *vt = ws + ovt,
            *hdr = ws + ohdr, *sdev = ws + os, *xs_dev = ws + oxs, *rpart = ws + orp, *sg = ws + osg, *trd = ws + otr;
@@ -572,16 +552,14 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
         dw = Wd;
     }
     JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/kpca.jl:93)
-    hipLaunchKernelGGL(k_pc_sqrt, dim3(pc_grid(ctx, n)), dim3(PC_NT), 0, ctx->stream, wn, n, sw);
-    JCH_HIP(ctx, hipGetLastError());
+    JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
     // ---- scal: xscales = colstd(X, w), X divided by them in place (:94-98)
     std::vector<double> xs((size_t)p, 1.0), xm((size_t)p);
     if (scal) {
         JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, xm.data(), xs.data()));
         JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_pc_divcols, dim3(pc_grid(ctx, n * p)), dim3(PC_NT), 0, ctx->stream, dX, ldxd, n, p, xs_dev);
-        JCH_HIP(ctx, hipGetLastError());
-        if (host) JCH_HIP(ctx, hipMemcpy2DAsync(X, sizeof(double) * ldx, dX, sizeof(double) * nn, sizeof(double) * nn, p, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));
+        if (host) JCH_TRY(jch_copy2d(ctx, X, ldx, dX, n, n, p, hipMemcpyDeviceToHost));
     }
     // ---- K = kern(X, X), vtot = K w, Kc = K - vtot' - vtot + w'vtot (:99-103)
     JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * nn * nn));
@@ -621,7 +599,7 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
     hipLaunchKernelGGL(k_pc_sign, dim3((unsigned)A), dim3(PC_NT), 0, ctx->stream, Xd, n, sg);
     JCH_HIP(ctx, hipGetLastError());
     double *Pd = Qd;
-    hipLaunchKernelGGL(k_pc_out, dim3(pc_grid(ctx, n * A)), dim3(PC_NT), 0, ctx->stream, Xd, WSd, n, A, sg, st.theta, sw, Xd, Pd, WSd);
+    hipLaunchKernelGGL(k_pc_out, dim3(jch_grid1(ctx, n * A)), dim3(PC_NT), 0, ctx->stream, Xd, WSd, n, A, sg, st.theta, sw, Xd, Pd, WSd);
     JCH_HIP(ctx, hipGetLastError());
     const bool psd = psd_kernel(kind, gamma, coef0, degree);
     if (psd) {

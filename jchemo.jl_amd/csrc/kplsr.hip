@@ -305,19 +305,6 @@ __global__ __launch_bounds__(KP_NT) void k_kp_rows(const double *__restrict__ M,
 
 namespace {
 
-int32_t check_kernel(jch_ctx *ctx, const char *who, int32_t kind, int32_t degree)
-{
-    if (kind != JCH_KERN_RBF && kind != JCH_KERN_POL) return jch_fail(ctx, JCH_EINVAL, "%s: unknown kernel kind %d", who, kind);
-    if (kind == JCH_KERN_POL && degree < 1) return jch_fail(ctx, JCH_EINVAL, "%s: degree = %d must be >= 1", who, degree);
-    if (ctx->nranks > 1) return jch_fail(ctx, JCH_EINVAL, "%s: the Gram matrix is not sharded: one rank only (communicator of %d)", who, ctx->nranks);
-    return JCH_OK;
-}
-
-unsigned grid1(jch_ctx *ctx, int64_t work)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((work + KP_NT - 1) / KP_NT, (int64_t)ctx->cus * 16));
-}
-
 template <int R>
 int32_t launch_pass_r(jch_ctx *ctx, const double *K, int64_t n, const double *V, int64_t ldv, int rr, double *out, int64_t ldo)
 {
@@ -371,7 +358,7 @@ int32_t launch_red(jch_ctx *ctx, const double *A, int64_t lda, int ka, const dou
 int32_t launch_apply(jch_ctx *ctx, double *out, int64_t ldo, const double *A, int64_t lda, const double *T, int64_t ldt, int ka,
                      const double *coef, const double *d, int64_t n, int q)
 {
-    hipLaunchKernelGGL(k_kp_apply, dim3(grid1(ctx, n * q)), dim3(KP_NT), 0, ctx->stream, out, ldo, A, lda, T, ldt, ka, coef, d, n, q);
+    hipLaunchKernelGGL(k_kp_apply, dim3(jch_grid1(ctx, n * q)), dim3(KP_NT), 0, ctx->stream, out, ldo, A, lda, T, ldt, ka, coef, d, n, q);
     JCH_HIP(ctx, hipGetLastError());
     return JCH_OK;
 }
@@ -386,30 +373,6 @@ int32_t launch_center(jch_ctx *ctx, const double *K, int64_t ldk, double *Kc, in
     return JCH_OK;
 }
 
-int32_t h2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols)
-{
-    JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * ldd, src, sizeof(double) * lds, sizeof(double) * rows, cols, hipMemcpyHostToDevice, ctx->stream));
-    return JCH_OK;
-}
-int32_t d2h(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols)
-{
-    JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * ldd, src, sizeof(double) * lds, sizeof(double) * rows, cols, hipMemcpyDeviceToHost, ctx->stream));
-    return JCH_OK;
-}
-int32_t d2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols)
-{
-    JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * ldd, src, sizeof(double) * lds, sizeof(double) * rows, cols, hipMemcpyDeviceToDevice, ctx->stream));
-    return JCH_OK;
-}
-
-// rows of new data per Gram block: JCH_KPLSR_QBLOCK, else 1 GiB of Gram (2^27 doubles)
-int64_t qblock(int64_t n)
-{
-    const int v = jch_knob("JCH_KPLSR_QBLOCK", 0);
-    if (v >= 1) return v;
-    return std::max<int64_t>(1, ((int64_t)1 << 27) / n);
-}
-
 struct kp_model {
     const double *weights, *vtot, *ymeans, *yscales, *R, *C;
     int64_t q; int32_t lo, hi, nlv;
@@ -421,65 +384,34 @@ int32_t kp_apply(jch_ctx *ctx, const char *who, int32_t loc, int32_t kind, doubl
                  int64_t p, int64_t ldx, const double *xscales, const double *Xt, int64_t n, int64_t ldxt, const kp_model &md, bool pred,
                  int64_t ncols, double *out, int64_t ldo)
 {
-    if (!ctx) return JCH_EINVAL;
-    JCH_TRY(check_kernel(ctx, who, kind, degree));
-    if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "%s: bad loc %d", who, loc);
-    if (!X || !Xt || !out || !md.weights || !md.vtot || m < 0 || n < 1 || p < 1 || ldx < m || ldxt < n || ldo < m)
-        return jch_fail(ctx, JCH_EINVAL, "%s: bad arguments (m=%lld n=%lld p=%lld ldx=%lld ldxt=%lld ldo=%lld)", who, (long long)m, (long long)n,
-                        (long long)p, (long long)ldx, (long long)ldxt, (long long)ldo);
-    if (m == 0) return JCH_OK;
-    JCH_HIP(ctx, hipSetDevice(ctx->device));
-    const bool host = loc == JCH_LOC_HOST;
-    const int64_t mb = std::min<int64_t>(m, qblock(n));
+    int64_t mb = 0;
+    JCH_TRY(jch_kblocks_begin(ctx, who, loc, kind, degree, X && Xt && out && md.weights && md.vtot, m, n, p, ldx, ldxt, ldo,
+                              jch_knob("JCH_KPLSR_QBLOCK", 0), &mb));
+    if (mb == 0) return JCH_OK;
     double s = 0.0;   // sum(D * DKt') = w' K w = weights . vtot
     for (int64_t j = 0; j < n; ++j) s += md.weights[j] * md.vtot[j];
     JCH_TRY(jch_reserve(ctx, ctx->dk_s, sizeof(double) * (size_t)(n + mb)));
     double *vt_dev = (double *)ctx->dk_s.ptr, *vnew = vt_dev + n;
     JCH_HIP(ctx, hipMemcpyAsync(vt_dev, md.vtot, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    const double *dXt = Xt;
-    int64_t ldxtd = ldxt;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(h2d(ctx, (double *)ctx->dk_x.ptr, n, Xt, ldxt, n, p));
-        dXt = (const double *)ctx->dk_x.ptr; ldxtd = n;
-        JCH_TRY(jch_reserve(ctx, ctx->dk_q, sizeof(double) * (size_t)mb * p));
-        JCH_TRY(jch_reserve(ctx, ctx->dk_o, sizeof(double) * (size_t)mb * ncols));
-    }
-    JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * (size_t)mb * n));
-    double *Kb = (double *)ctx->dk_k.ptr;
-    for (int64_t r0 = 0; r0 < m; r0 += mb) {
-        const int64_t rows = std::min(mb, m - r0);
-        const double *Zb = X + r0;
-        int64_t ldz = ldx;
-        double *ob = out + r0;
-        int64_t ldob = ldo;
-        if (host) {
-            JCH_TRY(h2d(ctx, (double *)ctx->dk_q.ptr, rows, X + r0, ldx, rows, p));
-            Zb = (const double *)ctx->dk_q.ptr; ldz = rows;
-            ob = (double *)ctx->dk_o.ptr; ldob = rows;
-        }
-        JCH_TRY(jch_launch_kgram(ctx, kind, Zb, rows, ldz, xscales, dXt, n, ldxtd, nullptr, p, gamma, coef0, degree, false, Kb, rows));
+    return jch_kblocks_run(ctx, loc, kind, gamma, coef0, degree, X, m, p, ldx, xscales, Xt, n, ldxt, mb, ncols, out, ldo,
+                           [&](double *Kb, int64_t rows, double *ob, int64_t ldob) {
         JCH_TRY(jch_transform(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, nullptr, nullptr, md.weights, 1, vnew, rows));
         JCH_TRY(launch_center(ctx, Kb, rows, Kb, rows, rows, n, vnew, vt_dev, nullptr, s));
         if (pred)
-            JCH_TRY(jch_predict(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, nullptr, nullptr, md.ymeans, md.yscales, md.R, md.C, md.q, md.lo, md.hi, ob, ldob));
-        else
-            JCH_TRY(jch_transform(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, nullptr, nullptr, md.R, md.nlv, ob, ldob));
-        if (host) JCH_TRY(d2h(ctx, out + r0, ldo, ob, ldob, rows, ncols));
-    }
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JCH_OK;
+            return jch_predict(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, nullptr, nullptr, md.ymeans, md.yscales, md.R, md.C, md.q, md.lo, md.hi, ob, ldob);
+        return jch_transform(ctx, JCH_LOC_DEVICE, Kb, rows, n, rows, nullptr, nullptr, md.R, md.nlv, ob, ldob);
+    });
 }
 
 }  // namespace
 
 // K = kern(X, X) (symmetric path) into Kraw, vtot = K w, s = w'vtot and Kc = K - vtot 1' - 1 vtot' + s into Kc (Kc == Kraw allowed):
-// the same launches as jch_kplsr_fit below, for kpca.hip
+// for jch_kplsr_fit below, kpca.hip and krr.hip
 int32_t jch_launch_kp_centred_gram(jch_ctx *ctx, int kind, double gamma, double coef0, int degree, const double *X, int64_t n, int64_t ldx,
                                    const double *xdiv, int64_t p, const double *wn, double *Kraw, double *Kc, double *vt, double *sdev)
 {
     JCH_TRY(jch_launch_kgram(ctx, kind, X, n, ldx, xdiv, X, n, ldx, xdiv, p, gamma, coef0, degree, true, Kraw, n));
-    JCH_TRY(launch_pass(ctx, Kraw, n, wn, n, 1, vt, n));
+    JCH_TRY(launch_pass(ctx, Kraw, n, wn, n, 1, vt, n));   // vtot = K w (columns of the symmetric K against w)
     hipLaunchKernelGGL(k_kp_wdot, dim3(1), dim3(KP_NT), 0, ctx->stream, wn, vt, n, sdev);
     JCH_HIP(ctx, hipGetLastError());
     return launch_center(ctx, Kraw, n, Kc, n, n, n, vt, vt, sdev, 0.0);
@@ -494,7 +426,7 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
     if (!ctx) return JCH_EINVAL;
     if (!desc) return jch_fail(ctx, JCH_EINVAL, "%s: desc is NULL", who);
     if (desc->dtype != JCH_F64) return jch_fail(ctx, JCH_EINVAL, "%s: Float64 only (dtype %d)", who, desc->dtype);
-    JCH_TRY(check_kernel(ctx, who, kind, degree));
+    JCH_TRY(jch_check_kernel(ctx, who, kind, degree));
     const jch_pls_desc &d = *desc;
     if (d.n < 1 || d.p < 1 || d.q < 1 || d.nlv < 1) return jch_fail(ctx, JCH_EINVAL, "%s: empty input or nlv < 1", who);
     if (maxit < 1) return jch_fail(ctx, JCH_EINVAL, "%s: maxit = %d must be >= 1", who, maxit);
@@ -514,7 +446,7 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
     const double *dw = weights;
     if (host) {
         JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(h2d(ctx, (double *)ctx->dk_x.ptr, n, (const double *)X, ldx, n, p));
+        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, (const double *)X, ldx, n, p, hipMemcpyHostToDevice));
         dX = (double *)ctx->dk_x.ptr; ldxd = n;
     }
     // ---- workspace (doubles, ld n): Ya | Wb (adjacent: one reduction gives Y_a'DM and M'DM) | Vb | T | U | DU, then the vectors and
@@ -522,14 +454,13 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
     const int pc = kp_padcols(std::max<int>((int)q, A));
     const int ldp = (int)std::max<int64_t>({(int64_t)A * q, 2 * q * q, (int64_t)A + 1});
     const size_t nn = (size_t)n;
-    size_t off = 0;
-    auto take = [&](size_t cnt) { const size_t o = off; off += (cnt + 31) & ~(size_t)31; return o; };
-    const size_t oY = take(nn * (q + pc)), oV = take(nn * pc), oT = take(nn * A), oU = take(nn * A), oDU = take(nn * A);
-    const size_t ow = take(nn), ovt = take(nn), ohdr = take(8), os = take(8), oms = take(2 * q + (size_t)p), oS = take((size_t)A * A),
-                 ocoef = take((size_t)A * q), ost = take(3 * (size_t)q + 1), omat = take(3 * (size_t)q * q), oC = take((size_t)A * q),
-                 oit = take(A), op1 = take((size_t)KP_RED_NB * ldp), op2 = take((size_t)KP_RED_NB * ldp), op3 = take((size_t)KP_RED_NB * ldp),
-                 op4 = take((size_t)KP_RED_NB * ldp), op5 = take((size_t)KP_RED_NB * ldp);
-    JCH_TRY(jch_reserve(ctx, ctx->kp_ws, sizeof(double) * off));
+    jch_carve cv;
+    const size_t oY = cv.take(nn * (q + pc)), oV = cv.take(nn * pc), oT = cv.take(nn * A), oU = cv.take(nn * A), oDU = cv.take(nn * A);
+    const size_t ow = cv.take(nn), ovt = cv.take(nn), ohdr = cv.take(8), os = cv.take(8), oms = cv.take(2 * q + (size_t)p), oS = cv.take((size_t)A * A),
+                 ocoef = cv.take((size_t)A * q), ost = cv.take(3 * (size_t)q + 1), omat = cv.take(3 * (size_t)q * q), oC = cv.take((size_t)A * q),
+                 oit = cv.take(A), op1 = cv.take((size_t)KP_RED_NB * ldp), op2 = cv.take((size_t)KP_RED_NB * ldp), op3 = cv.take((size_t)KP_RED_NB * ldp),
+                 op4 = cv.take((size_t)KP_RED_NB * ldp), op5 = cv.take((size_t)KP_RED_NB * ldp);
+    JCH_TRY(jch_reserve(ctx, ctx->kp_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kp_ws.ptr;
     double *Ya = ws + oY, *Wb = ws + oY + nn * q, *Vb = ws + oV, *Td = ws + oT, *Ud = ws + oU, *DU = ws + oDU, *wn = ws + ow, *vt = ws + ovt,
            *hdr = ws + ohdr, *sdev = ws + os, *ms = ws + oms, *Sd = ws + oS, *coef = ws + ocoef, *st = ws + ost, *mat = ws + omat,
@@ -540,7 +471,7 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
     }
     JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/kplsr.jl:124)
     // ---- Y: ymeans = colmean(Y, w); with scal, xscales = colstd(X, w), yscales = colstd(Y, w) (:125-135)
-    if (host) JCH_TRY(h2d(ctx, Ya, n, (const double *)Y, ldy, n, q));
+    if (host) JCH_TRY(jch_copy2d(ctx, Ya, n, (const double *)Y, ldy, n, q, hipMemcpyHostToDevice));
     const double *ysrc = host ? Ya : (const double *)Y;
     const int64_t ldys = host ? n : ldy;
     std::vector<double> xs((size_t)p, 1.0), ym((size_t)q), ys((size_t)q, 1.0), xm((size_t)p);
@@ -550,10 +481,10 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
     JCH_HIP(ctx, hipMemcpyAsync(ym_dev, ym.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
     JCH_HIP(ctx, hipMemcpyAsync(ys_dev, ys.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
     JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_kp_cscale, dim3(grid1(ctx, n * q)), dim3(KP_NT), 0, ctx->stream, ysrc, ldys, Ya, n, n, q, ym_dev, ys_dev);
+    hipLaunchKernelGGL(k_kp_cscale, dim3(jch_grid1(ctx, n * q)), dim3(KP_NT), 0, ctx->stream, ysrc, ldys, Ya, n, n, q, ym_dev, ys_dev);
     JCH_HIP(ctx, hipGetLastError());
     if (scal && inplace) {   // kplsr! hands X back divided by xscales (`scale!`, :131); otherwise the Gram divides on the fly
-        hipLaunchKernelGGL(k_kp_cscale, dim3(grid1(ctx, n * p)), dim3(KP_NT), 0, ctx->stream, dX, ldxd, dX, ldxd, n, p, nullptr, xs_dev);
+        hipLaunchKernelGGL(k_kp_cscale, dim3(jch_grid1(ctx, n * p)), dim3(KP_NT), 0, ctx->stream, dX, ldxd, dX, ldxd, n, p, nullptr, xs_dev);
         JCH_HIP(ctx, hipGetLastError());
     }
     // ---- K = kern(X, X) (:137), symmetric path; Kc = K - vtot 1' - 1 vtot' + w'Kw (:138-142) formed in the workspace Gram
@@ -561,10 +492,7 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
     double *Kc = (double *)ctx->dk_k.ptr;
     double *Kraw = K_out ? K_out : Kc;
     const double *gdiv = scal && !inplace ? xs.data() : nullptr;
-    JCH_TRY(jch_launch_kgram(ctx, kind, dX, n, ldxd, gdiv, dX, n, ldxd, gdiv, p, gamma, coef0, degree, true, Kraw, n));
-    JCH_TRY(launch_pass(ctx, Kraw, n, wn, n, 1, vt, n));   // vtot = K w (columns of the symmetric K against w)
-    hipLaunchKernelGGL(k_kp_wdot, dim3(1), dim3(KP_NT), 0, ctx->stream, wn, vt, n, sdev);
-    JCH_TRY(launch_center(ctx, Kraw, n, Kc, n, n, n, vt, vt, sdev, 0.0));
+    JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, gdiv, p, wn, Kraw, Kc, vt, sdev));
     // ---- LV loop (:157-188): one pass over Kc per LV
     const int nbr = (int)std::max<int64_t>(1, std::min<int64_t>(KP_RED_NB, (n + 255) / 256));
     for (int a = 0; a < A; ++a) {
@@ -588,7 +516,7 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
         kp_iter_args gi{part3, part4, mat, st, Cd, itd, a, (int)q, nbr, ldp, ldp, maxit, tol};
         hipLaunchKernelGGL(k_kp_iter, dim3(1), dim3(KP_NT), 0, ctx->stream, gi);
         JCH_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_kp_rows, dim3(grid1(ctx, n)), dim3(KP_NT), 0, ctx->stream, Wb, Ya, n, (int)q, st, Td + nn * a, Ud + nn * a);
+        hipLaunchKernelGGL(k_kp_rows, dim3(jch_grid1(ctx, n)), dim3(KP_NT), 0, ctx->stream, Wb, Ya, n, (int)q, st, Td + nn * a, Ud + nn * a);
         JCH_HIP(ctx, hipGetLastError());
         if (a + 1 < A) JCH_TRY(launch_red(ctx, Td, n, a + 1, Td + nn * a, n, 1, wn, n, nbr, part5, ldp));   // S row a = t_a' D T
     }
@@ -601,23 +529,15 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
     sm.P = Wb; sm.W = DU; sm.R = Rd;
     JCH_TRY(jch_launch_nipals_R(ctx, sm, (int)n, A));
     // ---- outputs
-    if (host) {
-        if (T) JCH_TRY(d2h(ctx, T, n, Td, n, n, A));
-        if (U) JCH_TRY(d2h(ctx, U, n, Ud, n, n, A));
-        if (R) JCH_TRY(d2h(ctx, R, n, Rd, n, n, A));
-        if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
-        if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
-        if (inplace) {
-            JCH_TRY(d2h(ctx, (double *)X, ldx, dX, ldxd, n, p));
-            JCH_TRY(d2h(ctx, (double *)Y, ldy, Ya, n, n, q));
-        }
-    } else {
-        if (T) JCH_TRY(d2d(ctx, T, n, Td, n, n, A));
-        if (U) JCH_TRY(d2d(ctx, U, n, Ud, n, n, A));
-        if (R) JCH_TRY(d2d(ctx, R, n, Rd, n, n, A));
-        if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, hipMemcpyDeviceToDevice, ctx->stream));
-        if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, hipMemcpyDeviceToDevice, ctx->stream));
-        if (inplace) JCH_TRY(d2d(ctx, (double *)Y, ldy, Ya, n, n, q));
+    const hipMemcpyKind dir = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (T) JCH_TRY(jch_copy2d(ctx, T, n, Td, n, n, A, dir));
+    if (U) JCH_TRY(jch_copy2d(ctx, U, n, Ud, n, n, A, dir));
+    if (R) JCH_TRY(jch_copy2d(ctx, R, n, Rd, n, n, A, dir));
+    if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, dir, ctx->stream));
+    if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, dir, ctx->stream));
+    if (inplace) {   // kplsr! hands X (scaled; already in place on the device) and Y (centred, scaled) back
+        if (host) JCH_TRY(jch_copy2d(ctx, (double *)X, ldx, dX, ldxd, n, p, dir));
+        JCH_TRY(jch_copy2d(ctx, (double *)Y, ldy, Ya, n, n, q, dir));
     }
     std::vector<double> Ch((size_t)A * q), ith((size_t)A);
     JCH_HIP(ctx, hipMemcpyAsync(Ch.data(), Cd, sizeof(double) * Ch.size(), hipMemcpyDeviceToHost, ctx->stream));

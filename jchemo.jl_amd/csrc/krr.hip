@@ -15,11 +15,6 @@
 
 #define KR_NT 256
 
-// sw = sqrt(w)
-__global__ __launch_bounds__(KR_NT) void k_kr_sqrt(const double *__restrict__ w, int64_t n, double *__restrict__ sw)
-{
-    for (int64_t i = (int64_t)blockIdx.x * KR_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * KR_NT) sw[i] = sqrt(w[i]);
-}
 // out[i, j] = r_i in[i, j] c_j (c = null: 1); out may be in (element-wise)
 __global__ __launch_bounds__(KR_NT) void k_kr_scale(const double *in, int64_t ldi, double *out, int64_t ldo, int64_t n, int64_t m,
                                                     const double *__restrict__ r, const double *__restrict__ c)
@@ -31,26 +26,11 @@ __global__ __launch_bounds__(KR_NT) void k_kr_scale(const double *in, int64_t ld
         out[(size_t)i + (size_t)j * (size_t)ldo] = c ? v * c[j] : v;
     }
 }
-__global__ __launch_bounds__(KR_NT) void k_kr_divcols(double *X, int64_t ldx, int64_t n, int64_t p, const double *__restrict__ xs)
-{
-    const int64_t tot = n * p;
-    for (int64_t e = (int64_t)blockIdx.x * KR_NT + threadIdx.x; e < tot; e += (int64_t)gridDim.x * KR_NT) {
-        const int64_t k = e / n, i = e - k * n;
-        X[(size_t)i + (size_t)k * (size_t)ldx] /= xs[k];
-    }
-}
 __global__ __launch_bounds__(KR_NT) void k_kr_adddiag(double *A, int64_t n, double v)
 {
     const int64_t i = (int64_t)blockIdx.x * KR_NT + threadIdx.x;
     if (i < n) A[(size_t)i * (size_t)(n + 1)] += v;
 }
-
-namespace {
-unsigned kr_grid(jch_ctx *ctx, int64_t work)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((work + KR_NT - 1) / KR_NT, (int64_t)ctx->cus * 16));
-}
-}  // namespace
 
 extern "C" int32_t jch_krr_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, double coef0, int32_t degree, double *X, int64_t n, int64_t p,
                                int64_t ldx, const double *Y, int64_t q, int64_t ldy, const double *weights, int32_t scal, double *Kd, double *K_out,
@@ -58,9 +38,7 @@ extern "C" int32_t jch_krr_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double g
 {
     static const char *who = "jch_krr_fit";
     if (!ctx) return JCH_EINVAL;
-    if (kind != JCH_KERN_RBF && kind != JCH_KERN_POL) return jch_fail(ctx, JCH_EINVAL, "%s: unknown kernel kind %d", who, kind);
-    if (kind == JCH_KERN_POL && degree < 1) return jch_fail(ctx, JCH_EINVAL, "%s: degree = %d must be >= 1", who, degree);
-    if (ctx->nranks > 1) return jch_fail(ctx, JCH_EINVAL, "%s: the Gram matrix is not sharded: one rank only (communicator of %d)", who, ctx->nranks);
+    JCH_TRY(jch_check_kernel(ctx, who, kind, degree));
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "%s: bad loc %d", who, loc);
     if (!X || n < 1 || p < 1 || ldx < n) return jch_fail(ctx, JCH_EINVAL, "%s: bad X (n=%lld p=%lld ldx=%lld)", who, (long long)n, (long long)p, (long long)ldx);
     if (!Y || q < 1 || ldy < n) return jch_fail(ctx, JCH_EINVAL, "%s: bad Y (q=%lld ldy=%lld)", who, (long long)q, (long long)ldy);
@@ -74,21 +52,20 @@ extern "C" int32_t jch_krr_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double g
     int64_t ldxd = ldx;
     if (host) {
         JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * nn * p));
-        JCH_HIP(ctx, hipMemcpy2DAsync(ctx->dk_x.ptr, sizeof(double) * nn, X, sizeof(double) * ldx, sizeof(double) * nn, p, hipMemcpyHostToDevice, ctx->stream));
+        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
         dX = (double *)ctx->dk_x.ptr; ldxd = n;
     }
-    size_t off = 0;
-    auto take = [&](size_t cnt) { const size_t o = off; off += (cnt + 31) & ~(size_t)31; return o; };
-    const size_t oY = take(nn * q), oB = take(nn * q), owr = take(nn), ow = take(nn), osw = take(nn), ovt = take(nn), ohdr = take(8), os = take(8),
-                 oxs = take((size_t)p);
-    JCH_TRY(jch_reserve(ctx, ctx->kr_ws, sizeof(double) * off));
+    jch_carve cv;
+    const size_t oY = cv.take(nn * q), oB = cv.take(nn * q), owr = cv.take(nn), ow = cv.take(nn), osw = cv.take(nn), ovt = cv.take(nn), ohdr = cv.take(8), os = cv.take(8),
+                 oxs = cv.take((size_t)p);
+    JCH_TRY(jch_reserve(ctx, ctx->kr_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kr_ws.ptr;
     double *Yd = ws + oY, *Bd = ws + oB, *wraw = ws + owr, *wn = ws + ow, *sw = ws + osw, *vt = ws + ovt, *hdr = ws + ohdr, *sdev = ws + os,
            *xs_dev = ws + oxs;
     const double *dY = Y;
     int64_t ldyd = ldy;
     if (host) {
-        JCH_HIP(ctx, hipMemcpy2DAsync(Yd, sizeof(double) * nn, Y, sizeof(double) * ldy, sizeof(double) * nn, q, hipMemcpyHostToDevice, ctx->stream));
+        JCH_TRY(jch_copy2d(ctx, Yd, n, Y, ldy, n, q, hipMemcpyHostToDevice));
         dY = Yd; ldyd = n;
     }
     const double *dw = weights;
@@ -97,24 +74,22 @@ extern "C" int32_t jch_krr_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double g
         dw = wraw;
     }
     JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/krr.jl:135)
-    hipLaunchKernelGGL(k_kr_sqrt, dim3(kr_grid(ctx, n)), dim3(KR_NT), 0, ctx->stream, wn, n, sw);
-    JCH_HIP(ctx, hipGetLastError());
+    JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
     // ---- scal: xscales = colstd(X, w), X divided by them in place (:136-140; X is not centred); ymeans = colmean(Y, w) (:141)
     std::vector<double> xs((size_t)p, 1.0), xm((size_t)p), ym((size_t)q);
     if (scal) {
         JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, xm.data(), xs.data()));
         JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_kr_divcols, dim3(kr_grid(ctx, n * p)), dim3(KR_NT), 0, ctx->stream, dX, ldxd, n, p, xs_dev);
-        JCH_HIP(ctx, hipGetLastError());
-        if (host) JCH_HIP(ctx, hipMemcpy2DAsync(X, sizeof(double) * ldx, dX, sizeof(double) * nn, sizeof(double) * nn, p, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));
+        if (host) JCH_TRY(jch_copy2d(ctx, X, ldx, dX, n, n, p, hipMemcpyDeviceToHost));
     }
     JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dY, n, q, ldyd, dw, ym.data(), nullptr));
     // ---- K = kern(X, X), vtot = K w, Kc = K - vtot' - vtot + w'vtot (:143-147) in the caller's buffer, then Kd = sqrtD Kc sqrtD (:150-151)
     JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, nullptr, p, wn, K_out ? K_out : Kd, Kd, vt, sdev));
-    hipLaunchKernelGGL(k_kr_scale, dim3(kr_grid(ctx, n * n)), dim3(KR_NT), 0, ctx->stream, Kd, n, Kd, n, n, n, sw, sw);
+    hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * n)), dim3(KR_NT), 0, ctx->stream, Kd, n, Kd, n, n, n, sw, sw);
     JCH_HIP(ctx, hipGetLastError());
     // ---- B = sqrtD Y (Y raw, as `U' * sqrtD * Y` :156)
-    hipLaunchKernelGGL(k_kr_scale, dim3(kr_grid(ctx, n * q)), dim3(KR_NT), 0, ctx->stream, dY, ldyd, Bd, n, n, q, sw, nullptr);
+    hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * q)), dim3(KR_NT), 0, ctx->stream, dY, ldyd, Bd, n, n, q, sw, nullptr);
     JCH_HIP(ctx, hipGetLastError());
     const hipMemcpyKind dir = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (B) JCH_HIP(ctx, hipMemcpyAsync(B, Bd, sizeof(double) * nn * q, dir, ctx->stream));
@@ -142,10 +117,9 @@ extern "C" int32_t jch_krr_solve(jch_ctx *ctx, int32_t loc, const double *Kd, in
     const bool host = loc == JCH_LOC_HOST;
     const size_t nn = (size_t)n;
     JCH_TRY(jch_reserve(ctx, ctx->chol_a, sizeof(double) * nn * nn));
-    size_t off = 0;
-    auto take = [&](size_t cnt) { const size_t o = off; off += (cnt + 31) & ~(size_t)31; return o; };
-    const size_t oA = take(nn * q), oal = take(nn * q), ow = take(nn), osw = take(nn), odf = take(8);
-    JCH_TRY(jch_reserve(ctx, ctx->kr_ws, sizeof(double) * off));
+    jch_carve cv;
+    const size_t oA = cv.take(nn * q), oal = cv.take(nn * q), ow = cv.take(nn), osw = cv.take(nn), odf = cv.take(8);
+    JCH_TRY(jch_reserve(ctx, ctx->kr_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kr_ws.ptr;
     double *Ad = ws + oA, *ald = ws + oal, *wn = ws + ow, *sw = ws + osw, *fro = ws + odf, *M = (double *)ctx->chol_a.ptr;
     int *idev = nullptr;
@@ -153,14 +127,14 @@ extern "C" int32_t jch_krr_solve(jch_ctx *ctx, int32_t loc, const double *Kd, in
     const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     JCH_HIP(ctx, hipMemcpyAsync(Ad, B, sizeof(double) * nn * q, in, ctx->stream));
     JCH_HIP(ctx, hipMemcpyAsync(wn, weights_norm, sizeof(double) * nn, in, ctx->stream));
-    hipLaunchKernelGGL(k_kr_sqrt, dim3(kr_grid(ctx, n)), dim3(KR_NT), 0, ctx->stream, wn, n, sw);
+    JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
     // ---- M = Kd + lb^2 I = L L'; A = M^-1 B (:170-172); alpha = sqrtD A (what predict multiplies with, :198)
     JCH_HIP(ctx, hipMemcpyAsync(M, Kd, sizeof(double) * nn * nn, hipMemcpyDeviceToDevice, ctx->stream));
     hipLaunchKernelGGL(k_kr_adddiag, dim3((unsigned)((n + KR_NT - 1) / KR_NT)), dim3(KR_NT), 0, ctx->stream, M, n, lb * lb);
     JCH_HIP(ctx, hipGetLastError());
     JCH_TRY(jch_launch_chol_factor(ctx, M, n, n, idev));
     JCH_TRY(jch_launch_chol_solve(ctx, M, n, n, Ad, q, n, idev));
-    hipLaunchKernelGGL(k_kr_scale, dim3(kr_grid(ctx, n * q)), dim3(KR_NT), 0, ctx->stream, Ad, n, ald, n, n, q, sw, nullptr);
+    hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * q)), dim3(KR_NT), 0, ctx->stream, Ad, n, ald, n, n, q, sw, nullptr);
     JCH_HIP(ctx, hipGetLastError());
     // ---- df = 1 + n - lb^2 trace(M^-1), trace(M^-1) = |L^-1|_F^2 (:175-176)
     if (want_df) JCH_TRY(jch_launch_chol_inv_fro2(ctx, M, n, n, fro, idev));
