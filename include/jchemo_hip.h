@@ -448,6 +448,34 @@ JCH_API int32_t jch_krr_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double gamm
 JCH_API int32_t jch_krr_solve(jch_ctx *ctx, int32_t loc, const double *Kd, int64_t n, const double *B, int64_t q, const double *weights_norm,
                               double lb, int32_t want_df, double *A, double *alpha, double *df, int32_t *info);
 
+/* ---- row-wise spectra preprocessing (src/preprocessing.jl) -------------------------------------------------------
+ * Three primitives the reference's snv!, detrend!, savgol!, mavg!, mavg_runmean! and fdif! reduce to.  Float64; X n x p column-major
+ * (ldx >= n), out column-major (ldo >= n), both [loc]; rows are independent (a communicator of any size: every rank preprocesses its own
+ * shard, no collective).  One thread owns a row from its first load to its last store, so
+ *   - out == X (with ldo == ldx) works for every entry and mode and needs no second n x p buffer (any other overlap of out and X is
+ *     undefined); host data is staged in row blocks of at most 64 MiB;
+ *   - every output element is one thread's fixed-order sum (two runs give identical bits) and a NaN / Inf in row i changes row i only.
+ * A call ends the validity of the working copy a fit may have left for JCH_REUSE_XCOPY (X may just have been rewritten in place).
+ *
+ * jch_rows_standardize — `snv!` (src/preprocessing.jl:473-481): out[i, :] = (x_i - mu_i) / s_i, mu_i = the row mean (0 without cent),
+ *   s_i = the UNcorrected row standard deviation around the row mean (src/utility.jl rowstd; 1 without scal), two-pass (the mean, then the
+ *   squared deviations).  A constant row divides by s_i = 0 as the reference does: NaN / Inf in that row.
+ * jch_rows_project_out — `detrend!` (:32-47): out[i, :] = x_i - V (A x_i); A (k x p, column-major ld k) and V (p x k, column-major ld p)
+ *   HOST matrices, 1 <= k <= 8.  For detrend V = vX and A = pinv(vX'vX, rtol = sqrt(eps)) vX' are built by the caller on the host.
+ * jch_rows_fir — `savgol!` (:424-441), `mavg!` (:247-260), `mavg_runmean!` (:307-335), `fdif!` (:87-93): taps f HOST doubles, f >= 1.
+ *   mode JCH_FIR_SAME: p outputs, out[i, j] = sum_{t < f} taps[t] x[i, clamp(j + lo + t, 0, p - 1)] (replicate border), -(f - 1) <= lo <= 0
+ *   (the window contains its output); any f, f > p included.  mode JCH_FIR_VALID: p - f + 1 outputs, lo == 0, f <= p, no clamping; in place
+ *   the columns from p - f + 1 on keep their input values.  Taps that are exactly 0.0 are skipped (no 0 * Inf; fdif is one subtraction).
+ *   Windows up to 57 run from a ring of the row's originals; wider ones from a copy of a bounded block of rows. */
+#define JCH_FIR_SAME 0
+#define JCH_FIR_VALID 1
+JCH_API int32_t jch_rows_standardize(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, int32_t cent, int32_t scal,
+                                     double *out, int64_t ldo);
+JCH_API int32_t jch_rows_project_out(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *A, const double *V,
+                                     int32_t k, double *out, int64_t ldo);
+JCH_API int32_t jch_rows_fir(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *taps, int64_t f, int64_t lo,
+                             int32_t mode, double *out, int64_t ldo);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in

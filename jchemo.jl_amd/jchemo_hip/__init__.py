@@ -5,3 +5,4 @@ from .plsr import (Lwplsr, LwplsrPred, Plsr, coef, lwplsr, lwplsr_predict, query
                    summary, transform, vip, xfit, xresid, msep, rmsep, ssr, bias, r2, cor2, segmkf, segmts, gridscorelv, gridcvlv, mpar, Plsrda, dummy, plsrda, plsrda_predict, Plslda, plslda, plsqda, plslda_predict, Mbplsr, mbplsr, mbplsr_transform, mbplsr_predict,
                    Dkplsr, dkplsr, dkplsr_, krbf, kpol, Kplsr, kplsr, kplsr_, Kpca, kpca, kpca_transform, kpca_summary)
 from .krr import Krr, Krrda, gridscorelb, krr, krr_, krr_coef, krr_predict, krrda, krrda_predict  # noqa: F401
+from .preproc import Savgk, detrend, detrend_, fdif, mavg, mavg_, mavg_runmean, savgk, savgol, savgol_, snv, snv_  # noqa: F401

@@ -32,7 +32,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        msep, rmsep, ssr, bias, r2, cor2, mpar, segmkf, segmts, gridscorelv, gridcvlv,
        Plsrda, dummy, plsrda, Mbplsr, mbplsr, vip, xfit, xresid,
        Dkplsr, dkplsr, dkplsr!, krbf, kpol, Kplsr, kplsr, kplsr!, Kpca, kpca,
-       Krr, krr, krr!, gridscorelb, Krrda, krrda
+       Krr, krr, krr!, gridscorelb, Krrda, krrda,
+       snv, snv!, detrend, detrend!, savgol, savgol!, savgk, mavg, mavg!, mavg_runmean, fdif
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -1283,6 +1284,142 @@ function predict(object::Krrda, X; lb = nothing, ctx = default_ctx())
     posts = post isa AbstractMatrix ? [post] : post
     preds = [reshape(object.lev[[argmax(view(Array(z), i, :)) for i in 1:size(z, 1)]], :, 1) for z in posts]
     post isa AbstractMatrix ? (pred = preds[1], posterior = posts[1]) : (pred = preds, posterior = posts)
+end
+
+# ---- row-wise spectra preprocessing (src/preprocessing.jl): snv, detrend, savgol, savgk, mavg, mavg_runmean, fdif over
+# jch_rows_standardize / jch_rows_project_out / jch_rows_fir (include/jchemo_hip.h; DESIGN.md §14).  A host Array in gives an Array out, a
+# device array in gives a device array out; the `!` variants work in place.  `interpl` is not provided. ----------------------------------
+const _FIR_SAME = Int32(0)
+const _FIR_VALID = Int32(1)
+
+function _rows_standardize!(out, X, cent, scal, ctx)
+    n, p = size(X)
+    GC.@preserve X out check(ctx, ccall((:jch_rows_standardize, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Int32, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), Int32(cent ? 1 : 0), Int32(scal ? 1 : 0), pointer(out), max(stride(out, 2), n)))
+    out
+end
+
+function _rows_project_out!(out, X, A::Matrix{Float64}, V::Matrix{Float64}, ctx)
+    n, p = size(X); k = size(A, 1)
+    GC.@preserve X out check(ctx, ccall((:jch_rows_project_out, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), A, V, Int32(k), pointer(out), max(stride(out, 2), n)))
+    out
+end
+
+function _rows_fir!(out, X, taps::Vector{Float64}, lo, mode, ctx)
+    n, p = size(X)
+    GC.@preserve X out check(ctx, ccall((:jch_rows_fir, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Int32, Ptr{Float64}, Int64),
+        ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), taps, length(taps), lo, mode, pointer(out), max(stride(out, 2), n)))
+    out
+end
+
+"`snv(X; cent = true, scal = true)` — src/preprocessing.jl:467-471: each row minus its mean, over its uncorrected standard deviation."
+function snv(X; cent = true, scal = true, ctx = default_ctx())
+    X = _in(X)
+    _rows_standardize!(_similar(X, size(X)...), X, cent, scal, ctx)
+end
+"`snv!(X; cent = true, scal = true)` — src/preprocessing.jl:473-481, in place."
+function snv!(X; cent = true, scal = true, ctx = default_ctx())
+    _rows_standardize!(X, X, cent, scal, ctx)
+    nothing
+end
+
+# Host coefficients of `detrend`: V holds the monomials z^0 ... z^pol of z = 1 ... p (in floating point, so a large p^pol cannot wrap),
+# A = pinv(V'V) V' with the cut-off sqrt(eps) on the relative singular values.  That cut-off is part of the reference's result (for
+# spectra-sized p the Gram of the monomials keeps rank 2, DESIGN.md §14), so the polynomial is never re-fitted on the device.
+function _detrend_coef(p, pol)
+    0 <= pol <= 7 || throw(ArgumentError("detrend: pol = $pol is outside 0 ... 7 (jch_rows_project_out takes k = pol + 1 <= 8)"))
+    z = range(1.0, Float64(p), length = Int(p))
+    V = Float64[zi^e for zi in z, e in 0:pol]
+    A = pinv(V' * V, rtol = sqrt(eps(Float64))) * V'
+    Matrix{Float64}(A), V
+end
+"`detrend(X; pol = 1)` — src/preprocessing.jl:27-31: each row minus vX A row, with the reference's truncating pinv."
+function detrend(X; pol = 1, ctx = default_ctx())
+    X = _in(X)
+    A, V = _detrend_coef(size(X, 2), pol)
+    _rows_project_out!(_similar(X, size(X)...), X, A, V, ctx)
+end
+"`detrend!(X; pol = 1)` — src/preprocessing.jl:32-47, in place."
+function detrend!(X; pol = 1, ctx = default_ctx())
+    A, V = _detrend_coef(size(X, 2), pol)
+    _rows_project_out!(X, X, A, V, ctx)
+    nothing
+end
+
+"""`savgk(m, pol, d)` — the Savitzky-Golay design on the window -m ... m, on the host: `S[i, j]` is the j-th monomial at the i-th window
+point, `G = S inv(S'S)` (its column d + 1 gives the d-th Taylor coefficient of the least-squares polynomial at the centre), and
+`kern = d! G[:, d + 1]`.  Returns `(S, G, kern)` under the reference's names."""
+function savgk(m, pol, d)
+    m, pol, d = Int(m), Int(pol), Int(d)
+    m < 1 && throw(ArgumentError("savgk: the half-width m = $m must be at least 1"))
+    1 <= pol <= 2m || throw(ArgumentError("savgk: pol = $pol is outside 1 ... 2m = $(2m)"))
+    0 <= d <= pol || throw(ArgumentError("savgk: d = $d is outside 0 ... pol = $pol"))
+    S = Float64[Float64(u)^e for u in -m:m, e in 0:pol]
+    G = S * inv(S' * S)        # (an explicit inverse, not a solve: bitwise the same route as preproc.py and the restatement)
+    (S = S, G = G, kern = factorial(d) .* G[:, d + 1])
+end
+
+# UNPINNED reading (DESIGN.md §6): imfilter is a correlation and the reference passes reflect(centered(kern))
+# (src/preprocessing.jl:430-434), so the filter is a true convolution, out[j] = sum_{u=-m}^{m} kern[u] x[j - u]: as a correlation window
+# that starts at j + lo, taps = reverse(kern) and lo = -m.  (Dropping the `reverse` gives the correlation reading.)
+_savgol_taps(kern) = (Vector{Float64}(reverse(kern)), -(length(kern) >> 1))
+# UNPINNED reading for even f (DESIGN.md §6): centered(ones(f) / f) (src/preprocessing.jl:250) has the axes
+# -((f + 1) >> 1) + 1 : f - ((f + 1) >> 1), i.e. -m:m for odd f and -f/2 + 1 : f/2 for even f; imfilter correlates.
+_mavg_window(f) = (fill(1.0 / f, f), 1 - ((f + 1) >> 1))
+
+function _savgol_args(f, pol, d)
+    f = Int64(f)
+    (isodd(f) && f >= 3) || throw(ArgumentError("f must be odd and >= 3"))
+    _savgol_taps(savgk((f - 1) >> 1, pol, d).kern)
+end
+"`savgol(X; f, pol, d)` — src/preprocessing.jl:418-422: Savitzky-Golay filter of each row, replicate padding."
+function savgol(X; f, pol, d, ctx = default_ctx())
+    taps, lo = _savgol_args(f, pol, d)
+    X = _in(X)
+    _rows_fir!(_similar(X, size(X)...), X, taps, lo, _FIR_SAME, ctx)
+end
+"`savgol!(X; f, pol, d)` — src/preprocessing.jl:424-441, in place."
+function savgol!(X; f, pol, d, ctx = default_ctx())
+    taps, lo = _savgol_args(f, pol, d)
+    _rows_fir!(X, X, taps, lo, _FIR_SAME, ctx)
+    nothing
+end
+
+"`mavg(X; f)` — src/preprocessing.jl:241-245: moving average of each row with the centred kernel ones(f) / f, replicate padding."
+function mavg(X; f, ctx = default_ctx())
+    f = Int64(f)
+    f >= 1 || throw(ArgumentError("f must be >= 1"))
+    taps, lo = _mavg_window(f)
+    X = _in(X)
+    _rows_fir!(_similar(X, size(X)...), X, taps, lo, _FIR_SAME, ctx)
+end
+"`mavg!(X; f)` — src/preprocessing.jl:247-260, in place."
+function mavg!(X; f, ctx = default_ctx())
+    f = Int64(f)
+    f >= 1 || throw(ArgumentError("f must be >= 1"))
+    taps, lo = _mavg_window(f)
+    _rows_fir!(X, X, taps, lo, _FIR_SAME, ctx)
+    nothing
+end
+
+"""`mavg_runmean(X; f)` — src/preprocessing.jl:299-335: moving average without padding, (n, p) -> (n, p - f + 1), each point on the first
+unit of the kernel; every output is its own f-term sum (the reference's running sum carries its rounding along the row)."""
+function mavg_runmean(X; f, ctx = default_ctx())
+    X = _in(X); n, p = size(X); f = Int64(f)
+    1 <= f <= p || throw(ArgumentError("f = $f must agree with: 1 <= f <= p = $p"))
+    _rows_fir!(_similar(X, n, p - f + 1), X, fill(1.0 / f, f), 0, _FIR_VALID, ctx)
+end
+
+"`fdif(X; f = 2)` — src/preprocessing.jl:79-93: M[:, j] = X[:, j + f - 1] - X[:, j], (n, p) -> (n, p - f + 1)."
+function fdif(X; f = 2, ctx = default_ctx())
+    X = _in(X); n, p = size(X); f = Int64(f)
+    2 <= f <= p || throw(ArgumentError("f = $f must agree with: 2 <= f <= p = $p"))
+    taps = zeros(f); taps[1] = -1.0; taps[f] = 1.0
+    _rows_fir!(_similar(X, n, p - f + 1), X, taps, 0, _FIR_VALID, ctx)
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
