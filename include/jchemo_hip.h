@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define JCH_VERSION 108 /* 0.1.8: jch_ctx_set_profiling(ctx, N > 1) samples the sweeps, JCH_COUNTER_SWEEPS_TIMED; 0.1.7: JCH_REUSE_XCOPY, JCH_COUNTER_XCOPY_REUSED; 0.1.6: + jch_score_sums_lv, jch_predict over an nlv range as running sums over the scores; 0.1.5: screened kNN (JCH_COUNTER_KNN_SCREENED / _REDONE); 0.1.4: no shape limits (generic lwplsr / small-state paths), JCH_NIPALS_ONE_PASS, JCH_COUNTER_LOCW_REFITS; 0.1.3: + jch_lwplsr_add_query_map (0.1.2: collective fields of jch_profile, jch_ctx_allreduce_probe, jch_lwplsr_prepare / _release) */
+#define JCH_VERSION 108 /* 0.1.8 (jch_covsel_fit, like the krr and row preprocessing entries, joined without a new number): jch_ctx_set_profiling(ctx, N > 1) samples the sweeps, JCH_COUNTER_SWEEPS_TIMED; 0.1.7: JCH_REUSE_XCOPY, JCH_COUNTER_XCOPY_REUSED; 0.1.6: + jch_score_sums_lv, jch_predict over an nlv range as running sums over the scores; 0.1.5: screened kNN (JCH_COUNTER_KNN_SCREENED / _REDONE); 0.1.4: no shape limits (generic lwplsr / small-state paths), JCH_NIPALS_ONE_PASS, JCH_COUNTER_LOCW_REFITS; 0.1.3: + jch_lwplsr_add_query_map (0.1.2: collective fields of jch_profile, jch_ctx_allreduce_probe, jch_lwplsr_prepare / _release) */
 
 #if defined(JCH_BUILD)
 #define JCH_API __attribute__((visibility("default")))
@@ -475,6 +475,38 @@ JCH_API int32_t jch_rows_project_out(jch_ctx *ctx, int32_t loc, const double *X,
                                      int32_t k, double *out, int64_t ldo);
 JCH_API int32_t jch_rows_fir(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *taps, int64_t f, int64_t lo,
                              int32_t mode, double *out, int64_t ldo);
+
+/* ---- Covsel: variable selection by repeated argmax and deflation (src/covsel.jl, src/covselr.jl) ----------------------
+ * jch_covsel_fit — `covsel!` / `covsel` (src/covsel.jl:59-122).  Float64; X n x p (ldx >= n) and Y n x q (ldy >= n) column-major [loc];
+ * one GPU only (a communicator of more than one rank is JCH_EINVAL).  xmeans, ymeans (:64-67); for q > 1 Y is divided by its uncorrected
+ * column stds (:68-70; yscales is ones when q == 1).  Per step (:81-116): the criterion z over the columns (typ JCH_COVSEL_COV:
+ * z_j = sum_k (Xd'Yd / n)_jk^2, :83-84; JCH_COVSEL_COR: the squared correlations, :87-88; "aic", :92-103, is not provided), C[:, i] = z,
+ * its argmax (ties: the lowest index; a NaN never wins), then X and Y orthogonalised to that column.  The reference does that with an
+ * n x n projector (:78, :111-113); here X is only READ, once per step: an orthonormal basis Q of the deflated selected columns and
+ * Yd = (I - QQ')Yc are kept, Xd'Yd = Xc'Yd, the deflated column sums of squares are css_j - sum_k G[j,k]^2 with G = Xc'Q, and the deflated
+ * selected column is Xc[:, j] - Q G[j, :]' (orthogonalised against Q a second time before it is normalised).
+ *   nlv >= 1 is clamped to p.  Deviations: a column whose deflated sum of squares is <= 1e-10 of its original one is
+ *   exhausted — `cor` gives it z = 0 (the reference divides rounding noise by rounding noise there), and when the argmax lands on one the
+ *   loop stops: *nlv_out = the completed steps (< nlv on a rank-deficient X), and what belongs to later steps is 0 (column nlv_out of C
+ *   holds the criterion of the abandoned step).
+ *   inplace != 0: X <- Xc - Q G' and Y <- Yd, what the reference leaves in its arguments (:112-113); the working copy a fit left for
+ *   JCH_REUSE_XCOPY is then no longer valid.  inplace == 0: X and Y are not written.
+ * Outputs, each may be NULL; HOST unless noted.  sel int32 [nlv], 0-based; selcov [nlv] (:108); cov2 [p] (:109); C p x nlv (ld p);
+ * cumpvarx, cumpvary [nlv] (:117-118); xmeans [p]; ymeans, yscales [q]; G p x nlv (ld p) = Xc'Q; QtY nlv x q (ld nlv) = Q'Yc in the units of
+ * the SCALED Y (multiply column k by yscales[k] for raw units); Q n x nlv (ld n) [loc]; nlv_out.  With Xc[:, sel] = Q R and
+ * R[k, i] = G[sel_i, k] (upper triangular), `covselr` (src/covselr.jl:48-53) is B = R^-1 QtY on the host.
+ * Every sum is taken in a fixed order: two runs give identical bits. */
+#define JCH_COVSEL_COV 0
+#define JCH_COVSEL_COR 1
+JCH_API int32_t jch_covsel_fit(jch_ctx *ctx, int32_t loc, double *X, int64_t n, int64_t p, int64_t ldx, double *Y, int64_t q, int64_t ldy, int32_t nlv,
+                               int32_t typ, int32_t inplace, int32_t *sel, double *selcov, double *cov2, double *C, double *cumpvarx, double *cumpvary,
+                               double *xmeans, double *ymeans, double *yscales, double *G, double *QtY, double *Q, int32_t *nlv_out);
+/* jch_covsel_pass — the one kernel a Covsel step spends its time in, on its own: out (p x b, ld p) = (X - 1 mu')' V, all DEVICE pointers; X n x p
+ * (ldx >= n, read only), mu p means or NULL (no centring), V n x b (ldv >= n), any b >= 1: up to 32 panel columns are served by one read of X,
+ * wider panels by one read per 32 columns.  mu is subtracted in registers (nothing relies on sum(V) = 0).  Per-workgroup partials are summed in
+ * a fixed order: two runs give identical bits. */
+JCH_API int32_t jch_covsel_pass(jch_ctx *ctx, const double *X, int64_t n, int64_t p, int64_t ldx, const double *mu, const double *V, int64_t b, int64_t ldv,
+                                double *out);
 
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix

@@ -85,6 +85,7 @@ struct jch_ctx {
     jch_buf kc_vt, pc_ws;   // panel operand of the Kc pass, kpca panels and small state (kpca.hip)
     jch_buf chol_inv, chol_a, chol_w, chol_s, kr_ws;   // inv(L_kk) blocks of the last factor, krr's working copy of Kd, the L^-T workspace of df, info / partial sums (chol.hip); krr staging (krr.hip)
     jch_buf rp_stage, rp_rows, rp_coef;   // row preprocessing (rowprep.hip): bounded row-block staging of host data, the row-block copy of the wide-window FIR, taps / A and V
+    jch_buf cs_ws, cs_part;   // covsel (covsel.hip): [Yd | Q] and the small state of a selection; per-workgroup partials of the pass
     const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
     int64_t chol_n = 0, chol_ld = 0;
     // profiling

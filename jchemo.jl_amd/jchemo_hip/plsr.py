@@ -388,7 +388,10 @@ def _predict_range(fm: Plsr, X, lo: int, hi: int, ctx):
 
 def coef(fm: Plsr, *, nlv: Optional[int] = None):
     """src/plskern.jl:207-217 — (B p x q, int 1 x q); nlv = 0 gives B = 0.  p x q host glue.  Dkplsr: coef(object.fm)
-    (src/dkplsr.jl:146-148).  Kplsr: (beta = C[:, 1:nlv]', int = ymeans') (src/kplsr.jl:221-228)."""
+    (src/dkplsr.jl:146-148).  Kplsr: (beta = C[:, 1:nlv]', int = ymeans') (src/kplsr.jl:221-228).  Covselr: coef(object.fm)."""
+    if type(fm).__name__ == "Covselr":
+        from .covsel import covselr_coef
+        return covselr_coef(fm)
     if isinstance(fm, Kplsr):
         return kplsr_coef(fm, nlv=nlv)
     if isinstance(fm, Dkplsr):
@@ -419,7 +422,11 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
             world: Optional[int] = None):
     """src/plskern.jl:226-238: a collection of nlv becomes the contiguous range max(0,min):min(a,max); one
     value -> matrix, several -> list of matrices.  All values are computed in ONE pass over X.
-    `rank` / `world` (kNN-LWPLSR only): split the queries over `world` replicas, see lwplsr_predict."""
+    `rank` / `world` (kNN-LWPLSR only): split the queries over `world` replicas, see lwplsr_predict.
+    A Covselr model: src/covselr.jl:61-64 (covselr_predict)."""
+    if type(fm).__name__ == "Covselr":
+        from .covsel import covselr_predict
+        return covselr_predict(fm, X, ctx=ctx)
     if isinstance(fm, Lwplsr):
         return lwplsr_predict(fm, X, nlv=nlv, ctx=ctx, rank=rank, world=world)
     if isinstance(fm, Plsrda):

@@ -33,7 +33,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Plsrda, dummy, plsrda, Mbplsr, mbplsr, vip, xfit, xresid,
        Dkplsr, dkplsr, dkplsr!, krbf, kpol, Kplsr, kplsr, kplsr!, Kpca, kpca,
        Krr, krr, krr!, gridscorelb, Krrda, krrda,
-       snv, snv!, detrend, detrend!, savgol, savgol!, savgk, mavg, mavg!, mavg_runmean, fdif
+       snv, snv!, detrend, detrend!, savgol, savgol!, savgk, mavg, mavg!, mavg_runmean, fdif,
+       Covsel, Covselr, covsel, covsel!, covselr
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -1420,6 +1421,90 @@ function fdif(X; f = 2, ctx = default_ctx())
     2 <= f <= p || throw(ArgumentError("f = $f must agree with: 2 <= f <= p = $p"))
     taps = zeros(f); taps[1] = -1.0; taps[f] = 1.0
     _rows_fir!(_similar(X, n, p - f + 1), X, taps, 0, _FIR_VALID, ctx)
+end
+
+# ---- Covsel (src/covsel.jl, src/covselr.jl) over jch_covsel_fit (include/jchemo_hip.h; DESIGN.md §15): variable selection that only READS
+# X, once per selected variable.  `sel` is 1-based here, as in the reference.  Deviations: a column whose deflated sum of squares fell to
+# 1e-10 of its original one is exhausted (`cor` gives it 0; a selection that lands on one stops, so a rank-deficient X yields fewer than nlv
+# rows); typ = "aic" is not provided. ----------------------------------------------------------------------------------------------------
+const _COVSEL_TYP = Dict("cov" => Int32(0), "cor" => Int32(1))
+
+struct Covsel                     # what the reference's `covsel` returns (src/covsel.jl:119-121): sel (the table sel, cov2, cumpvarx,
+    sel                           # cumpvary), cov2, C; then what `covselr` is computed from: the completed steps, the means and scales,
+    cov2::Vector{Float64}         # G = Xc'Q (p x nlv), QtY = Q'Yc (nlv x q, units of the scaled Y) and Q (n x nlv, where X lives)
+    C::Matrix{Float64}
+    nlv::Int
+    xmeans::Vector{Float64}
+    ymeans::Vector{Float64}
+    yscales::Vector{Float64}
+    G::Matrix{Float64}
+    QtY::Matrix{Float64}
+    Q
+end
+
+struct Mlr                        # the reference's Mlr as far as `covselr` uses it (src/mlr.jl): B (nlv x q), int (1 x q), raw Y units
+    B::Matrix{Float64}
+    int::Matrix{Float64}
+end
+
+struct Covselr                    # src/covselr.jl:1-5
+    fm
+    sel
+    cov2::Vector{Float64}
+end
+
+function _covsel_fit!(X, Y, nlv, typ, inplace, ctx)
+    haskey(_COVSEL_TYP, typ) || throw(ArgumentError("typ = $typ: \"cov\" or \"cor\" (\"aic\" is marked not useful in the reference and is not provided)"))
+    n, p = size(X); q = size(Y, 2)
+    size(Y, 1) == n || throw(DimensionMismatch("X has $n rows, Y has $(size(Y, 1))"))
+    nlv = nlv === nothing ? p : Int(nlv)                       # src/covsel.jl:63
+    nlv >= 1 || throw(ArgumentError("nlv = $nlv must be at least 1"))
+    a = min(nlv, p)
+    sel = zeros(Int32, a); selcov = zeros(a); cov2 = zeros(p); Cm = zeros(p, a); cpx = zeros(a); cpy = zeros(a)
+    xm = zeros(p); ym = zeros(q); ys = zeros(q); G = zeros(p, a); QtY = zeros(a, q)
+    Q = _similar(X, n, a)
+    done = Ref{Int32}(0)
+    GC.@preserve X Y Q check(ctx, ccall((:jch_covsel_fit, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Int32, Int32, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+        ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), pointer(Y), q, max(stride(Y, 2), n), Int32(a), _COVSEL_TYP[typ], Int32(inplace ? 1 : 0),
+        sel, selcov, cov2, Cm, cpx, cpy, xm, ym, ys, G, QtY, pointer(Q), done))
+    k = Int(done[])
+    tab = _table((sel = Int64.(sel)[1:k] .+ 1, cov2 = selcov[1:k], cumpvarx = cpx[1:k], cumpvary = cpy[1:k]))
+    Covsel(tab, cov2, Cm[:, 1:k], k, xm, ym, ys, G[:, 1:k], QtY[1:k, :], Q[:, 1:k])
+end
+
+"""`covsel(X, Y; nlv = nothing, typ = "cov")` — src/covsel.jl:54-57: X and Y are left untouched (and, unlike the reference, not copied: the
+selection only reads X).  nlv = nothing selects p variables."""
+function covsel(X, Y; nlv = nothing, typ = "cov", ctx = default_ctx())
+    X = _in(X)
+    _covsel_fit!(X, _colocate_mat(_in(Y), X), nlv, typ, false, ctx)
+end
+"""`covsel!(X, Y; nlv = nothing, typ = "cov")` — src/covsel.jl:59-122: X and Y end up centred (Y scaled when q > 1) and orthogonalised to
+every selected column, as the reference leaves them (:112-113)."""
+function covsel!(X, Y; nlv = nothing, typ = "cov", ctx = default_ctx())
+    _covsel_fit!(X, Y, nlv, typ, true, ctx)
+end
+
+"""`covselr(X, Y; nlv, typ = "cov")` — src/covselr.jl:48-53: `covsel`, then the MLR of Y on the selected columns.  With Xc[:, sel] = Q R and
+R[k, i] = G[sel_i, k] the coefficients are B = R^-1 Q'Yc, a nlv x nlv triangular solve on the host, rescaled by yscales to the raw Y."""
+function covselr(X, Y; nlv, typ = "cov", ctx = default_ctx())
+    res = covsel(X, Y; nlv = nlv, typ = typ, ctx = ctx)
+    s = res.sel.sel
+    R = UpperTriangular(permutedims(res.G[s, :]))
+    B = (R \ res.QtY) .* res.yscales'
+    int = res.ymeans' .- res.xmeans[s]' * B
+    Covselr(Mlr(B, Matrix(int)), res.sel, res.cov2)
+end
+
+"`coef(object::Covselr)` — `coef(object.fm)` of the reference's Mlr: (B, int)."
+coef(object::Covselr) = (B = object.fm.B, int = object.fm.int)
+
+"`predict(object::Covselr, X)` — src/covselr.jl:61-64: int + X[:, sel] B (jch_affine_gemm on the gathered columns)."
+function predict(object::Covselr, X; ctx = default_ctx())
+    X = _in(X)
+    s = object.sel.sel
+    (pred = _affine(X[:, s], nothing, nothing, object.fm.B, vec(object.fm.int), ctx),)
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
