@@ -508,6 +508,29 @@ JCH_API int32_t jch_covsel_fit(jch_ctx *ctx, int32_t loc, double *X, int64_t n, 
 JCH_API int32_t jch_covsel_pass(jch_ctx *ctx, const double *X, int64_t n, int64_t p, int64_t ldx, const double *mu, const double *V, int64_t b, int64_t ldv,
                                 double *out);
 
+/* ---- weighted centred Gram, PCA and PCR (src/pcasvd.jl, src/pcaeigen.jl, src/pcr.jl) ----------------------------------------
+ * jch_xtdx -- G = (X - 1 mu')' D (X - 1 mu') (p x p), D = diag(weights / sum weights) (weights NULL = ones), mu = X'D 1, in one pass over the
+ * column-major X on the f64 matrix cores with no n x p workspace: the means and the weights are applied in registers (nothing is computed as
+ * X'DX - mu mu').  X n x p (ldx >= n) and weights (n) [loc], read only; p <= 32768; row indices are 64-bit.  G_dev (ld ldg >= p) and mu_dev (p): DEVICE
+ * pointers, each may be NULL (ctx workspace); G_host (p x p, ld p) and mu_host (p): HOST copies, each may be NULL.  Rows >= n are never read.  Every
+ * sum has a fixed order and both triangles are written from one value: G == G' bitwise, two runs give identical bits, and so do a host and a
+ * device X and an aligned and an unaligned X.  A NaN at X[r, j] reaches only row j and column j of G.  One rank only. */
+JCH_API int32_t jch_xtdx(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *weights, double *G_dev, int64_t ldg,
+                         double *mu_dev, double *G_host, double *mu_host);
+/* jch_pca_fit -- `pcasvd!` / `pcaeigen!` / `pcaeigenk!` (src/pcasvd.jl:79-101) and what `pcr!` (src/pcr.jl:82-97) adds to it.  P and sv^2 are the nlv
+ * leading eigenpairs of G = Xs'D Xs (Xs = cscale(X, xmeans, xscales); jch_xtdx, rescaled by xscales = sqrt(diag G) when scal) from the block
+ * subspace iteration of jch_kpca_fit (tol, maxit: its stopping rule on the residuals |G p_i - eig_i p_i| <= tol eig_1); T = Xs P.  X is never
+ * written (the reference's `!` forms leave the centred X in their argument; here they do not).  nlv is clamped to min(n, p).
+ *   X n x p, weights n or NULL, Y n x q or NULL (q = 0) [loc].
+ *   Outputs, each may be NULL: T n x nlv (ld n) and weights_norm n [loc]; HOST: P p x nlv (ld p), each column signed so that its largest-|.| entry
+ *   (first index on ties) is positive; sv, eig, resid (nlv values: the reference keeps min(n, p)); xmeans, xscales, colvar = diag(G) before the
+ *   rescaling (p); sstot = trace(G); niter; nlv_out; converged (1 / 0: the iteration's own decision).  With Y: ymeans (q) and xtdy = Xs'D (Y - 1 ymeans') (p x q, ld p, through jch_covsel_pass),
+ *   from which beta = diag(1 / eig) P' xtdy (src/pcr.jl:93).  One rank only.  Every sum has a fixed order: two fits give identical bits. */
+JCH_API int32_t jch_pca_fit(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *weights, const double *Y, int64_t q,
+                            int64_t ldy, int32_t nlv, int32_t scal, double tol, int32_t maxit, double *T, double *P, double *sv, double *eig, double *xmeans,
+                            double *xscales, double *weights_norm, double *sstot, double *colvar, double *ymeans, double *xtdy, int32_t *niter,
+                            double *resid, int32_t *nlv_out, int32_t *converged);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in

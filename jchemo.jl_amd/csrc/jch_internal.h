@@ -82,10 +82,11 @@ struct jch_ctx {
     jch_buf gram, xr, yr, xstage, ystage, wstage, tbuf, dnorm, part, kpart, small, colpart, gemm_b, gemm_out, xq, tickets, qz, lw_work, lw_xrm, lvws, lw_flags, lw_screen;
     jch_buf kg_ws, dk_x, dk_y, dk_k, dk_q, dk_o, dk_s;   // Gram kernel workspace (kgram.hip), dkplsr staging (dkplsr.hip)
     jch_buf kp_ws;   // kplsr panels and small state (kplsr.hip)
-    jch_buf kc_vt, pc_ws;   // panel operand of the Kc pass, kpca panels and small state (kpca.hip)
+    jch_buf kc_vt, pc_ws, pc_vec;   // panel operand of the panel pass, the eigensolver's panels and small state, kpca's n-vectors (kpca.hip)
     jch_buf chol_inv, chol_a, chol_w, chol_s, kr_ws;   // inv(L_kk) blocks of the last factor, krr's working copy of Kd, the L^-T workspace of df, info / partial sums (chol.hip); krr staging (krr.hip)
     jch_buf rp_stage, rp_rows, rp_coef;   // row preprocessing (rowprep.hip): bounded row-block staging of host data, the row-block copy of the wide-window FIR, taps / A and V
     jch_buf cs_ws, cs_part;   // covsel (covsel.hip): [Yd | Q] and the small state of a selection; per-workgroup partials of the pass
+    jch_buf xt_part, xt_ws;   // xtdx.hip: per-split partial tiles of the Gram pass; G, the vectors and the staging of a PCA fit
     const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
     int64_t chol_n = 0, chol_ld = 0;
     // profiling
@@ -302,6 +303,23 @@ int32_t jch_launch_kp_centred_gram(jch_ctx *ctx, int kind, double gamma, double 
 // kpca.hip: out (n x b, ld ldo) = Kc (diag(d) V) on the f64 matrix cores (d: device n-vector or null); any b, chunks of 64 columns
 int32_t jch_launch_kc_panel(jch_ctx *ctx, const double *Kc, int64_t n, int64_t ldk, const double *V, int64_t ldv, int b, const double *d,
                             double *out, int64_t ldo);
+// kpca.hip: the nlv leading eigenpairs (by |.|) of the symmetric device matrix A (dim x dim, ld lda) -- of diag(sqrtw) A diag(sqrtw) when sqrtw (a
+// device dim-vector) is given -- by block subspace iteration with Rayleigh-Ritz, block b = min(dim, roundup16(nlv + oversample)); 1 <= nlv <= dim.
+// Stops when the residuals |A x_e - theta_e x_e| of the first nlv pairs are all <= tol |theta_0|, or after maxit iterations.  The device pointers
+// point into ctx->pc_ws and hold until the next call; the call ends synchronised with ctx->stream up to the sign kernels it enqueued last.
+struct jch_eig_lead_out {
+    int b = 0, niter = 0;
+    bool converged = false;
+    std::vector<double> theta, resid;   // host: the b Ritz values ordered by |.| descending; the residual norms of the first nlv pairs
+    double *X = nullptr;                // dim x b (ld dim): Ritz vectors, the first nlv signed so that their largest-|.| entry (first index on ties) is positive
+    double *AX = nullptr;               // dim x b: A (sqrtw o X), signed alike
+    const double *theta_dev = nullptr;  // the Ritz values on the device
+    double *scratch = nullptr;          // dim x b the caller may use (the last iterate)
+};
+int32_t jch_eig_lead(jch_ctx *ctx, const double *A, int64_t dim, int64_t lda, const double *sqrtw, int nlv, double tol, int maxit, jch_eig_lead_out *out);
+// xtdx.hip: G (p x p, ld ldg) = (X - 1 mu')' diag(d) (X - 1 mu'), everything on the device; X n x p column-major (ld ldx), read only.  Both
+// triangles are written from the same value; fixed-order sums, no atomics.
+int32_t jch_launch_xtdx(jch_ctx *ctx, const double *X, int64_t n, int p, int64_t ldx, const double *mu, const double *d, double *G, int64_t ldg);
 // kmethod.hip: what the kernel-method entry points (dkplsr.hip, kplsr.hip, kpca.hip, krr.hip) share
 int32_t jch_check_kernel(jch_ctx *ctx, const char *who, int32_t kind, int32_t degree);   // kernel kind / degree, one rank only
 // column-major rows x cols matrix from src (ld lds) to dst (ld ldd) on ctx->stream

@@ -11,7 +11,8 @@
 //   k_pc_svqb / k_pc_orth  SVQB orthonormalisation of the next block Z (twice), dependent directions refilled from a fixed
 //                          pseudo-random reservoir
 // Convergence is decided on the host from the residuals of the first nlv pairs; every reduction has a fixed order, so two fits
-// are bitwise equal.
+// are bitwise equal.  The iteration itself is jch_eig_lead (jch_internal.h): "a symmetric device matrix times a panel", with or without
+// the row metric sqrtw.  jch_kpca_fit runs it on Kc with sqrtw, jch_pca_fit (xtdx.hip) on the p x p Gram without.
 #include <math.h>
 #include <stdlib.h>
 
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(PC_NT) void k_pc_rot(const double *__restrict__ Q, 
                     wa[jj] = fma(wk, s, wa[jj]);
                 }
         }
-    const double swi = row ? sw[i] : 0.0;
+    const double swi = row ? (sw ? sw[i] : 1.0) : 0.0;   // (sw = null: no row metric; a product with 1.0 is exact)
 #pragma unroll
     for (int jj = 0; jj < 16; ++jj) {
         const int e = e0 + jj;
@@ -423,20 +424,28 @@ __global__ __launch_bounds__(PC_NT) void k_pc_sign(const double *__restrict__ X,
     if (threadIdx.x == 0) sg[blockIdx.x] = (si[0] < n && x[si[0]] < 0.0) ? -1.0 : 1.0;
 }
 
-// U = sg o X, P = sqrtw o U / sv (src/kpca.jl:113 `sqrtD * scale(U, sv)`), T = Kc P = sg o WS / sv (:114), first A columns.
-// U may alias X and T may alias WS (element-wise).
-__global__ __launch_bounds__(PC_NT) void k_pc_out(const double *X, const double *WS, int64_t n, int A, const double *__restrict__ sg,
-                                                  const double *__restrict__ theta, const double *__restrict__ sw, double *U, double *__restrict__ P,
-                                                  double *T)
+// In place: the first A columns of X and of WS times sg (a product with +-1 is exact)
+__global__ __launch_bounds__(PC_NT) void k_pc_apply_sign(double *__restrict__ X, double *__restrict__ WS, int64_t n, int A, const double *__restrict__ sg)
+{
+    const int64_t tot = n * A;
+    for (int64_t e = (int64_t)blockIdx.x * PC_NT + threadIdx.x; e < tot; e += (int64_t)gridDim.x * PC_NT) {
+        const double s = sg[e / n];
+        X[e] = s * X[e];
+        WS[e] = s * WS[e];
+    }
+}
+
+// From the sign-fixed Ritz vectors U and WS = Kc (sqrtw o U): P = sqrtw o U / sv (src/kpca.jl:113 `sqrtD * scale(U, sv)`),
+// T = Kc P = WS / sv (:114), first A columns.  T may alias WS (element-wise).
+__global__ __launch_bounds__(PC_NT) void k_pc_out(const double *__restrict__ U, const double *WS, int64_t n, int A, const double *__restrict__ theta,
+                                                  const double *__restrict__ sw, double *__restrict__ P, double *T)
 {
     const int64_t tot = n * A;
     for (int64_t e = (int64_t)blockIdx.x * PC_NT + threadIdx.x; e < tot; e += (int64_t)gridDim.x * PC_NT) {
         const int64_t j = e / n, i = e - j * n;
-        const double sv = sqrt(fabs(theta[j])), s = sg[j];
-        const double u = s * X[e], t = s * WS[e];
-        U[e] = u;
-        P[e] = sw[i] * u / sv;
-        T[e] = t / sv;
+        const double sv = sqrt(fabs(theta[j]));
+        P[e] = sw[i] * U[e] / sv;
+        T[e] = WS[e] / sv;
     }
 }
 
@@ -487,6 +496,83 @@ int oversample()
     return v >= 0 && v <= 4096 ? v : 7;
 }
 
+}  // namespace
+
+// The leading eigenpairs of the symmetric device matrix A (dim x dim, ld lda), or of sqrtw o A o sqrtw' when sqrtw is given, by block subspace
+// iteration with Rayleigh-Ritz (jch_internal.h).  One read of A per iteration; convergence is decided on the host from the
+// residuals of the first nlv pairs; every reduction has a fixed order.
+int32_t jch_eig_lead(jch_ctx *ctx, const double *A, int64_t dim, int64_t lda, const double *sqrtw, int nlv, double tol, int maxit, jch_eig_lead_out *out)
+{
+    const int64_t n = dim;
+    const size_t nn = (size_t)n;
+    const int b = (int)std::min<int64_t>(n, ((int64_t)nlv + oversample() + 15) / 16 * 16);
+    // ---- workspace (doubles, ld n): Q | W | Z | X | WS | reservoir (n x b each), partials and the small state
+    pc_state st{};
+    st.n = n; st.b = b;
+    st.nrb = (int)std::max<int64_t>(1, std::min<int64_t>(PC_RED_NB, (n + 255) / 256));
+    st.chunk = (n + st.nrb - 1) / st.nrb;
+    const int64_t rblk = (n + PC_NT - 1) / PC_NT;
+    jch_carve cv;
+    const size_t nb = nn * b;
+    const size_t oQ = cv.take(nb), oW = cv.take(nb), oZ = cv.take(nb), oX = cv.take(nb), oWS = cv.take(nb), oR = cv.take(nb),
+                 opart = cv.take((size_t)st.nrb * b * b), ogws = cv.take(b > PC_LDS_B ? pc_eig_doubles(b) : 0), oS = cv.take((size_t)b * b), oth = cv.take(b),
+                 oM = cv.take((size_t)b * b), orf = cv.take(b), orp = cv.take((size_t)rblk * b), osg = cv.take(nlv);
+    JCH_TRY(jch_reserve(ctx, ctx->pc_ws, sizeof(double) * cv.off));
+    double *ws = (double *)ctx->pc_ws.ptr;
+    double *Qd = ws + oQ, *Wd = ws + oW, *Zd = ws + oZ, *Xd = ws + oX, *WSd = ws + oWS, *rpart = ws + orp, *sg = ws + osg;
+    st.part = ws + opart; st.gws = ws + ogws; st.S = ws + oS; st.theta = ws + oth; st.M = ws + oM; st.refill = ws + orf; st.res = ws + oR;
+    st.lds = b <= PC_LDS_B ? sizeof(double) * pc_eig_doubles(b) : 0;
+    static jch_per_device_once attr;
+    if (!attr.done(ctx->device)) {
+        JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_pc_rr, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_pc_svqb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr.mark(ctx->device);
+    }
+    // ---- start block: uniform numbers from a fixed seed, orthonormalised (SVQB twice); the reservoir of refill columns
+    JCH_TRY(jch_launch_fill(ctx, st.res, n, b, n, 0, n, 0x6b706361ULL));
+    JCH_TRY(jch_launch_fill(ctx, Zd, n, b, n, 0, n, 0x6b706360ULL));
+    JCH_TRY(svqb(ctx, st, Zd, Xd));
+    JCH_TRY(svqb(ctx, st, Xd, Qd));
+    std::vector<double> &th = out->theta;
+    std::vector<double> &res = out->resid;
+    th.assign((size_t)b, 0.0);
+    res.assign((size_t)nlv, 0.0);
+    std::vector<double> rp((size_t)rblk * b);
+    int it = 0;
+    bool conv = false;
+    for (;;) {
+        ++it;
+        JCH_TRY(jch_launch_kc_panel(ctx, A, n, lda, Qd, n, b, sqrtw, Wd, n));          // W = A (sqrtw o Q)
+        JCH_TRY(launch_part(ctx, st, Qd, Wd, sqrtw));                                    // Q' (sqrtw o W) partials
+        hipLaunchKernelGGL(k_pc_rr, dim3(1), dim3(PC_NT), st.lds, ctx->stream, st.part, st.nrb, b, st.gws, st.S, st.theta);
+        JCH_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_pc_rot, rows_grid(st), dim3(PC_NT), 0, ctx->stream, Qd, Wd, n, b, st.S, st.theta, sqrtw, Xd, WSd, Zd, rpart);
+        JCH_HIP(ctx, hipGetLastError());
+        JCH_HIP(ctx, hipMemcpyAsync(th.data(), st.theta, sizeof(double) * b, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(rp.data(), rpart, sizeof(double) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        conv = true;
+        for (int e = 0; e < nlv; ++e) {
+            double s = 0.0;
+            for (int64_t r = 0; r < rblk; ++r) s += rp[(size_t)r * b + e];
+            res[e] = sqrt(s);
+            if (!(res[e] <= tol * fabs(th[0]))) conv = false;
+        }
+        if (conv || it >= maxit) break;
+        JCH_TRY(svqb(ctx, st, Zd, Wd));   // next block: orth(A X), W is free until the next pass
+        JCH_TRY(svqb(ctx, st, Wd, Qd));
+    }
+    // ---- the sign rule of the outputs, applied to the Ritz vectors and to W S alike
+    hipLaunchKernelGGL(k_pc_sign, dim3((unsigned)nlv), dim3(PC_NT), 0, ctx->stream, Xd, n, sg);
+    hipLaunchKernelGGL(k_pc_apply_sign, dim3(jch_grid1(ctx, n * nlv)), dim3(PC_NT), 0, ctx->stream, Xd, WSd, n, nlv, sg);
+    JCH_HIP(ctx, hipGetLastError());
+    out->b = b; out->niter = it; out->converged = conv;
+    out->X = Xd; out->AX = WSd; out->theta_dev = st.theta; out->scratch = Qd;
+    return JCH_OK;
+}
+
+namespace {
+
 bool psd_kernel(int kind, double gamma, double coef0, int degree)
 {
     if (kind == JCH_KERN_RBF) return gamma >= 0.0;
@@ -510,7 +596,6 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
     if (!(tol > 0.0)) return jch_fail(ctx, JCH_EINVAL, "%s: tol must be > 0", who);
     if (n > (1 << 20)) return jch_fail(ctx, JCH_EINVAL, "%s: n=%lld too large", who, (long long)n);
     const int A = (int)std::min<int64_t>(n, nlv);   // src/kpca.jl:100 `nlv = min(nlv, n)`
-    const int b = (int)std::min<int64_t>(n, ((int64_t)A + oversample() + 15) / 16 * 16);
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const bool host = loc == JCH_LOC_HOST;
     const size_t nn = (size_t)n;
@@ -522,34 +607,17 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
         JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
         dX = (double *)ctx->dk_x.ptr; ldxd = n;
     }
-    // ---- workspace (doubles, ld n): Q | W | Z | X | WS | reservoir (n x b each), vectors, partials and the small state
-    pc_state st{};
-    st.n = n; st.b = b;
-    st.nrb = (int)std::max<int64_t>(1, std::min<int64_t>(PC_RED_NB, (n + 255) / 256));
-    st.chunk = (n + st.nrb - 1) / st.nrb;
-    const int64_t rblk = (n + PC_NT - 1) / PC_NT;
+    // ---- the fit's own vectors (the eigensolver's panels live in ctx->pc_ws)
     jch_carve cv;
-    const size_t nb = nn * b;
-    const size_t oQ = cv.take(nb), oW = cv.take(nb), oZ = cv.take(nb), oX = cv.take(nb), oWS = cv.take(nb), oR = cv.take(nb), ow = cv.take(nn), osw = cv.take(nn),
-                 ovt = cv.take(nn), ohdr = cv.take(8), os = cv.take(8), oxs = cv.take((size_t)p), opart = cv.take((size_t)st.nrb * b * b),
-                 ogws = cv.take(b > PC_LDS_B ? pc_eig_doubles(b) : 0), oS = cv.take((size_t)b * b), oth = cv.take(b), oM = cv.take((size_t)b * b),
-                 orf = cv.take(b), orp = cv.take((size_t)rblk * b), osg = cv.take(A), otr = cv.take(8);
-    JCH_TRY(jch_reserve(ctx, ctx->pc_ws, sizeof(double) * cv.off));
-    double *ws = (double *)ctx->pc_ws.ptr;
-    double *Qd = ws + oQ, *Wd = ws + oW, *Zd = ws + oZ, *Xd = ws + oX, *WSd = ws + oWS, *wn = ws + ow, *sw = ws + osw, *vt = ws + ovt,
-           *hdr = ws + ohdr, *sdev = ws + os, *xs_dev = ws + oxs, *rpart = ws + orp, *sg = ws + osg, *trd = ws + otr;
-    st.part = ws + opart; st.gws = ws + ogws; st.S = ws + oS; st.theta = ws + oth; st.M = ws + oM; st.refill = ws + orf; st.res = ws + oR;
-    st.lds = b <= PC_LDS_B ? sizeof(double) * pc_eig_doubles(b) : 0;
-    static jch_per_device_once attr;
-    if (!attr.done(ctx->device)) {
-        JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_pc_rr, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_pc_svqb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr.mark(ctx->device);
-    }
+    const size_t ow = cv.take(nn), osw = cv.take(nn), ovt = cv.take(nn), owr = cv.take(nn), ohdr = cv.take(8), os = cv.take(8), oxs = cv.take((size_t)p),
+                 otr = cv.take(8);
+    JCH_TRY(jch_reserve(ctx, ctx->pc_vec, sizeof(double) * cv.off));
+    double *ws = (double *)ctx->pc_vec.ptr;
+    double *wn = ws + ow, *sw = ws + osw, *vt = ws + ovt, *wraw = ws + owr, *hdr = ws + ohdr, *sdev = ws + os, *xs_dev = ws + oxs, *trd = ws + otr;
     const double *dw = weights;
     if (host && weights) {
-        JCH_HIP(ctx, hipMemcpyAsync(Wd, weights, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));   // (W: free until the loop)
-        dw = Wd;
+        JCH_HIP(ctx, hipMemcpyAsync(wraw, weights, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
+        dw = wraw;
     }
     JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/kpca.jl:93)
     JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
@@ -565,41 +633,14 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
     JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * nn * nn));
     double *Kc = (double *)ctx->dk_k.ptr;
     JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, nullptr, p, wn, K_out ? K_out : Kc, Kc, vt, sdev));
-    // ---- start block: uniform numbers from a fixed seed, orthonormalised (SVQB twice); the reservoir of refill columns
-    JCH_TRY(jch_launch_fill(ctx, st.res, n, b, n, 0, n, 0x6b706361ULL));
-    JCH_TRY(jch_launch_fill(ctx, Zd, n, b, n, 0, n, 0x6b706360ULL));
-    JCH_TRY(svqb(ctx, st, Zd, Xd));
-    JCH_TRY(svqb(ctx, st, Xd, Qd));
-    std::vector<double> th((size_t)b), rp((size_t)rblk * b), res((size_t)A);
-    int it = 0;
-    bool conv = false;
-    for (;;) {
-        ++it;
-        JCH_TRY(jch_launch_kc_panel(ctx, Kc, n, n, Qd, n, b, sw, Wd, n));             // W = Kc (sqrtw o Q)
-        JCH_TRY(launch_part(ctx, st, Qd, Wd, sw));                                       // Q' A Q partials
-        hipLaunchKernelGGL(k_pc_rr, dim3(1), dim3(PC_NT), st.lds, ctx->stream, st.part, st.nrb, b, st.gws, st.S, st.theta);
-        JCH_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_pc_rot, rows_grid(st), dim3(PC_NT), 0, ctx->stream, Qd, Wd, n, b, st.S, st.theta, sw, Xd, WSd, Zd, rpart);
-        JCH_HIP(ctx, hipGetLastError());
-        JCH_HIP(ctx, hipMemcpyAsync(th.data(), st.theta, sizeof(double) * b, hipMemcpyDeviceToHost, ctx->stream));
-        JCH_HIP(ctx, hipMemcpyAsync(rp.data(), rpart, sizeof(double) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
-        JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        conv = true;
-        for (int e = 0; e < A; ++e) {
-            double s = 0.0;
-            for (int64_t r = 0; r < rblk; ++r) s += rp[(size_t)r * b + e];
-            res[e] = sqrt(s);
-            if (!(res[e] <= tol * fabs(th[0]))) conv = false;
-        }
-        if (conv || it >= maxit) break;
-        JCH_TRY(svqb(ctx, st, Zd, Wd));   // next block: orth(A X), W is free until the next pass
-        JCH_TRY(svqb(ctx, st, Wd, Qd));
-    }
+    // ---- the nlv leading eigenpairs of Kd = sqrtD Kc sqrtD
+    jch_eig_lead_out eg;
+    JCH_TRY(jch_eig_lead(ctx, Kc, n, n, sw, A, tol, maxit, &eg));
+    const std::vector<double> &th = eg.theta, &res = eg.resid;
+    const int it = eg.niter;
     // ---- outputs (:104-114): U = sign-fixed Ritz vectors, P = sqrtD U / sv, T = Kc P; eig = |theta|, sv = sqrt(eig)
-    hipLaunchKernelGGL(k_pc_sign, dim3((unsigned)A), dim3(PC_NT), 0, ctx->stream, Xd, n, sg);
-    JCH_HIP(ctx, hipGetLastError());
-    double *Pd = Qd;
-    hipLaunchKernelGGL(k_pc_out, dim3(jch_grid1(ctx, n * A)), dim3(PC_NT), 0, ctx->stream, Xd, WSd, n, A, sg, st.theta, sw, Xd, Pd, WSd);
+    double *Pd = eg.scratch, *WSd = eg.AX;
+    hipLaunchKernelGGL(k_pc_out, dim3(jch_grid1(ctx, n * A)), dim3(PC_NT), 0, ctx->stream, eg.X, WSd, n, A, eg.theta_dev, sw, Pd, WSd);
     JCH_HIP(ctx, hipGetLastError());
     const bool psd = psd_kernel(kind, gamma, coef0, degree);
     if (psd) {

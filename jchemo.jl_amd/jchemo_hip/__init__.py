@@ -7,3 +7,4 @@ from .plsr import (Lwplsr, LwplsrPred, Plsr, coef, lwplsr, lwplsr_predict, query
 from .krr import Krr, Krrda, gridscorelb, krr, krr_, krr_coef, krr_predict, krrda, krrda_predict  # noqa: F401
 from .preproc import Savgk, detrend, detrend_, fdif, mavg, mavg_, mavg_runmean, savgk, savgol, savgol_, snv, snv_  # noqa: F401
 from .covsel import Covsel, Covselr, Mlr, covsel, covsel_, covselr, covselr_coef, covselr_predict  # noqa: F401
+from .pca import Pca, Pcr, pca_summary, pca_transform, pcaeigen, pcaeigen_, pcaeigenk, pcaeigenk_, pcasvd, pcasvd_, pcr, pcr_  # noqa: F401

@@ -350,7 +350,11 @@ def _model_vec(v):
 
 def transform(fm: Plsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = None):
     """src/plskern.jl:187-195: `cscale(X, xmeans, xscales) * R[:, 1:nlv]` (nlv clamped to the model's) — jch_transform.
-    A Dkplsr model: src/dkplsr.jl:133-137 (dkplsr_transform).  A Kplsr model: src/kplsr.jl:202-212 (kplsr_transform)."""
+    A Dkplsr model: src/dkplsr.jl:133-137 (dkplsr_transform).  A Kplsr model: src/kplsr.jl:202-212 (kplsr_transform).  A Pca model:
+    src/pcasvd.jl:110-115 (pca_transform).  A Pcr model has R = P and takes the Plsr path."""
+    if type(fm).__name__ == "Pca":
+        from .pca import pca_transform
+        return pca_transform(fm, X, nlv=nlv, ctx=ctx)
     if isinstance(fm, Dkplsr):
         return dkplsr_transform(fm, X, nlv=nlv, ctx=ctx)
     if isinstance(fm, Kplsr):
@@ -452,7 +456,11 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
 
 
 def summary(fm: Plsr, X, *, ctx: Optional[Context] = None):
-    """src/plskern.jl:246-260 — explained X-variance table as a dict of columns (nlv, var, pvar, cumpvar)."""
+    """src/plskern.jl:246-260 — explained X-variance table as a dict of columns (nlv, var, pvar, cumpvar).  A Pca model:
+    src/pcasvd.jl:123-146 (pca_summary)."""
+    if type(fm).__name__ == "Pca":
+        from .pca import pca_summary
+        return pca_summary(fm, X)
     X = ensure_mat(X)
     try:
         _addr_ld(X)

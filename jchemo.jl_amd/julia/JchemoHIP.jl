@@ -34,7 +34,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Dkplsr, dkplsr, dkplsr!, krbf, kpol, Kplsr, kplsr, kplsr!, Kpca, kpca,
        Krr, krr, krr!, gridscorelb, Krrda, krrda,
        snv, snv!, detrend, detrend!, savgol, savgol!, savgk, mavg, mavg!, mavg_runmean, fdif,
-       Covsel, Covselr, covsel, covsel!, covselr
+       Covsel, Covselr, covsel, covsel!, covselr,
+       Pca, Pcr, pcasvd, pcasvd!, pcaeigen, pcaeigen!, pcaeigenk, pcaeigenk!, pcr, pcr!, xtdx
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -1505,6 +1506,131 @@ function predict(object::Covselr, X; ctx = default_ctx())
     X = _in(X)
     s = object.sel.sel
     (pred = _affine(X[:, s], nothing, nothing, object.fm.B, vec(object.fm.int), ctx),)
+end
+
+# ---- PCA and PCR (src/pcasvd.jl, src/pcaeigen.jl, src/pcaeigenk.jl, src/pcr.jl) over jch_pca_fit (include/jchemo_hip.h; DESIGN.md §16): P and
+# sv^2 are the leading eigenpairs of G = Xs'D Xs, formed in one pass over the column-major X, from kpca's block subspace iteration.  Deviations:
+# the three fit names run one algorithm; sv and eig hold nlv values; `summary` does not read X; the `!` forms do not leave a centred X behind;
+# the iteration needs a gap behind the block (pure-noise data ends at eig_maxit with converged = false). ----------------------------------
+struct Pca                        # the reference's fields (src/pcasvd.jl:100), then what the eigen route knows
+    T
+    P::Matrix{Float64}
+    sv::Vector{Float64}
+    xmeans::Vector{Float64}
+    xscales::Vector{Float64}
+    weights
+    niter
+    conv
+    eig::Vector{Float64}
+    sstot::Float64
+    colvar::Vector{Float64}
+    resid::Vector{Float64}
+    converged::Bool
+end
+
+struct Pcr                        # src/pcr.jl:96; R = P and C = beta' have the shapes of a Plsr: transform, coef and predict are the generic ones
+    fm_pca
+    T
+    R::Matrix{Float64}
+    C::Matrix{Float64}
+    xmeans::Vector{Float64}
+    xscales::Vector{Float64}
+    ymeans::Vector{Float64}
+    yscales::Vector{Float64}
+    weights
+end
+_nlv_fit(object::Pcr) = size(object.R, 2)
+
+function _pca_fit(who, X, Y, weights, nlv, scal, eig_tol, eig_maxit, ctx)
+    nlv >= 1 || throw(ArgumentError("nlv = $nlv must be >= 1"))
+    eig_maxit >= 1 || throw(ArgumentError("eig_maxit = $eig_maxit must be >= 1"))
+    eig_tol > 0 || throw(ArgumentError("eig_tol = $eig_tol must be > 0"))
+    X = _in(X); n, p = size(X)
+    weights = _w(weights, X)
+    weights === nothing || length(weights) == n || throw(DimensionMismatch("weights has $(length(weights)) entries, X has $n rows"))
+    q = Y === nothing ? 0 : size(Y, 2)
+    Yd = Y === nothing ? _similar(X, 1, 1) : _colocate_mat(_in(Y), X)
+    q == 0 || size(Yd, 1) == n || throw(DimensionMismatch("X has $n rows, Y has $(size(Yd, 1))"))
+    a = min(nlv, n, p)                                                   # src/pcasvd.jl:82
+    T = _similar(X, n, a); wn = _similar(X, n)
+    P = zeros(p, a); sv = zeros(a); eig = zeros(a); res = zeros(a); xm = zeros(p); xs = zeros(p); cvar = zeros(p); ym = zeros(max(q, 1)); K = zeros(p, max(q, 1))
+    sst = Ref{Float64}(0.0); nit = Ref{Int32}(0); got = Ref{Int32}(0); cvg = Ref{Int32}(0)
+    GC.@preserve X weights Yd T wn check(ctx, ccall((:jch_pca_fit, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int32, Int32, Float64, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ref{Int32}, Ptr{Float64}, Ref{Int32}, Ref{Int32}),
+        ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights),
+        q == 0 ? Ptr{Float64}(C_NULL) : pointer(Yd), q, max(stride(Yd, 2), n), Int32(nlv), Int32(scal ? 1 : 0), Float64(eig_tol), Int32(eig_maxit),
+        pointer(T), P, sv, eig, xm, xs, pointer(wn), sst, cvar, ym, K, nit, res, got, cvg))
+    conv = cvg[] != 0
+    conv || @warn "$who: the subspace iteration did not converge in $(nit[]) iterations" maxresid = maximum(res) tol = eig_tol * eig[1]
+    (fm = Pca(T, P, sv, xm, xs, wn, Int(nit[]), conv, eig, sst[], cvar, res, conv), ymeans = ym[1:q], xtdy = K[:, 1:q])
+end
+
+"""`pcasvd(X, weights; nlv, scal = false)` — src/pcasvd.jl:73-101 through jch_pca_fit; X is only read.  `eig_tol`, `eig_maxit`: the subspace
+iteration's stopping rule; a fit that did not converge warns and returns what it has."""
+function pcasvd(X, weights = nothing; nlv, scal = false, ctx = default_ctx(), eig_tol = 1e-10, eig_maxit = 300)
+    _pca_fit("pcasvd", X, nothing, weights, nlv, scal, eig_tol, eig_maxit, ctx).fm
+end
+"`pcaeigen(X, weights; nlv, scal = false)` — src/pcaeigen.jl: the eigen-decomposition of X'DX, which is what every fit here runs."
+function pcaeigen(X, weights = nothing; nlv, scal = false, ctx = default_ctx(), eig_tol = 1e-10, eig_maxit = 300)
+    _pca_fit("pcaeigen", X, nothing, weights, nlv, scal, eig_tol, eig_maxit, ctx).fm
+end
+"`pcaeigenk(X, weights; nlv, scal = false)` — src/pcaeigenk.jl (the n x n route for n < p): the same T, P and sv from the one algorithm."
+function pcaeigenk(X, weights = nothing; nlv, scal = false, ctx = default_ctx(), eig_tol = 1e-10, eig_maxit = 300)
+    _pca_fit("pcaeigenk", X, nothing, weights, nlv, scal, eig_tol, eig_maxit, ctx).fm
+end
+# the reference's `!` forms leave the centred (scaled) X in their argument; the fit here never writes X: aliases
+const pcasvd! = pcasvd
+const pcaeigen! = pcaeigen
+const pcaeigenk! = pcaeigenk
+
+"`transform(object::Pca, X; nlv)` — src/pcasvd.jl:110-115: cscale(X, xmeans, xscales) * P[:, 1:nlv] (jch_affine_gemm)."
+function transform(object::Pca, X; nlv = nothing, ctx = default_ctx())
+    a = size(object.P, 2)
+    nlv = nlv === nothing ? a : min(nlv, a)
+    size(X, 2) == size(object.P, 1) || throw(DimensionMismatch("X has $(size(X, 2)) columns, the model has $(size(object.P, 1))"))
+    _affine(X, object.xmeans, object.xscales, nlv == a ? object.P : object.P[:, 1:nlv], nothing, ctx)
+end
+
+"""`summary(object::Pca, X)` — src/pcasvd.jl:123-146 from the stored quantities (X is only checked for its shape): with G = Xs'D Xs and
+G P = P diag(eig), sstot = trace(G), tt = eig, coord_var = P diag(sv), cor_circle = coord_var ./ colstd(Xs), contr_var from coord_var,
+contr_ind = D T.^2 ./ tt (where T lives)."""
+function Base.summary(object::Pca, X)
+    size(X) == (size(object.T, 1), size(object.P, 1)) || throw(DimensionMismatch("X is not the matrix the model was fitted on"))
+    a = size(object.P, 2)
+    tt = object.eig[1:a]
+    pvar = tt ./ object.sstot
+    explvarx = _table((lv = collect(1:a), var = tt, pvar = pvar, cumpvar = cumsum(pvar)))
+    contr_ind = object.weights .* object.T .^ 2 ./ _colocate_mat(reshape(tt, 1, a), object.T)
+    coord_var = object.P .* object.sv[1:a]'
+    cor_circle = coord_var ./ (sqrt.(object.colvar) ./ object.xscales)
+    cc = coord_var .^ 2
+    contr_var = cc ./ sum(cc, dims = 1)
+    (explvarx = explvarx, contr_ind = contr_ind, contr_var = contr_var, coord_var = coord_var, cor_circle = cor_circle)
+end
+
+"""`pcr(X, Y, weights; nlv, scal = false)` — src/pcr.jl:76-97: the PCA fit plus one pass Xs'D Yc over X; beta = diag(1 / sv^2) P' Xs'D Yc on
+the host.  `coef` and `predict` (one nlv or a range, 0 = intercept only) are the generic ones."""
+function pcr(X, Y, weights = nothing; nlv, scal = false, ctx = default_ctx(), eig_tol = 1e-10, eig_maxit = 300)
+    r = _pca_fit("pcr", X, Y, weights, nlv, scal, eig_tol, eig_maxit, ctx)
+    fm = r.fm
+    beta = (fm.P' * r.xtdy) ./ fm.eig
+    Pcr(fm, fm.T, fm.P, Matrix(beta'), fm.xmeans, fm.xscales, r.ymeans, ones(length(r.ymeans)), fm.weights)
+end
+const pcr! = pcr    # src/pcr.jl:82: X and Y are not written here
+
+"""`xtdx(X, weights)` — (G = (X - 1 mu')' D (X - 1 mu'), mu) as host arrays: jch_xtdx, one pass over the column-major X with the means and the
+weights applied in registers."""
+function xtdx(X, weights = nothing; ctx = default_ctx())
+    X = _in(X); n, p = size(X)
+    weights = _w(weights, X)
+    G = zeros(p, p); mu = zeros(p)
+    GC.@preserve X weights check(ctx, ccall((:jch_xtdx, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights),
+        Ptr{Float64}(C_NULL), p, Ptr{Float64}(C_NULL), G, mu))
+    (G = G, mu = mu)
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
