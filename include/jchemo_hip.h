@@ -531,6 +531,17 @@ JCH_API int32_t jch_pca_fit(jch_ctx *ctx, int32_t loc, const double *X, int64_t 
                             double *xscales, double *weights_norm, double *sstot, double *colvar, double *ymeans, double *xtdy, int32_t *niter,
                             double *resid, int32_t *nlv_out, int32_t *converged);
 
+/* ---- outlier distances (src/occsd.jl, src/occod.jl, src/occsdod.jl) ------------------------------------------------------------
+ * jch_row_resid_ss -- out[i] = sum_j ( X[i, j] - shift[j] - sum_{l < k} Z[i, l] B[j, l] )^2: the row sums of squares of the rank-k residual
+ * E = (X - 1 shift') - Z B' without forming E (the reference's `sum(E .* E, dims = 2)` over `xresid`, src/occod.jl:48-49, with shift = xmeans, Z = the
+ * scores and B = diag(xscales) P[:, 1:k]).  X m x p (ldx >= m), Z m x k (ldz >= m) and out (m) [loc], X and Z read only; shift (p, NULL = zeros) and
+ * B (p x k, ldb >= p) HOST.  k = 0 is valid (Z and B may then be NULL): the centred row sums of squares.  Any m, p, k: coefficients that do not fit in
+ * LDS are read from L2, more than 64 score columns are walked in chunks.  Rows >= m and columns >= p are never read.  Every sum has a fixed order and
+ * no atomics: two runs give identical bits, and so do a host and a device X or Z and an aligned and an unaligned one.  A NaN at X[i, j] or Z[i, l]
+ * reaches out[i] only.  One rank only. */
+JCH_API int32_t jch_row_resid_ss(jch_ctx *ctx, int32_t loc, const double *X, int64_t m, int64_t p, int64_t ldx, const double *shift, const double *Z,
+                                 int64_t k, int64_t ldz, const double *B, int64_t ldb, double *out);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in

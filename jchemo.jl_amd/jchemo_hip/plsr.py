@@ -427,10 +427,14 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
     """src/plskern.jl:226-238: a collection of nlv becomes the contiguous range max(0,min):min(a,max); one
     value -> matrix, several -> list of matrices.  All values are computed in ONE pass over X.
     `rank` / `world` (kNN-LWPLSR only): split the queries over `world` replicas, see lwplsr_predict.
-    A Covselr model: src/covselr.jl:61-64 (covselr_predict)."""
+    A Covselr model: src/covselr.jl:61-64 (covselr_predict).  An Occsd, Occod or Occsdod model: src/occsd.jl:153-164, src/occod.jl:65-75,
+    src/occsdod.jl:60-74 (occ_predict)."""
     if type(fm).__name__ == "Covselr":
         from .covsel import covselr_predict
         return covselr_predict(fm, X, ctx=ctx)
+    if type(fm).__name__ in ("Occsd", "Occod", "Occsdod"):
+        from .occ import occ_predict
+        return occ_predict(fm, X, ctx=ctx)
     if isinstance(fm, Lwplsr):
         return lwplsr_predict(fm, X, nlv=nlv, ctx=ctx, rank=rank, world=world)
     if isinstance(fm, Plsrda):
@@ -488,9 +492,18 @@ def summary(fm: Plsr, X, *, ctx: Optional[Context] = None):
     return dict(nlv=np.arange(1, nlv + 1), var=tt_adj / n, pvar=pvar, cumpvar=np.cumsum(pvar))
 
 
+def _xmodel(fm):
+    """The record `xfit` / `xresid` read T, P, xmeans and xscales from, and its p x a matrix R with T = cscale(X) R (src/xfit.jl:37-40):
+    a Pcr stands for its fm_pca, and a Pca has R = P."""
+    if type(fm).__name__ == "Pcr":
+        fm = fm.fm_pca
+    return fm, (fm.P if type(fm).__name__ == "Pca" else fm.R)
+
+
 def xfit(fm: Plsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = None):
-    """`xfit(object, X; nlv)` — src/xfit.jl:37-56: X reconstructed from nlv LVs in the original scale,
+    """`xfit(object::Union{Pca, Pcr, Plsr}, X; nlv)` — src/xfit.jl:37-56: X reconstructed from nlv LVs in the original scale,
     (cscale(X) R_k) (P_k' diag(xscales)) + xmeans: the scores pass over X, then a GEMM on the m x nlv scores."""
+    fm, _ = _xmodel(fm)
     k = _nlv_arg(fm, nlv)
     p = fm.P.shape[0]
     if k == 0:   # the column means (src/xfit.jl:41-45); an m x p broadcast through the same device primitive
@@ -500,11 +513,12 @@ def xfit(fm: Plsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = Non
 
 
 def xresid(fm: Plsr, X, *, nlv: Optional[int] = None, ctx: Optional[Context] = None):
-    """`xresid(object, X; nlv)` — src/xfit.jl:86-93: E = X - xfit(X) = cscale(X) (I - R_k P_k') diag(xscales),
+    """`xresid(object::Union{Pca, Pcr, Plsr}, X; nlv)` — src/xfit.jl:86-93: E = X - xfit(X) = cscale(X) (I - R_k P_k') diag(xscales),
     one p x p device GEMM on X (no n x p temporary on the host)."""
+    fm, R = _xmodel(fm)
     k = _nlv_arg(fm, nlv)
     p = fm.P.shape[0]
-    M = np.eye(p) - fm.R[:, :k] @ fm.P[:, :k].T
+    M = np.eye(p) - R[:, :k] @ fm.P[:, :k].T
     return _affine(X, fm.xmeans, fm.xscales, M * fm.xscales[None, :], None, ctx)
 
 

@@ -35,7 +35,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Krr, krr, krr!, gridscorelb, Krrda, krrda,
        snv, snv!, detrend, detrend!, savgol, savgol!, savgk, mavg, mavg!, mavg_runmean, fdif,
        Covsel, Covselr, covsel, covsel!, covselr,
-       Pca, Pcr, pcasvd, pcasvd!, pcaeigen, pcaeigen!, pcaeigenk, pcaeigenk!, pcr, pcr!, xtdx
+       Pca, Pcr, pcasvd, pcasvd!, pcaeigen, pcaeigen!, pcaeigenk, pcaeigenk!, pcr, pcr!, xtdx,
+       Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -839,17 +840,21 @@ function vip(object, Y; nlv = nothing, ctx = default_ctx())
     Aimp = vec(sum(rdd' .* W2, dims = 2))
     (imp = sqrt.(Aimp ./ (sum(rdd) / p)), W2 = W2, rdd = rdd)
 end
-"`xfit(object, X; nlv)` — src/xfit.jl:37-56: the scores pass over X, then a GEMM on the m x nlv scores, original scale."
+# the record xfit / xresid read P, xmeans and xscales from (a Pcr stands for its fm_pca, src/xfit.jl:40) and its R with T = cscale(X) R (a Pca: P)
+_xmodel(object) = hasproperty(object, :fm_pca) ? _xmodel(object.fm_pca) : (object, hasproperty(object, :R) ? object.R : object.P)
+"`xfit(object::Union{Pca, Pcr, Plsr}, X; nlv)` — src/xfit.jl:37-56: the scores pass over X, then a GEMM on the m x nlv scores, original scale."
 function xfit(object, X; nlv = nothing, ctx = default_ctx())
+    object, R = _xmodel(object)
     a = _nlv_fit(object); k = nlv === nothing ? a : min(nlv, a); p = size(object.P, 1)
     k == 0 && return _affine(X, nothing, nothing, zeros(p, p), object.xmeans, ctx)
-    Tq = transform(object, X; nlv = k, ctx = ctx)
+    Tq = _affine(X, object.xmeans, object.xscales, R[:, 1:k], nothing, ctx)
     _affine(Tq, nothing, nothing, Matrix((object.P[:, 1:k] .* object.xscales)'), object.xmeans, ctx)
 end
-"`xresid(object, X; nlv)` — src/xfit.jl:86-93: E = X - xfit(X) = cscale(X) (I - R_k P_k') diag(xscales), one device GEMM."
+"`xresid(object::Union{Pca, Pcr, Plsr}, X; nlv)` — src/xfit.jl:86-93: E = X - xfit(X) = cscale(X) (I - R_k P_k') diag(xscales), one device GEMM."
 function xresid(object, X; nlv = nothing, ctx = default_ctx())
+    object, R = _xmodel(object)
     a = _nlv_fit(object); k = nlv === nothing ? a : min(nlv, a); p = size(object.P, 1)
-    M = Matrix{Float64}(I, p, p) - object.R[:, 1:k] * object.P[:, 1:k]'
+    M = Matrix{Float64}(I, p, p) - R[:, 1:k] * object.P[:, 1:k]'
     _affine(X, object.xmeans, object.xscales, M .* object.xscales', nothing, ctx)
 end
 
@@ -1631,6 +1636,143 @@ function xtdx(X, weights = nothing; ctx = default_ctx())
         ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights),
         Ptr{Float64}(C_NULL), p, Ptr{Float64}(C_NULL), G, mu))
     (G = G, mu = mu)
+end
+
+# ---- outlier distances (src/occsd.jl, src/occod.jl, src/occsdod.jl; DESIGN.md 17): no m x p residual is formed ---------------------
+struct Occsd                      # src/occsd.jl:1-8 (e_cdf: the sorted training d), then Lc with Sinv = Lc Lc'
+    d
+    fm
+    Sinv::Matrix{Float64}
+    e_cdf
+    cutoff::Float64
+    nlv::Int
+    Lc::Matrix{Float64}
+end
+struct Occod                      # src/occod.jl:1-7
+    d
+    fm
+    e_cdf
+    cutoff::Float64
+    nlv::Int
+end
+struct Occsdod                    # src/occsdod.jl:1-5
+    d
+    fm_sd
+    fm_od
+end
+
+"""`row_resid_ss(X, shift, Z, B)` — out[i] = sum_j (X[i, j] - shift[j] - sum_l Z[i, l] B[j, l])^2 where X lives (jch_row_resid_ss); shift and B
+on the host; `Z = nothing`: k = 0, the centred row sums of squares."""
+function row_resid_ss(X, shift = nothing, Z = nothing, B = nothing; ctx = default_ctx())
+    X = _in(X); m, p = size(X)
+    k = Z === nothing ? 0 : size(Z, 2)
+    out = _similar(X, m)
+    shift = shift === nothing ? nothing : Vector{Float64}(vec(shift))
+    Bm = k == 0 ? zeros(1, 1) : Matrix{Float64}(B)
+    k == 0 || size(Bm) == (p, k) || throw(DimensionMismatch("B is not $p x $k"))
+    Zm = k == 0 ? X : Z
+    GC.@preserve X Zm out shift begin
+        check(ctx, ccall((:jch_row_resid_ss, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                          Ptr{Float64}),
+                         ctx.h, _loc(X), pointer(X), m, p, max(stride(X, 2), m), shift === nothing ? Ptr{Float64}(C_NULL) : pointer(shift),
+                         k == 0 ? Ptr{Float64}(C_NULL) : pointer(Zm), k, k == 0 ? 0 : max(stride(Zm, 2), m), Bm, p, pointer(out)))
+    end
+    out
+end
+
+const _MAD_CONSTANT = 1.4826022185056018      # StatsBase 0.33 / 0.34 `mad(x)`: normalize = true is the default (DESIGN.md 6)
+_median_sorted(s) = (n = length(s); isodd(n) ? s[(n + 1) >> 1] : (s[n >> 1] + s[(n >> 1) + 1]) / 2)
+function _quantile_sorted(s, q)   # Statistics._quantile with alpha = beta = 1 (type 7)
+    n = length(s); aleph = n * q + (1 - q)
+    j = clamp(trunc(Int, aleph), 1, max(n - 1, 1)); g = clamp(aleph - j, 0, 1)
+    a = s[j]; b = s[min(j + 1, n)]
+    a + g * (b - a)
+end
+function _occ_cutoff(s, typc, cri, alpha)      # s: the sorted d on the host
+    typc == "mad" && (med = _median_sorted(s); return med + cri * _MAD_CONSTANT * _median_sorted(sort(abs.(s .- med))))
+    typc == "q" && return _quantile_sorted(s, 1 - alpha)
+    throw(ArgumentError("typc = $typc must be \"mad\" or \"q\""))
+end
+# pval(e_cdf, q) = 1 - #(d <= q) / n by a right-sided search in the sorted training d; the m values go through the host
+_occ_pval(e_cdf, d) = (s = Array(e_cdf); _colocate([1 - searchsortedlast(s, v) / length(s) for v in Array(d)], d))
+_occ_pred(dstand) = reshape(Int64.(Array(dstand) .> 1), :, 1)
+_occ_loadings(object) = hasproperty(object, :R) ? object.R : object.P
+
+"""`occsd(object; nlv, typc = "mad", cri = 3, alpha = .025)` — src/occsd.jl:129-145 for a Pca, Kpca or Plsr record (this module's or the reference's:
+only the fields are read): S = cov(T[:, 1:nlv], corrected = false) (jch_weighted_cov), Sinv = Lc Lc' by a host Cholesky, d2 = |Lc' t|^2 from
+U = T Lc (jch_affine_gemm) and jch_row_resid_ss with k = 0.  `kwargs` are not taken (the reference passes them to a `kde` it never calls)."""
+function occsd(object; nlv = nothing, typc = "mad", cri = 3, alpha = .025, ctx = default_ctx())
+    a = size(object.T, 2)
+    k = nlv === nothing ? a : min(nlv, a)
+    k >= 1 || throw(ArgumentError("nlv = $nlv must be >= 1"))
+    T = k == a ? object.T : object.T[:, 1:k]      # a copy, as in `vip`: a view of a host Matrix is no Array, and `_loc` would take it for device memory
+    S = _cov(T, ctx)
+    Lc = Matrix(inv(cholesky(Symmetric(S)).L)')
+    d2 = row_resid_ss(_affine(T, nothing, nothing, Lc, nothing, ctx); ctx = ctx)
+    d = sqrt.(d2)
+    e_cdf = sort(Array(d))
+    cutoff = _occ_cutoff(e_cdf, typc, cri, alpha)
+    tab = _table((d = d, dstand = d ./ cutoff, pval = _occ_pval(e_cdf, d), gh = d2 ./ k))
+    Occsd(tab, object, Lc * Lc', e_cdf, cutoff, k, Lc)
+end
+
+function _occ_sd_cols(object::Occsd, X, ctx)
+    fm = object.fm; k = object.nlv
+    U = hasproperty(fm, :vtot) ? _affine(transform(fm, X; nlv = k, ctx = ctx), nothing, nothing, object.Lc, nothing, ctx) :
+        _affine(X, fm.xmeans, fm.xscales, _occ_loadings(fm)[:, 1:k] * object.Lc, nothing, ctx)
+    d2 = row_resid_ss(U; ctx = ctx)
+    d = sqrt.(d2)
+    (d = d, dstand = d ./ object.cutoff, pval = _occ_pval(object.e_cdf, d), gh = d2 ./ k)
+end
+"`predict(object::Occsd, X)` — src/occsd.jl:153-164: Lc folded into the loadings, one pass over X, then jch_row_resid_ss."
+function predict(object::Occsd, X; ctx = default_ctx())
+    cols = _occ_sd_cols(object, X, ctx)
+    (pred = _occ_pred(cols.dstand), d = _table(cols))
+end
+
+function _occ_od2(fm, X, k, ctx)
+    X = _in(X)
+    k == 0 && return row_resid_ss(X, fm.xmeans; ctx = ctx)
+    Tq = _affine(X, fm.xmeans, fm.xscales, _occ_loadings(fm)[:, 1:k], nothing, ctx)      # transform(fm, X; nlv = k): R of a Plsr, P of a Pca
+    row_resid_ss(X, fm.xmeans, Tq, fm.P[:, 1:k] .* fm.xscales; ctx = ctx)
+end
+"""`occod(object, X; nlv, typc = "mad", cri = 3, alpha = .025)` — src/occod.jl:43-57: T = transform(object, X; nlv), then
+jch_row_resid_ss with shift = xmeans, Z = T, B = diag(xscales) P[:, 1:nlv] (src/xfit.jl:48-51); nlv = 0 is k = 0.  A Pca or Plsr record."""
+function occod(object, X; nlv = nothing, typc = "mad", cri = 3, alpha = .025, ctx = default_ctx())
+    hasproperty(object, :vtot) && throw(ArgumentError("occod takes a Pca or Plsr model (src/occod.jl:43)"))
+    a = size(object.T, 2)
+    k = nlv === nothing ? a : min(nlv, a)
+    k >= 0 || throw(ArgumentError("nlv = $nlv must be >= 0"))
+    d = sqrt.(_occ_od2(object, X, k, ctx))
+    e_cdf = sort(Array(d))
+    cutoff = _occ_cutoff(e_cdf, typc, cri, alpha)
+    Occod(_table((d = d, dstand = d ./ cutoff, pval = _occ_pval(e_cdf, d))), object, e_cdf, cutoff, k)
+end
+function _occ_od_cols(object::Occod, X, ctx)
+    d = sqrt.(_occ_od2(object.fm, X, object.nlv, ctx))
+    (d = d, dstand = d ./ object.cutoff, pval = _occ_pval(object.e_cdf, d))
+end
+"`predict(object::Occod, X)` — src/occod.jl:65-75."
+function predict(object::Occod, X; ctx = default_ctx())
+    cols = _occ_od_cols(object, X, ctx)
+    (pred = _occ_pred(cols.dstand), d = _table(cols))
+end
+
+_occ_hcat(sd, od) = merge(NamedTuple{Tuple(Symbol(c, "_sd") for c in keys(sd))}(values(sd)), NamedTuple{Tuple(Symbol(c, "_od") for c in keys(od))}(values(od)),
+                          (dstand = sqrt.(sd.dstand .* od.dstand),))
+_occ_cols(tab) = tab isa NamedTuple ? tab : NamedTuple{Tuple(Symbol.(names(tab)))}(Tuple(tab[!, c] for c in names(tab)))
+"""`occsdod(object, X; nlv_sd, nlv_od, typc = "mad", cri = 3, alpha = .025)` — src/occsdod.jl:35-52; `fm_sd.d` is not renamed in
+place."""
+function occsdod(object, X; nlv_sd = nothing, nlv_od = nothing, typc = "mad", cri = 3, alpha = .025, ctx = default_ctx())
+    fm_sd = occsd(object; nlv = nlv_sd, typc = typc, cri = cri, alpha = alpha, ctx = ctx)
+    fm_od = occod(object, X; nlv = nlv_od, typc = typc, cri = cri, alpha = alpha, ctx = ctx)
+    Occsdod(_table(_occ_hcat(_occ_cols(fm_sd.d), _occ_cols(fm_od.d))), fm_sd, fm_od)
+end
+"`predict(object::Occsdod, X)` — src/occsdod.jl:60-74."
+function predict(object::Occsdod, X; ctx = default_ctx())
+    cols = _occ_hcat(_occ_sd_cols(object.fm_sd, X, ctx), _occ_od_cols(object.fm_od, X, ctx))
+    (pred = _occ_pred(cols.dstand), d = _table(cols))
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
