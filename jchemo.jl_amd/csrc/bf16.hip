@@ -908,13 +908,15 @@ __device__ __forceinline__ constexpr int bf_rowsum_lane(int rr)
     return 16 * (((rr & 3) == 1) ? 2 : ((rr & 3) == 2) ? 1 : (rr & 3)) + (R == 8 ? 8 * (rr >> 2) : 0);
 }
 
-template <int KC, int R>
+// TSTAGE (JCH_SWEEP_TSTAGE, `tcap` > 0): the T column goes through per-wave LDS rings of `tcap` row groups, written out with all 64
+// lanes when a ring is full and once behind the wave's last group — as in k_sweep_v2 (sweep.hip), the scores staged as doubles.
+template <int KC, int R, bool TSTAGE = false>
 __global__ __launch_bounds__(256) void k_sweep_bf16_v2(const bf16_t *__restrict__ Xr, int64_t n, int ldr, const double *__restrict__ dw,
                                                        const double *__restrict__ rvec, const double *__restrict__ mom,
                                                        const double *__restrict__ scl, int p,
-                                                       double *__restrict__ tcol, double *__restrict__ part, int ldpart)
+                                                       double *__restrict__ tcol, double *__restrict__ part, int ldpart, int tcap = 0)
 {
-    extern __shared__ __attribute__((aligned(16))) double red[];  // [4][KC*512] + [8]
+    extern __shared__ __attribute__((aligned(16))) double red[];  // [4][KC*512] + [8] (+ TSTAGE: [4][tcap][R] score rings)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int coff[KC];   // element offset of this lane's 8 columns in chunk k, clamped to the row's last 16 bytes
 #pragma unroll
@@ -960,6 +962,26 @@ __global__ __launch_bounds__(256) void k_sweep_bf16_v2(const bf16_t *__restrict_
     }
     const float off = (float)jch_wave_sum(offd);
     double tt = 0.0, st = 0.0;
+    // TSTAGE: this wave's ring, the row groups it holds (slot i = the wave's iteration tdone + i) and those already written out
+    double *tring = red + 4 * KC * 512 + 8 + (TSTAGE ? __builtin_amdgcn_readfirstlane(wv) * tcap * R : 0);
+    int tfill = 0;
+    int64_t tdone = 0;
+    auto tflush = [&] {   // all 64 lanes: lane l takes slot s + l / R, row l % R
+        const int nf = __builtin_amdgcn_readfirstlane(tfill);
+        const int64_t gfirst = (int64_t)blockIdx.x * 4 + wv;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        for (int s = 0; s < nf; s += 64 / R) {
+            const int slot = s + lane / R;
+            if (slot < nf) {   // (guards the LDS read as well)
+                const int64_t row = (gfirst + (tdone + slot) * gstride) * R + lane % R;
+                const double v = tring[s * R + lane];
+                if (row < n) tcol[row] = v;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        tdone += nf;
+        tfill = 0;
+    };
     auto process = [&](v4u32 (&x)[R][KC], double (&dv)[R], int64_t gg) {
         const int64_t row0 = gg * R;
         float sp[R];
@@ -993,7 +1015,12 @@ __global__ __launch_bounds__(256) void k_sweep_bf16_v2(const bf16_t *__restrict_
         {
             const int src = 16 * (((lane & 3) == 1) ? 2 : ((lane & 3) == 2) ? 1 : (lane & 3)) + (R == 8 ? 8 * ((lane >> 2) & 1) : 0);
             const float tl = __shfl(h, src, 64);
-            if (lane < R && row0 + lane < n) tcol[row0 + lane] = (double)tl;
+            if constexpr (TSTAGE) {
+                if (lane < R) tring[tfill * R + lane] = (double)tl;
+                if (__builtin_amdgcn_readfirstlane(++tfill) == tcap) tflush();   // wave-uniform
+            } else {
+                if (lane < R && row0 + lane < n) tcol[row0 + lane] = (double)tl;
+            }
         }
     };
     while (g < ngroups) {
@@ -1007,6 +1034,7 @@ __global__ __launch_bounds__(256) void k_sweep_bf16_v2(const bf16_t *__restrict_
             }
         }
     }
+    if constexpr (TSTAGE) tflush();   // what is left in the ring
     double *zred = red;                 // [4][KC*512]
     double *tred = red + 4 * KC * 512;  // [8]
 #pragma unroll
@@ -1074,25 +1102,37 @@ static int32_t launch_sweep_bf16_v2_t(jch_ctx *ctx, const bf16_t *Xr, int64_t n,
                                       const double *mom, const double *scl, int p, double *tcol, double *zt8, int ldzb, int *nslice,
                                       jch_part_view *pv = nullptr /*split small-state path on one rank / with the per-block inbox: leave the block partials unreduced*/)
 {
-    const size_t lds = sizeof(double) * (4 * KC * 512 + 8);
-    static int bpc = 0;
+    const size_t lds0 = sizeof(double) * (4 * KC * 512 + 8);
+    static_assert(sizeof(double) * (4 * KC * 512 + 8) < 64 * 1024, "the combine area and a score ring share 64 KB");
+    // JCH_SWEEP_TSTAGE (see k_sweep_bf16_v2): a ring is at most what keeps the block within 64 KB of LDS (two blocks per CU still fit)
+    constexpr int TCAP_MAX = (int)((64 * 1024 - sizeof(double) * (4 * KC * 512 + 8)) / (sizeof(double) * 4 * R));
+    const int tstage = ctx->sweep_tstage;
+    const bool staged = tstage > 0 || (tstage < 0 && jch_sweep_bf16_tstage_default(n, ctx->cus));
+    static int bpc2[2] = {0, 0};   // [staged]: the occupancy query sees the LDS of the launch (the largest ring for the staged kernel)
     static jch_per_device_once occ_once;
     if (!occ_once.done(ctx->device)) {
         int nblk = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_bf16_v2<KC, R>, 256, lds);
-        bpc = (e == hipSuccess && nblk > 0) ? nblk : 2;
-        if (lds > 64 * 1024)
-            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_sweep_bf16_v2<KC, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_bf16_v2<KC, R>, 256, lds0);
+        bpc2[0] = (e == hipSuccess && nblk > 0) ? nblk : 2;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_bf16_v2<KC, R, true>, 256, lds0 + sizeof(double) * 4 * TCAP_MAX * R);
+        bpc2[1] = (e == hipSuccess && nblk > 0) ? nblk : 2;
         occ_once.mark(ctx->device);
     }
+    const int bpc = bpc2[staged];
     const int64_t ngroups = (n + R - 1) / R;
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((ngroups + 3) / 4, (int64_t)ctx->cus * bpc));
     const int m = ldr_b + 2, ldpart = (m + 7) & ~7;
     JCH_TRY(jch_reserve(ctx, ctx->part, sizeof(double) * (size_t)nb * ldpart));
     double *part = (double *)ctx->part.ptr;
+    int tcap = 0;   // every row group of the wave with the most of them (one flush, behind the last), or the switch's, or the 64 KB's
+    if (staged) tcap = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(tstage > 0 ? tstage : TCAP_MAX, TCAP_MAX), (ngroups + (int64_t)nb * 4 - 1) / ((int64_t)nb * 4)));
+    const size_t lds = lds0 + sizeof(double) * 4 * (size_t)tcap * R;
     const bool timed = jch_prof_sample(ctx);
     if (timed) (void)jch_ev(ctx);
-    hipLaunchKernelGGL((k_sweep_bf16_v2<KC, R>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr_b, d, rvec, mom, scl, p, tcol, part, ldpart);
+    if (tcap > 0)
+        hipLaunchKernelGGL((k_sweep_bf16_v2<KC, R, true>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr_b, d, rvec, mom, scl, p, tcol, part, ldpart, tcap);
+    else
+        hipLaunchKernelGGL((k_sweep_bf16_v2<KC, R>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr_b, d, rvec, mom, scl, p, tcol, part, ldpart, 0);
     if (timed) (void)jch_ev(ctx);
     if (pv) { pv->part = part; pv->nb = nb; pv->ldpart = ldpart; *nslice = 1; JCH_HIP(ctx, hipGetLastError()); return JCH_OK; }
     JCH_TRY(jch_launch_reduce_part8(ctx, part, nb, ldpart, m, zt8, ldzb, nslice));

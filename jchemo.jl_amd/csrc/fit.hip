@@ -226,6 +226,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     ctx->sweep_alt = jch_knob("JCH_SWEEP_ALT", 0);
     ctx->sweep_fused_reduce = jch_knob("JCH_SWEEP_FUSED_REDUCE", 0) == 1;
     ctx->sweep_resident_mb = jch_knob("JCH_SWEEP_RESIDENT_MB", -1);
+    ctx->sweep_tstage = jch_knob("JCH_SWEEP_TSTAGE", -1);
     // JCH_HOST_TIMING=1: host-side timeline of a fit on host arrays (stderr): where the wall time of the secondary metric goes
     const bool host_timing = jch_knob_set("JCH_HOST_TIMING");
     auto now_ms = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };

@@ -55,6 +55,12 @@ struct jch_p2p {   // P2P inbox transport (p2p.hip)
 // T column, the weights and the small state between two sweeps).
 constexpr int JCH_INFINITY_CACHE_MIB = 256;
 constexpr int JCH_RESIDENT_DEFAULT_MIB = 128;
+// Where the plskern sweeps stage the T column in LDS when JCH_SWEEP_TSTAGE is unset (k_sweep_v2 / k_sweep_bf16_v2): per kernel and
+// shard size, wherever the A/B against the direct store met the bar of DESIGN.md §4 (sweeps of a fit down by more than 3 x the parent's
+// run-to-run spread).  500-column Float64 rows from 3900 rows per CU on (1e6 rows on one MI355X: 14.21 -> 13.89 ms per 25 sweeps); 500 k
+// rows and less showed nothing, the bf16 sweep gained 0.26 ms of 4.19 at 1e6 rows beside a parent spread of 0.14 ms: direct stores.
+inline bool jch_sweep_tstage_default(int kc, int64_t n, int cus) { return kc == 4 && n >= (int64_t)3900 * cus; }
+inline bool jch_sweep_bf16_tstage_default(int64_t n, int cus) { (void)n; (void)cus; return false; }
 
 struct jch_ctx {
     int device = 0;
@@ -79,6 +85,7 @@ struct jch_ctx {
     int sweep_alt = 0;                 // JCH_SWEEP_ALT and JCH_SWEEP_FUSED_REDUCE=1 as read when the current fit started
     bool sweep_fused_reduce = false;
     int sweep_resident_mb = -1;        // JCH_SWEEP_RESIDENT_MB, read with them: MiB of the working copy the sweep keeps in the Infinity Cache (< 0: by shape)
+    int sweep_tstage = -1;             // JCH_SWEEP_TSTAGE, read with them: row groups per wave of the T column's LDS ring (0: direct stores; < 0: by shape)
     jch_buf gram, xr, yr, xstage, ystage, wstage, tbuf, dnorm, part, kpart, small, colpart, gemm_b, gemm_out, xq, tickets, qz, lw_work, lw_xrm, lvws, lw_flags, lw_screen;
     jch_buf kg_ws, dk_x, dk_y, dk_k, dk_q, dk_o, dk_s;   // Gram kernel workspace (kgram.hip), dkplsr staging (dkplsr.hip)
     jch_buf kp_ws;   // kplsr panels and small state (kplsr.hip)

@@ -215,14 +215,19 @@ __device__ __forceinline__ void jch_slice_sum_by_last_block(const double *__rest
 // copy stays in the cache from sweep to sweep while the rest streams past it, its hits served beside the HBM stream and not in
 // front of it.  The choice is wave-uniform and fixed for the launch: one scalar branch selects between two copies of the row
 // loop.  Which wave reads which rows, and every order of summation, are those of the NT kernel: the same bits come out.
-template <int KC, int R, int NBUF, bool NT = true, bool MIX = false>
+// TSTAGE (JCH_SWEEP_TSTAGE, `tcap` > 0): the T column does not leave as one 64-byte store per row group between the loads.  Every wave
+// keeps its scores in a private LDS ring of `tcap` row groups (behind the combine area: [4][tcap][R] doubles) and writes the ring out
+// with all 64 lanes — 64 / R row groups per store instruction — when it is full and once behind its last group.  No block barrier: a
+// wave reads back only what it wrote itself, and the LDS serves one wave's accesses in order.  The stored values are the registers
+// the direct store writes, to the same addresses: the same bits.  TSTAGE = false is the direct store.
+template <int KC, int R, int NBUF, bool NT = true, bool MIX = false, bool TSTAGE = false>
 __global__ __launch_bounds__(256) void k_sweep_v2(const double *__restrict__ Xr, int64_t n, int ldr,
                                                   const double *__restrict__ dw, const double *__restrict__ rvec,
                                                   double *__restrict__ tcol, double *__restrict__ part, int ldpart,
                                                   const double *__restrict__ mu, int *__restrict__ tickets,
-                                                  double *__restrict__ zt, int ldz, int nslice, int rev = 0, int nres = 0)
+                                                  double *__restrict__ zt, int ldz, int nslice, int rev = 0, int nres = 0, int tcap = 0)
 {
-    extern __shared__ __attribute__((aligned(16))) double red[];  // [nw][KC*128] + [16] tt, st
+    extern __shared__ __attribute__((aligned(16))) double red[];  // [nw][KC*128] + [16] tt, st (+ TSTAGE: [nw][tcap][R] score rings)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
     v2f64 rf[KC], zp[KC];
     int coff[KC];   // element offset of this lane's pair in chunk k (clamped to the row's last pair)
@@ -252,6 +257,26 @@ __global__ __launch_bounds__(256) void k_sweep_v2(const double *__restrict__ Xr,
         }
     };
     double tt = 0.0, st = 0.0, off = 0.0;
+    // TSTAGE: this wave's ring, the row groups it holds (`tfill`, slot i = the wave's iteration tdone + i) and those already written out
+    double *tring = red + nw * KC * 128 + 16 + (TSTAGE ? __builtin_amdgcn_readfirstlane(wv) * tcap * R : 0);
+    int tfill = 0;
+    int64_t tdone = 0;
+    auto tflush = [&] {   // all 64 lanes: lane l takes slot s + l / R, row l % R (consecutive lanes, consecutive LDS words)
+        const int nf = __builtin_amdgcn_readfirstlane(tfill);
+        const int64_t gfirst = (int64_t)blockIdx.x * nw + wv;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        for (int s = 0; s < nf; s += 64 / R) {
+            const int slot = s + lane / R;
+            if (slot < nf) {   // (guards the LDS read as well: the lanes past the last filled slot would read another wave's ring)
+                const int64_t row = (gbase + gsign * (gfirst + (tdone + slot) * gstride)) * R + lane % R;
+                const double v = tring[s * R + lane];
+                if (row < n) tcol[row] = v;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        tdone += nf;
+        tfill = 0;
+    };
     auto coefficients = [&] {
 #pragma unroll
         for (int k = 0; k < KC; ++k) rf[k] = 2 * lane + 128 * k < ldr ? *reinterpret_cast<const v2f64 *>(rvec + 2 * lane + 128 * k) : v2f64{0.0, 0.0};
@@ -292,7 +317,12 @@ __global__ __launch_bounds__(256) void k_sweep_v2(const double *__restrict__ Xr,
         {
             const int src = 16 * (((lane & 3) == 1) ? 2 : ((lane & 3) == 2) ? 1 : (lane & 3)) + (R == 8 ? 8 * ((lane >> 2) & 1) : 0);
             const double tl = __shfl(h, src, 64);
-            if (lane < R && row0 + lane < n) tcol[row0 + lane] = tl;
+            if constexpr (TSTAGE) {
+                if (lane < R) tring[tfill * R + lane] = tl;
+                if (__builtin_amdgcn_readfirstlane(++tfill) == tcap) tflush();   // wave-uniform
+            } else {
+                if (lane < R && row0 + lane < n) tcol[row0 + lane] = tl;
+            }
         }
     };
     auto stream = [&](auto nt) {   // this wave's row groups, all with one load policy
@@ -326,6 +356,7 @@ __global__ __launch_bounds__(256) void k_sweep_v2(const double *__restrict__ Xr,
     } else {
         stream(std::integral_constant<bool, NT>{});
     }
+    if constexpr (TSTAGE) tflush();   // what is left in the ring (nothing in a wave without row groups)
     // ---- combine the waves of the block in wave order, then one partial row per block
     double *zred = red;                     // [nw][KC*128]
     double *tred = red + nw * KC * 128;     // [16]
@@ -583,15 +614,28 @@ static int32_t launch_sweep_v2_t(jch_ctx *ctx, const double *Xr, int64_t n, int 
                                  jch_part_view *pv)
 {
     const int64_t ngroups = (n + R - 1) / R;
-    const size_t lds = sizeof(double) * (4 * KC * 128 + 16);
-    static int bpc = 0;
+    const size_t lds0 = sizeof(double) * (4 * KC * 128 + 16);
+    // JCH_SWEEP_TSTAGE: the T column through per-wave LDS rings (see k_sweep_v2).  Only the two wide instantiations have the staged
+    // copies (the narrow sweeps run several blocks per CU on the LDS they have); the JCH_SWEEP_ALT kernels keep the direct store.
+    // A ring is at most what keeps the block within 64 KB of LDS.  Unset: TSTAGE_DEFAULT (the measured choice by shape).
+    constexpr bool WIDE = KC == 4 || KC == 8;
+    constexpr int TCAP_MAX = WIDE ? (int)((64 * 1024 - sizeof(double) * (4 * KC * 128 + 16)) / (sizeof(double) * 4 * R)) : 0;
+    const int tstage = ctx->sweep_tstage;
+    const bool staged = WIDE && !ctx->sweep_alt && (tstage > 0 || (tstage < 0 && jch_sweep_tstage_default(KC, n, ctx->cus)));
+    static int bpc2[2] = {0, 0};   // [staged]: the occupancy query sees the LDS of the launch (the largest ring for the staged kernel)
     static jch_per_device_once once;
     if (!once.done(ctx->device)) {
         int nblk = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_v2<KC, R, NBUF, true>, 256, lds);
-        bpc = (e == hipSuccess && nblk > 0) ? nblk : 1;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_v2<KC, R, NBUF, true>, 256, lds0);
+        bpc2[0] = bpc2[1] = (e == hipSuccess && nblk > 0) ? nblk : 1;
+        if constexpr (WIDE) {
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_sweep_v2<KC, R, NBUF, true, false, true>, 256,
+                                                             lds0 + sizeof(double) * 4 * TCAP_MAX * R);
+            bpc2[1] = (e == hipSuccess && nblk > 0) ? nblk : 1;
+        }
         once.mark(ctx->device);
     }
+    const int bpc = bpc2[staged];
     int64_t nb64 = (ngroups + 3) / 4;
     // FEWER blocks than CUs (round 4, last session; profiles/r04c_sweep_grid_scan.log): at one 4-wave block per CU the 500-column sweep
     // is faster with 13/16 of the CUs streaming — 208 of 256: 581 us per launch against 593-598 at 1e6 rows (6.91 TB/s against 6.75),
@@ -609,6 +653,11 @@ static int32_t launch_sweep_v2_t(jch_ctx *ctx, const double *Xr, int64_t n, int 
     const int ldpart = (m + 7) & ~7;
     JCH_TRY(jch_reserve(ctx, ctx->part, sizeof(double) * (size_t)nb * ldpart));
     double *part = (double *)ctx->part.ptr;
+    // the ring: every row group of the wave with the most of them, so that the only flush is the one behind the last group — or what
+    // the switch asks for, or what the 64 KB allow; a shorter ring is written out whenever it is full
+    int tcap = 0;
+    if (staged) tcap = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(tstage > 0 ? tstage : TCAP_MAX, TCAP_MAX), (ngroups + (int64_t)nb * 4 - 1) / ((int64_t)nb * 4)));
+    const size_t lds = lds0 + sizeof(double) * 4 * (size_t)tcap * R;
     int nslice = std::max(1, std::min(JCH_ZT_SLICES, nb / 8));
     // JCH_SWEEP_FUSED_REDUCE=1: the slice sums happen in the sweep's last-arriving blocks instead of k_reduce_part.  Measured
     // and NOT the default: it removes 4 us of small-state time per LV (one launch boundary + the reduce kernel) but the tail it
@@ -650,9 +699,15 @@ static int32_t launch_sweep_v2_t(jch_ctx *ctx, const double *Xr, int64_t n, int 
         const double wave_bytes = (double)ngroups / (double)W * R * ldr * sizeof(double);
         nres = (int)std::max<int64_t>(1, std::min<int64_t>(W, (int64_t)(std::min(resident_mb, JCH_INFINITY_CACHE_MIB) * 1048576.0 / wave_bytes)));
     }
-    if (nres > 0)
-        hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true, KC == 4 || KC == 8>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
+    if (nres > 0 && tcap > 0)
+        hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true, WIDE, WIDE>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
+                           tickets, zt, ldz, fused ? nslice : 0, first ? 1 : 0, nres, tcap);
+    else if (nres > 0)
+        hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true, WIDE>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
                            tickets, zt, ldz, fused ? nslice : 0, first ? 1 : 0, nres);
+    else if (tcap > 0)
+        hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true, false, WIDE>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
+                           tickets, zt, ldz, fused ? nslice : 0, first ? 1 : 0, 0, tcap);
     else
         hipLaunchKernelGGL((k_sweep_v2<KC, R, NBUF, true>), dim3(nb), dim3(256), lds, ctx->stream, Xr, n, ldr, d, rvec, tcol, part, ldpart, mu,
                            tickets, zt, ldz, fused ? nslice : 0, first ? 1 : 0);
