@@ -542,6 +542,26 @@ JCH_API int32_t jch_pca_fit(jch_ctx *ctx, int32_t loc, const double *X, int64_t 
 JCH_API int32_t jch_row_resid_ss(jch_ctx *ctx, int32_t loc, const double *X, int64_t m, int64_t p, int64_t ldx, const double *shift, const double *Z,
                                  int64_t k, int64_t ldz, const double *B, int64_t ldb, double *out);
 
+/* ---- exact column medians and MADs, Stahel-Donoho outlyingness (src/utility.jl:162, src/stah.jl, src/occstah.jl) ---------------
+ * jch_col_median_mad -- med[j] = median(X[:, j]), mad[j] = 1.4826022185056018 * median(|X[:, j] - med[j]|) (StatsBase's `mad`), by an
+ * exact radix select on the device: no sampling, no sort, no n x p workspace (the deviations fl(|fl(x - med)|) are recomputed from X in every pass).
+ * X n x p (ldx >= n) [loc], read only; med and mad (p values each; mad may be NULL) on the host or the device as out_loc says.  With loc and
+ * out_loc both JCH_LOC_DEVICE the call only enqueues on the ctx stream and returns without a host synchronisation.  Odd n: the order statistic of
+ * rank (n - 1) / 2; even n: Julia's middle(lo, hi) = lo / 2 + hi / 2 of ranks n / 2 - 1 and n / 2.  Any n >= 1 and p >= 1; rows >= n are never read; row
+ * indices and counts are 64-bit.  Integer counters only: two runs give identical bits, and so do a host and a device X and an aligned and an
+ * unaligned one.  A column holding a NaN gets med = mad = NaN and no other column is touched; +-Inf are ordinary ordered values (a NaN deviation
+ * Inf - Inf makes that column's MAD NaN); the sign of a zero result is not specified. */
+JCH_API int32_t jch_col_median_mad(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, double *med, double *mad, int32_t out_loc);
+/* jch_stah -- `stah` (src/stah.jl:37-58, fit != 0) and the distances of `predict(::Occstah, X)` (src/occstah.jl:55-73, fit = 0) in one entry:
+ * d[i] = max_j |(t_ij - mu_j) / s_j| with T = ((X - 1 mu_scal') diag(1 / s_scal)) P.  X n x p (ldx >= n) and d (n) [loc], X read only; mu_scal and
+ * s_scal (p, NULL = zeros / ones) and P (p x a, ldp >= p) HOST; mu and s (a) HOST: written when fit (the medians and MADs of the columns of T,
+ * jch_col_median_mad), read otherwise.  P is walked in column panels within a fixed workspace budget: T never exists beyond one panel, a host X is
+ * staged once, the whole loop is enqueued without a host synchronisation.  The projection is jch_affine_gemm's (centring and scaling folded into
+ * the coefficients); the division by s_j is a true division and nothing guards s_j = 0 (a constant direction gives the IEEE result).  A NaN term
+ * makes d[i] NaN and stays in its row.  Any n, a >= 1.  One rank only. */
+JCH_API int32_t jch_stah(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *mu_scal, const double *s_scal,
+                         const double *P, int64_t a, int64_t ldp, int32_t fit, double *mu, double *s, double *d);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in

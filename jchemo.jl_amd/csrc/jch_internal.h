@@ -94,6 +94,8 @@ struct jch_ctx {
     jch_buf rp_stage, rp_rows, rp_coef;   // row preprocessing (rowprep.hip): bounded row-block staging of host data, the row-block copy of the wide-window FIR, taps / A and V
     jch_buf cs_ws, cs_part;   // covsel (covsel.hip): [Yd | Q] and the small state of a selection; per-workgroup partials of the pass
     jch_buf xt_part, xt_ws;   // xtdx.hip: per-split partial tiles of the Gram pass; G, the vectors and the staging of a PCA fit
+    jch_buf sel_ws, sel_out;   // colselect.hip: digit counters and per-column state of a chunk of columns; medians and MADs on their way to the host
+    jch_buf st_t, st_ms;   // stah.hip: one panel of projections; [mu | s | d of a host call]
     const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
     int64_t chol_n = 0, chol_ld = 0;
     // profiling
@@ -327,6 +329,10 @@ int32_t jch_eig_lead(jch_ctx *ctx, const double *A, int64_t dim, int64_t lda, co
 // xtdx.hip: G (p x p, ld ldg) = (X - 1 mu')' diag(d) (X - 1 mu'), everything on the device; X n x p column-major (ld ldx), read only.  Both
 // triangles are written from the same value; fixed-order sums, no atomics.
 int32_t jch_launch_xtdx(jch_ctx *ctx, const double *X, int64_t n, int p, int64_t ldx, const double *mu, const double *d, double *G, int64_t ldg);
+// colselect.hip: exact medians (and, mad non-null, MADs) of the p columns of the device matrix X (n x p, ld ldx) into the device vectors med and mad.
+// jch_colselect_reserve(ctx, p) first: the launcher itself reserves nothing and only enqueues.
+int32_t jch_colselect_reserve(jch_ctx *ctx, int64_t p);
+int32_t jch_launch_col_median_mad(jch_ctx *ctx, const double *X, int64_t n, int64_t p, int64_t ldx, double *med, double *mad);
 // kmethod.hip: what the kernel-method entry points (dkplsr.hip, kplsr.hip, kpca.hip, krr.hip) share
 int32_t jch_check_kernel(jch_ctx *ctx, const char *who, int32_t kind, int32_t degree);   // kernel kind / degree, one rank only
 // column-major rows x cols matrix from src (ld lds) to dst (ld ldd) on ctx->stream

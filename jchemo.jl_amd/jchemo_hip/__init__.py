@@ -9,3 +9,4 @@ from .preproc import Savgk, detrend, detrend_, fdif, mavg, mavg_, mavg_runmean, 
 from .covsel import Covsel, Covselr, Mlr, covsel, covsel_, covselr, covselr_coef, covselr_predict  # noqa: F401
 from .pca import Pca, Pcr, pca_summary, pca_transform, pcaeigen, pcaeigen_, pcaeigenk, pcaeigenk_, pcasvd, pcasvd_, pcr, pcr_  # noqa: F401
 from .occ import Occod, OccPred, Occsd, Occsdod, occ_predict, occod, occsd, occsdod, row_resid_ss  # noqa: F401
+from .stah import Occstah, Stah, col_median_mad, colmad, occstah, stah  # noqa: F401

@@ -33,7 +33,7 @@ SYMBOLS = (
     "jch_kplsr_fit", "jch_kplsr_transform", "jch_kplsr_predict", "jch_kpca_fit", "jch_kc_panel",
     "jch_krr_fit", "jch_krr_solve", "jch_chol_factor", "jch_chol_solve", "jch_chol_inv_fro2",
     "jch_rows_standardize", "jch_rows_project_out", "jch_rows_fir", "jch_covsel_fit", "jch_covsel_pass",
-    "jch_xtdx", "jch_pca_fit", "jch_row_resid_ss",
+    "jch_xtdx", "jch_pca_fit", "jch_row_resid_ss", "jch_col_median_mad", "jch_stah",
 )
 
 
@@ -133,6 +133,8 @@ def load():
     L.jch_xtdx.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, dp, dp, dp]
     L.jch_pca_fit.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i64, i32, i32, f64, i32] + [dp] * 11 + [C.POINTER(i32), dp, C.POINTER(i32), C.POINTER(i32)]
     L.jch_row_resid_ss.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, i64, dp]
+    L.jch_col_median_mad.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i32]
+    L.jch_stah.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, dp, i64, i64, i32, dp, dp, dp]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]
     L.jch_ctx_set_profiling.argtypes = [vp, i32]
     L.jch_ctx_get_profile.argtypes = [vp, C.POINTER(Profile)]

@@ -308,8 +308,12 @@ def occsdod(fm, X, *, nlv_sd: Optional[int] = None, nlv_od: Optional[int] = None
 
 def occ_predict(obj, X, *, ctx: Optional[Context] = None) -> OccPred:
     """`predict(object::Occsd, X)`, `predict(object::Occod, X)`, `predict(object::Occsdod, X)` (src/occsd.jl:153-164, src/occod.jl:65-75,
-    src/occsdod.jl:60-74): the table of the new rows and pred = Int64.(dstand .> 1) as an m x 1 matrix."""
+    src/occsdod.jl:60-74): the table of the new rows and pred = Int64.(dstand .> 1) as an m x 1 matrix.  An Occstah model: src/occstah.jl:55-73
+    (stah.py)."""
     kind = _kind(obj)
+    if kind == "Occstah":
+        from .stah import _predict_stah
+        return _predict_stah(obj, X, ctx)
     if kind == "Occsd":
         tab = _predict_sd(obj, X, ctx)
     elif kind == "Occod":
@@ -318,5 +322,5 @@ def occ_predict(obj, X, *, ctx: Optional[Context] = None) -> OccPred:
         X = _colmajor_x(X)
         tab = _hcat_sd_od(_predict_sd(obj.fm_sd, X, ctx), _predict_od(obj.fm_od, X, ctx))
     else:
-        raise TypeError(f"occ_predict takes an Occsd, Occod or Occsdod model, not a {kind}")
+        raise TypeError(f"occ_predict takes an Occsd, Occod, Occsdod or Occstah model, not a {kind}")
     return OccPred(_pred(tab["dstand"]), tab)

@@ -428,11 +428,11 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
     value -> matrix, several -> list of matrices.  All values are computed in ONE pass over X.
     `rank` / `world` (kNN-LWPLSR only): split the queries over `world` replicas, see lwplsr_predict.
     A Covselr model: src/covselr.jl:61-64 (covselr_predict).  An Occsd, Occod or Occsdod model: src/occsd.jl:153-164, src/occod.jl:65-75,
-    src/occsdod.jl:60-74 (occ_predict)."""
+    src/occsdod.jl:60-74; an Occstah model: src/occstah.jl:55-73 (occ_predict)."""
     if type(fm).__name__ == "Covselr":
         from .covsel import covselr_predict
         return covselr_predict(fm, X, ctx=ctx)
-    if type(fm).__name__ in ("Occsd", "Occod", "Occsdod"):
+    if type(fm).__name__ in ("Occsd", "Occod", "Occsdod", "Occstah"):
         from .occ import occ_predict
         return occ_predict(fm, X, ctx=ctx)
     if isinstance(fm, Lwplsr):

@@ -36,7 +36,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        snv, snv!, detrend, detrend!, savgol, savgol!, savgk, mavg, mavg!, mavg_runmean, fdif,
        Covsel, Covselr, covsel, covsel!, covselr,
        Pca, Pcr, pcasvd, pcasvd!, pcaeigen, pcaeigen!, pcaeigenk, pcaeigenk!, pcr, pcr!, xtdx,
-       Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss
+       Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss,
+       Occstah, occstah, stah, colmad, col_median_mad
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -1772,6 +1773,82 @@ end
 "`predict(object::Occsdod, X)` — src/occsdod.jl:60-74."
 function predict(object::Occsdod, X; ctx = default_ctx())
     cols = _occ_hcat(_occ_sd_cols(object.fm_sd, X, ctx), _occ_od_cols(object.fm_od, X, ctx))
+    (pred = _occ_pred(cols.dstand), d = _table(cols))
+end
+
+# ---- exact column medians / MADs and the Stahel-Donoho outlyingness (src/utility.jl:162, src/stah.jl, src/occstah.jl; DESIGN.md 18) ----------
+struct Occstah                    # src/occstah.jl:1-6 (e_cdf: the sorted training d)
+    d
+    res_stah
+    e_cdf
+    cutoff::Float64
+end
+
+"""`col_median_mad(X)` — (med, mad) of the columns of X as host vectors, exact order statistics from the device (jch_col_median_mad): odd n the
+middle value, even n `middle(lo, hi)`; mad = 1.4826022185056018 * median(|x - med|).  A column holding a NaN gives NaN for both."""
+function col_median_mad(X; ctx = default_ctx())
+    X = _in(X); n, p = size(X)
+    med = zeros(p); md = zeros(p)
+    GC.@preserve X med md begin
+        check(ctx, ccall((:jch_col_median_mad, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int32),
+                         ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), pointer(med), pointer(md), Int32(0)))
+    end
+    (med, md)
+end
+"`colmad(X)` — src/utility.jl:162-170: the MAD of each column (jch_col_median_mad)."
+colmad(X; ctx = default_ctx()) = col_median_mad(X; ctx = ctx)[2]
+
+# one jch_stah call: d where X lives; mu and s are written when fit
+function _stah_call(X, mu_scal, s_scal, P, fit::Bool, mu, s, ctx)
+    n, p = size(X); a = size(P, 2)
+    size(P, 1) == p || throw(DimensionMismatch("P is not $p x $a"))
+    d = _similar(X, n)
+    GC.@preserve X mu_scal s_scal P mu s d begin
+        check(ctx, ccall((:jch_stah, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int32,
+                          Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), pointer(mu_scal), pointer(s_scal), pointer(P), a, p, Int32(fit),
+                         pointer(mu), pointer(s), pointer(d)))
+    end
+    d
+end
+
+"""`stah(X, a; scal = true)` — src/stah.jl:37-58: (d, P, mu_scal, s_scal, mu, s).  mu_scal, s_scal: the column medians and MADs of X when `scal`;
+T = cscale(X, mu_scal, s_scal) * P in column panels, mu and s its column medians and MADs, d[i] = max_j |(t_ij - mu_j) / s_j| (jch_stah).  `P`
+(p x a) is drawn with `rand(0:1, p, a)` unless given: the reference's `sample(0:1, p * a)` comes from a stream it does not pin."""
+function stah(X, a; scal = true, P = nothing, ctx = default_ctx())
+    a >= 1 || throw(ArgumentError("a = $a must be >= 1"))
+    X = _in(X); n, p = size(X)
+    Pm = P === nothing ? Matrix{Float64}(rand(0:1, p, a)) : Matrix{Float64}(P)
+    size(Pm) == (p, a) || throw(DimensionMismatch("P is not $p x $a"))
+    mu_scal = zeros(p); s_scal = ones(p)
+    if scal
+        mu_scal, s_scal = col_median_mad(X; ctx = ctx)
+    end
+    mu = zeros(a); s = zeros(a)
+    d = _stah_call(X, mu_scal, s_scal, Pm, true, mu, s, ctx)
+    (d = d, P = Pm, mu_scal = mu_scal, s_scal = s_scal, mu = mu, s = s)
+end
+
+"""`occstah(X; a = 2000, typc = "mad", cri = 3, alpha = .025, scal = true)` — src/occstah.jl:28-47.  `kwargs` are not taken (the reference passes
+them to a `kde` it never calls)."""
+function occstah(X; a = 2000, typc = "mad", cri = 3, alpha = .025, scal = true, P = nothing, ctx = default_ctx())
+    typc in ("mad", "q") || throw(ArgumentError("typc = $typc must be \"mad\" or \"q\""))
+    res = stah(X, a; scal = scal, P = P, ctx = ctx)
+    d = res.d
+    e_cdf = sort(Array(d))
+    cutoff = _occ_cutoff(e_cdf, typc, cri, alpha)
+    Occstah(_table((d = d, dstand = d ./ cutoff, pval = _occ_pval(e_cdf, d))), res, e_cdf, cutoff)
+end
+
+"`predict(object::Occstah, X)` — src/occstah.jl:55-73: one jch_stah call with fit = 0."
+function predict(object::Occstah, X; ctx = default_ctx())
+    res = object.res_stah
+    X = _in(X)
+    d = _stah_call(X, Vector{Float64}(res.mu_scal), Vector{Float64}(res.s_scal), Matrix{Float64}(res.P), false, Vector{Float64}(res.mu),
+                   Vector{Float64}(res.s), ctx)
+    cols = (d = d, dstand = d ./ object.cutoff, pval = _occ_pval(object.e_cdf, d))
     (pred = _occ_pred(cols.dstand), d = _table(cols))
 end
 
