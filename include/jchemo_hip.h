@@ -562,6 +562,28 @@ JCH_API int32_t jch_col_median_mad(jch_ctx *ctx, int32_t loc, const double *X, i
 JCH_API int32_t jch_stah(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *mu_scal, const double *s_scal,
                          const double *P, int64_t a, int64_t ldp, int32_t fit, double *mu, double *s, double *d);
 
+/* ---- Kennard-Stone and Duplex sampling without an n x n distance matrix (src/sampling.jl:40-148) ---------------------------------
+ * Row indices are 0-based int64_t.  X n x p (ldx >= n) [loc], read only; a host X is staged once per call.  No atomics: two runs give identical
+ * bits, and so do a host and a device X and an aligned and an unaligned one.  One rank only.
+ * jch_farthest_pair -- pair[0] > pair[1] (HOST): the two rows with the largest squared Euclidean distance among the rows that are not listed in
+ * skip (nskip indices, HOST; may be NULL when nskip = 0) and hold no non-finite entry; ties go to the smallest pair[1], then the smallest pair[0]:
+ * the first maximum of a column-major scan of the symmetric distance matrix (`findall(D .== maximum(D))[1]`).  The search compares
+ * |a_i|^2 + |a_j|^2 - 2 a_i.a_j of the rows a = x - c centred on the column means of the candidates, 128 x 128 tiles of the triangle on the f64
+ * matrix cores, n^2 p flop, nothing n x n stored (one triple per tile); every compared value is within 4 (p + 20) 2^-53 of the largest squared
+ * distance.  *d2 (HOST) = the pair's squared distance in direct form, sum_j (x_rj - x_cj)^2 in ascending j.  JCH_EINVAL: fewer than
+ * two candidate rows, a skip index out of range, more than 2^31 - 1 tiles.
+ * jch_maxmin_select -- nsets = 1: Kennard-Stone; nsets = 2: Duplex.  init (HOST, 2 nsets indices): the starting pair of each set; k >= 2: rows per
+ * set, the starting pair included (k <= n, 2 k <= n for Duplex).  Every further row of a set is argmax_i min_{s in the set} d2(i, s) over the rows
+ * no set has taken, ties to the smallest index; in a Duplex step the first set chooses first.  d2 in direct form, ascending j.  One read of X per
+ * selected row (per pair of rows for Duplex), no host synchronisation inside the loop.  sel (HOST, k x nsets column-major): the rows in the order
+ * they were taken; dsel (HOST, same shape, may be NULL): the min-distance at which each row was taken, the starting pairs their mutual d2.  A
+ * row with a non-finite distance to a selected row is never taken and changes nothing for the others.  JCH_EINVAL: k out of range, init out of
+ * range or repeated, fewer than k nsets rows that can be taken. */
+JCH_API int32_t jch_farthest_pair(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const int64_t *skip, int32_t nskip,
+                                  int64_t *pair, double *d2);
+JCH_API int32_t jch_maxmin_select(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, int32_t nsets, const int64_t *init,
+                                  int64_t k, int64_t *sel, double *dsel);
+
 /* ---- harness utilities (bench / tests) ---------------------------------------------------------- */
 /* Fill device matrix out (n x p, column-major ld) with rows [row0,row0+n) of the n_total x p matrix
  * whose element (i,j) is splitmix64-uniform(seed, i + j*n_total) — the README's `rand(n,p)` stand-in

@@ -96,6 +96,7 @@ struct jch_ctx {
     jch_buf xt_part, xt_ws;   // xtdx.hip: per-split partial tiles of the Gram pass; G, the vectors and the staging of a PCA fit
     jch_buf sel_ws, sel_out;   // colselect.hip: digit counters and per-column state of a chunk of columns; medians and MADs on their way to the host
     jch_buf st_t, st_ms;   // stah.hip: one panel of projections; [mu | s | d of a host call]
+    jch_buf sp_ws;   // samp.hip: row flags, per-workgroup triples and the result of a farthest-pair search; running minima, partials and targets of a max-min selection
     const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
     int64_t chol_n = 0, chol_ld = 0;
     // profiling
@@ -306,6 +307,9 @@ int32_t jch_launch_scores(jch_ctx *ctx, const double *Xr, int64_t n, int p, int 
 // pointer, ld and divisors), only the tiles on or below the diagonal are computed and each is stored twice
 int32_t jch_launch_kgram(jch_ctx *ctx, int kind, const double *Z, int64_t m, int64_t ldz, const double *zdiv, const double *X, int64_t n,
                          int64_t ldx, const double *xdiv, int64_t p, double gamma, double coef0, int degree, bool sym, double *K, int64_t ldk);
+// kgram.hip: the preparation of the symmetric krbf Gram on its own (samp.hip): cp (ldc x pp, ldc and pp the padded sizes of jch_launch_kgram) = the
+// zero-padded copy of X - 1 c' (c: device p-vector, given), nrm (ldc) = the squared norms of its rows
+int32_t jch_launch_kgram_prep(jch_ctx *ctx, const double *X, int64_t n, int64_t ldx, int64_t p, const double *c, double *cp, int64_t ldc, int64_t pp, double *nrm);
 // kplsr.hip: K = kern(X, X) into Kraw, vtot = K w, *sdev = w'vtot, Kc = K - vtot 1' - 1 vtot' + *sdev (Kc == Kraw allowed)
 int32_t jch_launch_kp_centred_gram(jch_ctx *ctx, int kind, double gamma, double coef0, int degree, const double *X, int64_t n, int64_t ldx,
                                    const double *xdiv, int64_t p, const double *wn, double *Kraw, double *Kc, double *vt, double *sdev);

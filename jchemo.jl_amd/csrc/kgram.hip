@@ -153,6 +153,15 @@ __global__ __launch_bounds__(256, 2) void k_gram(const double *__restrict__ Zc, 
     }
 }
 
+int32_t jch_launch_kgram_prep(jch_ctx *ctx, const double *X, int64_t n, int64_t ldx, int64_t p, const double *c, double *cp, int64_t ldc, int64_t pp, double *nrm)
+{
+    const unsigned nb = (unsigned)std::min<int64_t>((ldc * pp + 255) / 256, (int64_t)ctx->cus * 16);
+    hipLaunchKernelGGL(k_gram_copy, dim3(nb), dim3(256), 0, ctx->stream, X, n, ldx, p, (const double *)nullptr, c, cp, ldc, pp);
+    hipLaunchKernelGGL(k_gram_norms, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)cp, ldc, pp, nrm);
+    JCH_HIP(ctx, hipGetLastError());
+    return JCH_OK;
+}
+
 int32_t jch_launch_kgram(jch_ctx *ctx, int kind, const double *Z, int64_t m, int64_t ldz, const double *zdiv, const double *X, int64_t n,
                          int64_t ldx, const double *xdiv, int64_t p, double gamma, double coef0, int degree, bool sym, double *K, int64_t ldk)
 {

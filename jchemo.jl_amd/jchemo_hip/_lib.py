@@ -34,6 +34,7 @@ SYMBOLS = (
     "jch_krr_fit", "jch_krr_solve", "jch_chol_factor", "jch_chol_solve", "jch_chol_inv_fro2",
     "jch_rows_standardize", "jch_rows_project_out", "jch_rows_fir", "jch_covsel_fit", "jch_covsel_pass",
     "jch_xtdx", "jch_pca_fit", "jch_row_resid_ss", "jch_col_median_mad", "jch_stah",
+    "jch_farthest_pair", "jch_maxmin_select",
 )
 
 
@@ -135,6 +136,8 @@ def load():
     L.jch_row_resid_ss.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, i64, dp]
     L.jch_col_median_mad.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i32]
     L.jch_stah.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, dp, i64, i64, i32, dp, dp, dp]
+    L.jch_farthest_pair.argtypes = [vp, i32, dp, i64, i64, i64, dp, i32, dp, dp]
+    L.jch_maxmin_select.argtypes = [vp, i32, dp, i64, i64, i64, i32, dp, i64, dp, dp]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]
     L.jch_ctx_set_profiling.argtypes = [vp, i32]
     L.jch_ctx_get_profile.argtypes = [vp, C.POINTER(Profile)]

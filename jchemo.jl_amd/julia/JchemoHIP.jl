@@ -26,6 +26,7 @@ file against include/jchemo_hip.h (literal signatures, argument counts and types
 module JchemoHIP
 
 using LinearAlgebra
+using Random
 
 export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!, plsrosa, plsrosa!, plswold, plswold!,
        lwplsr, transform, coef, predict, explvarx, JchCtx, attach!, nipals_one_pass!,
@@ -37,7 +38,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Covsel, Covselr, covsel, covsel!, covselr,
        Pca, Pcr, pcasvd, pcasvd!, pcaeigen, pcaeigen!, pcaeigenk, pcaeigenk!, pcr, pcr!, xtdx,
        Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss,
-       Occstah, occstah, stah, colmad, col_median_mad
+       Occstah, occstah, stah, colmad, col_median_mad,
+       sampks, sampdp, sampsys, sampcla, farthest_pair, maxmin_select
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -1850,6 +1852,110 @@ function predict(object::Occstah, X; ctx = default_ctx())
                    Vector{Float64}(res.s), ctx)
     cols = (d = d, dstand = d ./ object.cutoff, pval = _occ_pval(object.e_cdf, d))
     (pred = _occ_pred(cols.dstand), d = _table(cols))
+end
+
+# ---- sampling of the calibration set (src/sampling.jl; DESIGN.md 19): Kennard-Stone and Duplex without an n x n matrix ---------------------
+# All indices are 1-based here; the C ABI is 0-based.
+"""`farthest_pair(X; skip = Int[])` — (row, col, d2), row > col: the two rows of X with the largest squared Euclidean distance among the rows not in
+`skip` (jch_farthest_pair); ties go to the smallest col, then the smallest row, as `findall(D .== maximum(D))[1]` on the distance matrix."""
+function farthest_pair(X; skip = Int[], ctx = default_ctx())
+    X = _in(X); n, p = size(X)
+    sk = Vector{Int64}(collect(skip) .- 1)
+    pair = zeros(Int64, 2); d2 = zeros(1)
+    GC.@preserve X sk pair d2 begin
+        check(ctx, ccall((:jch_farthest_pair, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int64}, Int32, Ptr{Int64}, Ptr{Float64}),
+                         ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), pointer(sk), Int32(length(sk)), pointer(pair), pointer(d2)))
+    end
+    (row = pair[1] + 1, col = pair[2] + 1, d2 = d2[1])
+end
+
+"""`maxmin_select(X, init, k; nsets = 1)` — (sel, dsel), k x nsets: the rows in the order they were taken and the min-distance at which each was taken,
+from the starting pair(s) `init` (jch_maxmin_select).  nsets = 1: Kennard-Stone; nsets = 2: Duplex, one read of X per pair of rows."""
+function maxmin_select(X, init, k; nsets = 1, ctx = default_ctx())
+    X = _in(X); n, p = size(X)
+    ini = Vector{Int64}(vec(collect(init)) .- 1)
+    length(ini) == 2 * nsets || throw(ArgumentError("init must hold 2 nsets = $(2 * nsets) rows"))
+    k >= 2 || throw(ArgumentError("k = $k must be >= 2"))
+    sel = zeros(Int64, k, nsets); dsel = zeros(k, nsets)
+    GC.@preserve X ini sel dsel begin
+        check(ctx, ccall((:jch_maxmin_select, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Int32, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Float64}),
+                         ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), Int32(nsets), pointer(ini), k, pointer(sel), pointer(dsel)))
+    end
+    (sel = sel .+ 1, dsel = dsel)
+end
+
+# X itself ("eucl"), or Z = X * Uinv where X lives ("mahal": S = U'U the uncorrected covariance, src/distances.jl:104-117; p = 1: 1 / sqrt(S))
+function _samp_space(X, metric, ctx)
+    metric in ("eucl", "mahal") || throw(ArgumentError("metric = $metric must be \"eucl\" or \"mahal\""))
+    X = _in(X)
+    metric == "eucl" && return X
+    p = size(X, 2)
+    S = _cov(X, ctx)
+    if p == 1
+        S[1, 1] > 0 || throw(ArgumentError("the covariance of X is not positive definite"))
+        return _affine(X, nothing, nothing, fill(1 / sqrt(S[1, 1]), 1, 1), nothing, ctx)
+    end
+    Uinv = Matrix{Float64}(inv(cholesky(Hermitian(S)).U))          # throws PosDefException on a singular S
+    _affine(X, nothing, nothing, Uinv, nothing, ctx)
+end
+
+"""`sampks(X; k, metric = "eucl")` — src/sampling.jl:40-60, Kennard-Stone: (train, test); train in selection order, starting with the farthest
+pair [row, col], test ascending.  Nothing n x n is built: jch_farthest_pair, then one read of X per selected row (jch_maxmin_select)."""
+function sampks(X; k, metric = "eucl", ctx = default_ctx())
+    k = Int64(round(k))
+    Z = _samp_space(X, metric, ctx); n = size(Z, 1)
+    2 <= k <= n || throw(ArgumentError("k = $k must be >= 2 and <= n = $n"))
+    pr = farthest_pair(Z; ctx = ctx)
+    s = vec(maxmin_select(Z, [pr.row, pr.col], k; nsets = 1, ctx = ctx).sel)
+    (train = s, test = setdiff(1:n, s))
+end
+
+"""`sampdp(X; k, metric = "eucl")` — src/sampling.jl:118-148, Duplex: (train, test, remain), k rows each.  The second pair is the farthest pair among
+the rows outside the first (the masked reading of :133, DESIGN.md 6)."""
+function sampdp(X; k, metric = "eucl", ctx = default_ctx())
+    k = Int64(round(k))
+    Z = _samp_space(X, metric, ctx); n = size(Z, 1)
+    (2 <= k && 2 * k <= n && n >= 4) || throw(ArgumentError("k = $k must be >= 2 and <= n / 2 (n = $n)"))
+    p1 = farthest_pair(Z; ctx = ctx)
+    p2 = farthest_pair(Z; skip = [p1.row, p1.col], ctx = ctx)
+    sel = maxmin_select(Z, [p1.row, p1.col, p2.row, p2.col], k; nsets = 2, ctx = ctx).sel
+    s1 = sel[:, 1]; s2 = sel[:, 2]
+    (train = s1, test = s2, remain = setdiff(1:n, vcat(s1, s2)))
+end
+
+"""`sampsys(y; k)` — src/sampling.jl:168-182: k ranks on a regular grid over the sorted y (the minimum and the maximum always); host only."""
+function sampsys(y; k)
+    k = Int64(round(k)); y = vec(y); n = length(y)
+    k >= 2 || throw(ArgumentError("k = $k must be >= 2"))
+    z = unique(Int64.(round.(range(1, n; length = k))))
+    s = sortperm(y)[z]
+    (train = s, test = setdiff(1:n, s))
+end
+
+"""`sampcla(x, y = nothing; k, seed = nothing)` — src/sampling.jl:218-243: k rows (one number, or one per class) from every class of x, clipped to
+the class size; random without replacement when y is nothing (`seed` pins the stream), else `sampsys` over the class's y; host only."""
+function sampcla(x, y = nothing; k, seed = nothing)
+    x = vec(x); n = length(x)
+    lev = sort(unique(x)); nlev = length(lev)
+    ni = [count(==(l), x) for l in lev]
+    kk = length(k) == 1 ? fill(Int64(round(k[1])), nlev) : Int64.(round.(collect(k)))
+    length(kk) == nlev || throw(ArgumentError("k has $(length(kk)) entries: one, or one per class ($nlev)"))
+    rng = seed === nothing ? Random.default_rng() : Random.MersenneTwister(seed)
+    s = Int64[]
+    for i in 1:nlev
+        kk[i] = min(kk[i], ni[i])
+        zs = findall(==(lev[i]), x)
+        if y === nothing
+            append!(s, Random.shuffle(rng, zs)[1:kk[i]])
+        elseif kk[i] == 1
+            push!(s, zs[argmin(vec(y)[zs])])
+        else
+            append!(s, zs[sampsys(vec(y)[zs]; k = kk[i]).train])
+        end
+    end
+    (train = s, test = setdiff(1:n, s), lev = lev, ni = ni, k = kk)
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
