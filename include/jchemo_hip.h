@@ -131,7 +131,10 @@ typedef struct jch_pls_desc {
  * of a parameter grid.  A Float64 plskern-shaped fit whose predecessor left its row-major working copy in the workspace then skips
  * the staging of X (host arrays) and the transposing copy, and takes X'D[Yc | 1] from one streaming read of that copy (q <= 11,
  * p <= 512; same results up to the summation order of X'DY).  In every other situation the bit is ignored.  Y and the weights may
- * change freely; if X changed, the results are those of the OLD X. */
+ * change freely; if X changed, the results are those of the OLD X.
+ * The promise is about X only, never about the ctx: a result does not depend on what ran on the ctx before.  Any call in between
+ * that touched the staging buffer or the working copy (another fit, a prediction, a kernel method, a preprocessing call, ...) makes
+ * the library ignore the bit and run the whole prologue, with correct results. */
 #define JCH_REUSE_XCOPY 8
 
 /*

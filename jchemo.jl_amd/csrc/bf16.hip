@@ -1171,7 +1171,7 @@ int32_t jch_fit_plskern_bf16(jch_ctx *ctx, const jch_pls_desc &d, const void *Xv
     const int p = (int)d.p, q = (int)d.q;
     const bf16_t *Xc = (const bf16_t *)Xv, *Yc = (const bf16_t *)Yv;
     const int ldr_b = (p + 7) & ~7;                    // bf16 row stride: 16-B aligned rows
-    JCH_TRY(jch_reserve(ctx, ctx->xr, sizeof(bf16_t) * (size_t)n * ldr_b));
+    JCH_TRY(jch_reserve_xr(ctx, sizeof(bf16_t) * (size_t)n * ldr_b));
     JCH_TRY(jch_reserve(ctx, ctx->yr, sizeof(double) * (size_t)n * qpad));
     bf16_t *Xr = (bf16_t *)ctx->xr.ptr;
     double *Yr = (double *)ctx->yr.ptr;

@@ -199,7 +199,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         const jch_pls_desc &db = *io.d;
         JCH_HIP(ctx, hipSetDevice(ctx->device));
         ctx->xcopy_valid = false;
-        JCH_TRY(jch_reserve(ctx, ctx->xstage, sizeof(double) * (size_t)db.n * db.p));
+        JCH_TRY(jch_reserve_xstage(ctx, sizeof(double) * (size_t)db.n * db.p));
         JCH_TRY(jch_reserve(ctx, ctx->ystage, sizeof(double) * (size_t)db.n * db.q));
         const unsigned nbw = (unsigned)std::min<int64_t>(((int64_t)db.n * db.p + 255) / 256, (int64_t)ctx->cus * 16);
         hipLaunchKernelGGL(k_widen_bf16, dim3(nbw), dim3(256), 0, ctx->stream, (const unsigned short *)io.X, io.ldx, db.n, db.p, (double *)ctx->xstage.ptr);
@@ -246,7 +246,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     const double *wdev = io.weights;
     int64_t ldxc = io.ldx, ldyc = io.ldy;
     if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->xstage, sizeof(double) * (size_t)n * p));
+        JCH_TRY(jch_reserve_xstage(ctx, sizeof(double) * (size_t)n * p, /*keep_copy =*/reuse_x));
         JCH_TRY(jch_reserve(ctx, ctx->ystage, sizeof(double) * (size_t)n * q));
         Xc = (double *)ctx->xstage.ptr; Yc = (double *)ctx->ystage.ptr; ldxc = n; ldyc = n;
         if (!reuse_x) JCH_TRY(h2d_matrix(ctx, Xc, (const double *)io.X, n, p, io.ldx));   // (reuse: the staging copy of the previous fit is this X)
@@ -261,7 +261,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     // ---- working copies and small state
     const int nlv_cap = (int)std::min<int64_t>(d.nlv, p);  // upper bound before the global-n clamp
     if (d.dtype == JCH_F64) {
-        JCH_TRY(jch_reserve(ctx, ctx->xr, sizeof(double) * (size_t)n * ldr));
+        JCH_TRY(jch_reserve_xr(ctx, sizeof(double) * (size_t)n * ldr, /*keep_copy =*/reuse_x));
         JCH_TRY(jch_reserve(ctx, ctx->yr, sizeof(double) * (size_t)n * qpad));
     }
     double *Xr = (double *)ctx->xr.ptr, *Yr = (double *)ctx->yr.ptr;
@@ -710,8 +710,7 @@ extern "C" int32_t jch_col_stats(jch_ctx *ctx, int32_t loc, const double *X, int
     const double *dX = X, *dw = weights;
     int64_t ldxd = ldx;
     if (loc == JCH_LOC_HOST) {
-        if (ctx->xcopy.host) ctx->xcopy_valid = false;   // (the staging buffer a host-array fit would re-use is overwritten)
-        JCH_TRY(jch_reserve(ctx, ctx->xstage, sizeof(double) * (size_t)n * p));
+        JCH_TRY(jch_reserve_xstage(ctx, sizeof(double) * (size_t)n * p));   // (the staging buffer a host-array fit would re-use is overwritten)
         JCH_TRY(h2d_matrix(ctx, (double *)ctx->xstage.ptr, X, n, p, ldx));
         dX = (const double *)ctx->xstage.ptr; ldxd = n;
         if (weights) {

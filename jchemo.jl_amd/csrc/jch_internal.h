@@ -160,6 +160,17 @@ bool jch_knob_set(const char *name);
 int jch_knob(const char *name, int dflt);
 
 int32_t jch_reserve(jch_ctx *ctx, jch_buf &b, size_t bytes);
+// The two buffers the JCH_REUSE_XCOPY state lives in are reserved through these two and nowhere else: `xstage` holds the staged X of
+// a host-array fit (the reuse path takes the pivot from it and never uploads X again), `xr` the raw row-major copy itself.  Whoever
+// takes either of them for something else thereby drops the copy; only the fit that is itself reusing it passes keep_copy.
+inline int32_t jch_reserve_xstage(jch_ctx *ctx, size_t bytes, bool keep_copy = false) {
+    if (!keep_copy && ctx->xcopy.host) ctx->xcopy_valid = false;   // (a device-resident X has no staging copy to lose)
+    return jch_reserve(ctx, ctx->xstage, bytes);
+}
+inline int32_t jch_reserve_xr(jch_ctx *ctx, size_t bytes, bool keep_copy = false) {
+    if (!keep_copy) ctx->xcopy_valid = false;
+    return jch_reserve(ctx, ctx->xr, bytes);
+}
 int32_t jch_reserve_host(jch_ctx *ctx, size_t bytes);   // ctx->hstage (pinned)
 int32_t jch_allreduce_f64(jch_ctx *ctx, double *dev_buf, size_t count);  // no-op when nranks == 1
 // all-reduce of the per-LV sweep output zt [nslice][ldz] (first m entries of every slice); *nslice_out = slices the

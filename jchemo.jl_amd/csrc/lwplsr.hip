@@ -744,8 +744,7 @@ static int32_t launch_locw_q(jch_ctx *ctx, locw_args &g)
     }
     const int nb = std::min(g.m, ctx->cus * 2);
     g.slab = ((size_t)g.k * g.ldr + 2 * (size_t)g.nlv_hi * g.ldr + 31) & ~(size_t)31;
-    if (ctx->xcopy.host) ctx->xcopy_valid = false;   // (the staging buffer of a host-array fit is re-used for the slabs)
-    JCH_TRY(jch_reserve(ctx, ctx->xstage, sizeof(double) * g.slab * nb));
+    JCH_TRY(jch_reserve_xstage(ctx, sizeof(double) * g.slab * nb));   // (the staging buffer of a host-array fit is re-used for the slabs)
     g.scratch = (double *)ctx->xstage.ptr;
     hipLaunchKernelGGL((k_locw_plskern<KC, Q>), dim3(nb), dim3(256), lds, ctx->stream, g);
     JCH_HIP(ctx, hipGetLastError());
@@ -1084,7 +1083,7 @@ extern "C" int32_t jch_lwplsr_prepare(jch_ctx *ctx, int32_t loc, const double *X
     const double *dX = Xtrain;
     int64_t ldxd = ldx;
     if (loc == JCH_LOC_HOST) {   // stage the column-major X once, transpose on the device
-        int32_t st = jch_reserve(ctx, ctx->xstage, sizeof(double) * (size_t)n * p);
+        int32_t st = jch_reserve_xstage(ctx, sizeof(double) * (size_t)n * p);
         if (st != JCH_OK) return fail(st);
         if (hipMemcpy2DAsync(ctx->xstage.ptr, sizeof(double) * n, Xtrain, sizeof(double) * ldx, sizeof(double) * n, p, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
             return fail(jch_fail(ctx, JCH_EHIP, "jch_lwplsr_prepare: copy of X failed"));
@@ -1222,8 +1221,7 @@ extern "C" int32_t jch_weighted_cov(jch_ctx *ctx, int32_t loc, const double *A, 
         }
     }
     JCH_TRY(jch_reserve(ctx, ctx->dnorm, sizeof(double) * (size_t)n));
-    ctx->xcopy_valid = false;   // (the fit workspace's row-major copy is overwritten here)
-    JCH_TRY(jch_reserve(ctx, ctx->xr, sizeof(double) * (size_t)n * ldr));
+    JCH_TRY(jch_reserve_xr(ctx, sizeof(double) * (size_t)n * ldr));   // (the fit workspace's row-major copy is overwritten here)
     if (d > JCH_MAXQ) {
         // wide A (round 4; the Mahalanobis branch of getknn on raw spectra, nlvdis = 0: src/getknn.jl:37-49, src/lwplsr.jl:21): the
         // centred row-major copy from K2 (with A's first column standing in for Y), then the tiled MFMA SYRK of kern2.hip on it

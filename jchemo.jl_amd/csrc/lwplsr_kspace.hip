@@ -663,7 +663,7 @@ static int32_t launch_ks(jch_ctx *ctx, locw_args &g)
     const int rounds = (g.m + ctx->cus - 1) / ctx->cus;
     const int nb = std::min(ctx->cus, (g.m + rounds - 1) / rounds);
     g.slab = ((size_t)std::max(g.ldr, 16 + KS_KP) + 31) & ~(size_t)31;
-    JCH_TRY(jch_reserve(ctx, ctx->xstage, sizeof(double) * g.slab * nb));
+    JCH_TRY(jch_reserve_xstage(ctx, sizeof(double) * g.slab * nb));   // (slab scratch in the staging buffer of a host-array fit)
     g.scratch = (double *)ctx->xstage.ptr;
     hipLaunchKernelGGL((k_locw_kspace<Q>), dim3(nb), dim3(KS_NT), lds, ctx->stream, g);
     JCH_HIP(ctx, hipGetLastError());
