@@ -612,6 +612,45 @@ JCH_API int32_t jch_chol_factor(jch_ctx *ctx, double *A, int64_t n, int64_t lda,
 JCH_API int32_t jch_chol_solve(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *B, int64_t q, int64_t ldb);
 JCH_API int32_t jch_chol_inv_fro2(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *out);
 
+/* ---- the k-nearest-neighbour search on its own, and the reductions over a neighbourhood (src/getknn.jl, src/knnr.jl, src/knnda.jl,
+ * src/occknndis.jl, src/occlknndis.jl) -------------------------------------------------------------------------------------------
+ * jch_knn_prepare -- a handle on a search space Ztrain (n x dd, ldzt >= n) [loc]: the device copy of it and, where the screened search can apply
+ *   (dd <= 62, n < 2^26), the screen's operand copy, built once.  jch_knn_release frees it (NULL is allowed).
+ * jch_knn_search -- the k nearest rows of the search space for each of the m rows of Zq (m x dd, ldzq >= m) [loc], in (distance, row index) order:
+ *   exactly the search of jch_lwplsr_predict (the screened search on the bf16 matrix cores with exact Float64 distances for the survivors, the exact
+ *   scan, or the generic selection outside their envelopes: any n, dd, k; JCH_KNN_SCREEN=0 / JCH_KNN_GENERIC=1 choose as they do there), without
+ *   the local fits.  Outputs [out_loc], each may be NULL: ind (int32, 0-based, [m][k] row-major), dist and w ([m][k]: Euclidean distances, not
+ *   squared, and the `wdist` weights exp(-d / (h MAD)) / max with the 4-MAD cutoff, NaN -> 1, then clamped from below to tol, src/wdist.jl:64-75;
+ *   h = Inf is valid: all weights 1 before the clamp), dmed ([m]: the median of the query's k distances, Julia's middle(lo, hi) = lo / 2 + hi / 2
+ *   for even k).  k is clamped to the number of candidates: n, or n - 1 when `self` is given (the caller sizes the outputs with the clamped k).
+ *   self: NULL, or [m] int64 [loc]; self[i] >= 0 removes training row self[i] from query i's candidates -- the reference's
+ *   getknn(rmrow(T, s), ...) without the copy, rows reported in the ORIGINAL numbering.  Done as a search for k + 1 followed by the drop of the
+ *   entry of row self[i] if it is among them and of the last entry otherwise (also for self[i] < 0); weights and dmed are computed after the drop,
+ *   over the k kept distances.  A query holding a NaN gets NaN distances, the in-range rows 0 .. k-1 and weights 1, and disturbs no other query.
+ *   With loc and out_loc both JCH_LOC_DEVICE the call only enqueues on the ctx stream; otherwise it returns synchronised.  The screen counters
+ *   (JCH_COUNTER_KNN_SCREENED / _REDONE) and the handle's "stop screening" rule follow host-output calls only.  One rank only.
+ * jch_knn_wmean -- pred[i, c] = sum_j (w_ij / sum_j w_ij) Y[ind_ij, c] (`mweight` + `colmean`, src/knnr.jl:120-124).  Y n x q (ldy >= n), ind and w
+ *   [m][k], pred m x q column-major (ld m), all [loc].  Fixed summation order (per query one wave: lane l adds the terms l, l + 64, ... in order, the
+ *   64 partial sums combine in a fixed butterfly), no atomics: two runs give identical bits.  Error per element <= 4 (k + 4) 2^-53 sum_j w~_ij |y_ij|.
+ *   A NaN stays in its query.  A row index outside [0, n) contributes NaN.
+ * jch_knn_vote -- score[i, c] = sum of w_ij over the neighbours j with cls[ind_ij] = c, in neighbour order (m x ncls column-major, ld m; may be NULL;
+ *   0 for an absent class); pred[i] (int32) = the class with the largest score among those PRESENT in the neighbourhood, ties to the lowest code
+ *   (`findmax_cla`, src/utility.jl:564-570).  cls: [n] int32 class codes, 0-based in sorted-level order; codes outside [0, ncls) are ignored.  Any
+ *   ncls >= 1.  All arrays [loc].
+ * jch_knn_gather_median -- out[i] = median_j v[ind_ij], middle(lo, hi) for even k; NaN sorts last and the median is NaN if a middle place is.
+ *   v (n), ind [m][k], out (m), all [loc].  Any k.
+ * The last three only enqueue on the ctx stream when loc is JCH_LOC_DEVICE. */
+typedef struct jch_knn_model jch_knn_model;
+JCH_API int32_t jch_knn_prepare(jch_ctx *ctx, int32_t loc, const double *Ztrain, int64_t n, int64_t dd, int64_t ldzt, jch_knn_model **model_out);
+JCH_API int32_t jch_knn_release(jch_ctx *ctx, jch_knn_model *model);
+JCH_API int32_t jch_knn_search(jch_ctx *ctx, const jch_knn_model *model, int32_t loc, const double *Zq, int64_t m, int64_t ldzq, int32_t k,
+                               const int64_t *self, double h, double tol, int32_t out_loc, int32_t *ind, double *dist, double *w, double *dmed);
+JCH_API int32_t jch_knn_wmean(jch_ctx *ctx, int32_t loc, const double *Y, int64_t n, int64_t q, int64_t ldy, const int32_t *ind, const double *w,
+                              int64_t m, int32_t k, double *pred);
+JCH_API int32_t jch_knn_vote(jch_ctx *ctx, int32_t loc, const int32_t *cls, int64_t n, int32_t ncls, const int32_t *ind, const double *w, int64_t m,
+                             int32_t k, int32_t *pred, double *score);
+JCH_API int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double *v, int64_t n, const int32_t *ind, int64_t m, int32_t k, double *out);
+
 typedef struct jch_profile {
     double fit_ms;        /* device time of the last fit, first kernel -> last kernel (HIP events)   */
     double prologue_ms;   /* weights + means (+ var) + centre/transpose/XtY                           */
@@ -643,6 +682,9 @@ typedef struct jch_profile {
  * made, sweep_launches = the launches made; JCH_COUNTER_SWEEPS_TIMED counts the launches actually bracketed. */
 JCH_API int32_t jch_ctx_set_profiling(jch_ctx *ctx, int32_t enable);
 JCH_API int32_t jch_ctx_get_profile(const jch_ctx *ctx, jch_profile *out);
+/* Waits for everything queued on the ctx stream: what a caller of an entry that "only enqueues" (jch_col_median_mad and jch_knn_* with device
+ * inputs and outputs) does before it reads the results on another stream or on the host. */
+JCH_API int32_t jch_ctx_synchronize(jch_ctx *ctx);
 
 /* jch_ctx_allreduce_probe — diagnostic: all-reduce (sum) the `count` doubles of `vec` (HOST, in/out) `iters` times
  * back to back through ONE named transport and report the average time per all-reduce in microseconds (HIP events on

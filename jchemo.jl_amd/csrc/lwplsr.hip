@@ -847,6 +847,42 @@ int32_t jch_launch_knn_scan(jch_ctx *ctx, knn_args a, jch_buf &cbuf)
     return JCH_OK;
 }
 
+// The search of one call (lw_run and jch_knn_search, knn.hip): the screened search, the exact scan or the generic selection, by shape and knobs.
+// scr: the model's operand copy for the screen, or null (rebuilt in the ctx workspace); screen_off: the model's "stop screening" flag, or null;
+// *sflags_out: the screen's per-query "redone by the exact selection" flags (device, in ctx->lw_flags at [m, 2 m)), null when another path ran.
+int32_t jch_knn_dispatch(jch_ctx *ctx, knn_args a, const knn_screen *scr, const bool *screen_off, int **sflags_out)
+{
+    const int64_t n = a.n;
+    const int m = a.m, dd = a.dd, k = a.k;
+    *sflags_out = nullptr;
+    const size_t lds = jch_knn_scan_lds(dd);
+    // outside the scan's envelope (k beyond the candidate buffers, a search space too wide for its LDS, 2^29 rows): the generic
+    // selection, one workgroup per query (lwplsr_generic.hip); JCH_KNN_GENERIC=1 forces it (tests)
+    const bool knn_generic = jch_knob("JCH_KNN_GENERIC", 0) == 1;
+    // the screened kNN (lwplsr_screen.hip: all pairs in f32 on the matrix cores, exact distances for the survivors only) when the
+    // shape is inside its envelope; JCH_KNN_SCREEN=0 selects the exact scan below (A/B runs, tests)
+    const bool screen = !knn_generic && jch_knob("JCH_KNN_SCREEN", 1) != 0 && !(screen_off && *screen_off) && jch_knn_screen_shape_ok(n, dd, k);
+    if (screen) {
+        knn_screen local;
+        if (!scr) {   // one-shot call: the model-constant operand copy is rebuilt in the ctx workspace
+            JCH_TRY(jch_reserve(ctx, ctx->lw_screen, jch_knn_screen_model_bytes(n, dd)));
+            JCH_TRY(jch_knn_screen_build(ctx, a.Zt, a.ldzt, n, dd, ctx->lw_screen.ptr, &local));
+            scr = &local;
+        }
+        // (one reservation for both flag arrays of a call: the neighbour-space kernel's pivot flags [0, m), the screen's [m, 2 m))
+        JCH_TRY(jch_reserve(ctx, ctx->lw_flags, sizeof(int) * 2 * (size_t)m + 256));
+        int *sflags = (int *)ctx->lw_flags.ptr + (size_t)m;
+        JCH_TRY(jch_launch_knn_screen(ctx, a, *scr, sflags));
+        *sflags_out = sflags;
+    } else
+    if (k > KNN_CAP - 256 || lds > 150 * 1024 || n >= ((int64_t)1 << 29) || knn_generic) {
+        JCH_TRY(jch_launch_knn_generic(ctx, a));
+    } else {
+        JCH_TRY(jch_launch_knn_scan(ctx, a, ctx->gemm_b));
+    }
+    return JCH_OK;
+}
+
 // kNN + weights + batched local fits on device-resident pieces; results to the host.  Xrm / dY / dZt: the model; dZq, dXq: the queries.
 static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64_t p, const double *dY, int64_t q, int64_t ldyd,
                       const double *dZt, int64_t ldztd, const double *dZq, int64_t ldzqd, int64_t dd, const double *dXq, int64_t m,
@@ -866,30 +902,7 @@ static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64
         knn_args a;
         a.Zt = dZt; a.ldzt = ldztd; a.n = n; a.Zq = dZq; a.ldzq = ldzqd; a.m = (int)m; a.dd = (int)dd; a.k = k;
         a.h = h; a.cri = 4.0; a.tol = tol; a.ind = dind; a.dist = ddist; a.w = dw;
-        const size_t lds = jch_knn_scan_lds((int)dd);
-        // outside the scan's envelope (k beyond the candidate buffers, a search space too wide for its LDS, 2^29 rows): the generic
-        // selection, one workgroup per query (lwplsr_generic.hip); JCH_KNN_GENERIC=1 forces it (tests)
-        const bool knn_generic = jch_knob("JCH_KNN_GENERIC", 0) == 1;
-        // the screened kNN (lwplsr_screen.hip: all pairs in f32 on the matrix cores, exact distances for the survivors only) when the
-        // shape is inside its envelope; JCH_KNN_SCREEN=0 selects the exact scan below (A/B runs, tests)
-        const bool screen = !knn_generic && jch_knob("JCH_KNN_SCREEN", 1) != 0 && !(screen_off && *screen_off) && jch_knn_screen_shape_ok(n, (int)dd, k);
-        if (screen) {
-            knn_screen local;
-            if (!scr) {   // one-shot call: the model-constant operand copy is rebuilt in the ctx workspace
-                JCH_TRY(jch_reserve(ctx, ctx->lw_screen, jch_knn_screen_model_bytes(n, (int)dd)));
-                JCH_TRY(jch_knn_screen_build(ctx, dZt, ldztd, n, (int)dd, ctx->lw_screen.ptr, &local));
-                scr = &local;
-            }
-            // (one reservation for both flag arrays of a call: the neighbour-space kernel's pivot flags [0, m), the screen's [m, 2 m))
-            JCH_TRY(jch_reserve(ctx, ctx->lw_flags, sizeof(int) * 2 * (size_t)m + 256));
-            sflags = (int *)ctx->lw_flags.ptr + (size_t)m;
-            JCH_TRY(jch_launch_knn_screen(ctx, a, *scr, sflags));
-        } else
-        if (k > KNN_CAP - 256 || lds > 150 * 1024 || n >= ((int64_t)1 << 29) || knn_generic) {
-            JCH_TRY(jch_launch_knn_generic(ctx, a));
-        } else {
-        JCH_TRY(jch_launch_knn_scan(ctx, a, ctx->gemm_b));
-        }
+        JCH_TRY(jch_knn_dispatch(ctx, a, scr, screen_off, &sflags));
     }
     ev2 = jch_ev(ctx);
     // neighbours, distances and weights are final here: their copies to the host (3.2 MB at cfg5, into pages of the caller's

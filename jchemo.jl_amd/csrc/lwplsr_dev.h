@@ -63,6 +63,8 @@ void jch_lw_to_rowmajor(jch_ctx *ctx, const double *dX, int64_t ldxd, int64_t n,
 // lwplsr.hip: the exact scan (k <= 768, LDS for the score space: jch_knn_scan_lds <= 150 KB)
 size_t jch_knn_scan_lds(int dd);
 int32_t jch_launch_knn_scan(jch_ctx *ctx, knn_args a, jch_buf &cbuf);
+// lwplsr.hip: the search of one call — screen, scan or generic selection by shape and knobs (lw_run; jch_knn_search, knn.hip)
+int32_t jch_knn_dispatch(jch_ctx *ctx, knn_args a, const knn_screen *scr, const bool *screen_off, int **sflags_out);
 
 // lwplsr_generic.hip: the paths WITHOUT shape limits (any k <= n, any p, q, nlv) behind the batched kernels' envelope.
 // kNN + weights of all m queries: exact selection of the k smallest distances per query, (distance, index) order, wdist weights
@@ -159,15 +161,15 @@ __device__ __forceinline__ void knn_sort64_lanes(double &kv, int &iv)
         }
 }
 
-// The tail shared by the finishing kernels (k_knn_finish, k_knn_finish_screen): okey / oidx [kk] hold the query's nearest squared
-// distances and rows in (distance, index) order (sentinels +inf / 0x7fffffff where fewer than kk were found); writes the neighbour
-// list, the distances and the wdist weights (src/wdist.jl:64-75).  256 threads; key: scratch of >= kk doubles; every thread calls.
-__device__ static void knn_finish_tail(const knn_args &g, int qi, int kk, double *key, double *okey, int *oidx, double *sred, double *smed, int *snn)
+// The tail shared by the finishing kernels (k_knn_finish, k_knn_finish_screen), in two parts the callers run back to back.  okey / oidx [kk] hold the
+// query's nearest squared distances and rows in (distance, index) order (sentinels +inf / 0x7fffffff where fewer than kk were found).
+// Part 1, knn_tail_holes: writes the neighbour list and the distances, and leaves the distances (square-rooted) in okey.  256 threads; every thread calls.
+__device__ static void knn_tail_holes(const knn_args &g, int qi, int kk, double *okey, const int *oidx)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int k = g.k;
     int *oi = g.ind + (size_t)qi * k;
-    double *od = g.dist + (size_t)qi * k, *ow = g.w + (size_t)qi * k;
+    double *od = g.dist + (size_t)qi * k;
     // fewer than k candidates with a finite distance (NaN / Inf in the query's or the training scores: no comparison
     // against the bar ever holds): the empty places keep the sentinel index.  They are given the in-range row `e` and a
     // NaN distance — wdist then yields weights 1 for the query exactly as the reference's arithmetic does (every
@@ -179,7 +181,12 @@ __device__ static void knn_finish_tail(const knn_args &g, int qi, int kk, double
         okey[e] = dv;
         od[e] = dv;
     }
-    __syncthreads();
+}
+// Part 2, knn_tail_wdist: the wdist weights (src/wdist.jl:64-75) of the kk distances okey (not squared, ascending, NaN last; any address space) into
+// ow [kk].  key: scratch of >= kk doubles; sred [8], smed [2], snn [4]: LDS.  256 threads; every thread calls, behind a barrier after okey was written.
+__device__ static void knn_tail_wdist(double h, double cri, double tol, int kk, double *key, const double *okey, double *ow, double *sred, double *smed, int *snn)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // wdist (src/wdist.jl:64-75): median, MAD, cutoff, exp weights, / max, NaN -> 1, then the tol clamp
     const double med = (kk & 1) ? okey[kk / 2] : 0.5 * (okey[kk / 2 - 1] + okey[kk / 2]);
     // the median of |d - med|: the values at the places t0, t1 of the kk deviations in ascending order, NaN last.
@@ -235,14 +242,14 @@ __device__ static void knn_finish_tail(const knn_args &g, int qi, int kk, double
     }
     __syncthreads();
     const double zmad = 1.4826 * ((kk & 1) ? smed[1] : 0.5 * (smed[0] + smed[1]));
-    const double cutoff = med + g.cri * zmad;
+    const double cutoff = med + cri * zmad;
     // weights; max with NaN propagation (Julia's `maximum` returns NaN if any NaN is present)
     double wmax = -__builtin_inf();
     int anynan = 0;
     __syncthreads();                                           // (key: the deviations are done with, the weights go there)
     for (int e = tid; e < kk; e += 256) {
         const double dv = okey[e];
-        const double wv_ = dv <= cutoff ? exp(-dv / (g.h * zmad)) : 0.0;
+        const double wv_ = dv <= cutoff ? exp(-dv / (h * zmad)) : 0.0;
         key[e] = wv_;
         if (wv_ != wv_) anynan = 1;
         else if (wv_ > wmax) wmax = wv_;
@@ -255,8 +262,34 @@ __device__ static void knn_finish_tail(const knn_args &g, int qi, int kk, double
     for (int e = tid; e < kk; e += 256) {
         double wv_ = key[e] / wmax;
         if (wv_ != wv_) wv_ = 1.0;
-        if (wv_ < g.tol) wv_ = g.tol;
+        if (wv_ < tol) wv_ = tol;
         ow[e] = wv_;
     }
+}
+__device__ static void knn_finish_tail(const knn_args &g, int qi, int kk, double *key, double *okey, int *oidx, double *sred, double *smed, int *snn)
+{
+    knn_tail_holes(g, qi, kk, okey, oidx);
+    __syncthreads();
+    knn_tail_wdist(g.h, g.cri, g.tol, kk, key, okey, g.w + (size_t)qi * g.k, sred, smed, snn);
+}
+
+// ascending bitonic sort of cap (power of two) (key, idx) pairs by (key, idx), NaN last; any address space; 256 threads
+__device__ static void kg_bitonic(double *key, int *idx, int cap)
+{
+    const int tid = threadIdx.x;
+    for (int size = 2; size <= cap; size <<= 1) {
+        for (int stride = size >> 1, ls = 31 - __builtin_clz(size >> 1); stride > 0; stride >>= 1, --ls) {
+            __syncthreads();
+            for (int t = tid; t < cap / 2; t += 256) {
+                const int lo = ((t >> ls) << (ls + 1)) | (t & (stride - 1)), hi = lo + stride;
+                const bool up = ((lo & size) == 0);
+                const double a = key[lo], b = key[hi];
+                const int ia = idx[lo], ib = idx[hi];
+                const bool gt = (a > b) || (a == b && ia > ib) || (a != a && b == b);
+                if (gt == up) { key[lo] = b; key[hi] = a; idx[lo] = ib; idx[hi] = ia; }
+            }
+        }
+    }
+    __syncthreads();
 }
 #endif

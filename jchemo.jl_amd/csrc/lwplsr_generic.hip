@@ -23,26 +23,7 @@
 
 #define KG_NT 256
 
-// ascending bitonic sort of cap (power of two) (key, idx) pairs by (key, idx), NaN last; any address space; KG_NT threads
-__device__ static void kg_bitonic(double *key, int *idx, int cap)
-{
-    const int tid = threadIdx.x;
-    for (int size = 2; size <= cap; size <<= 1) {
-        for (int stride = size >> 1, ls = 31 - __builtin_clz(size >> 1); stride > 0; stride >>= 1, --ls) {
-            __syncthreads();
-            for (int t = tid; t < cap / 2; t += KG_NT) {
-                const int lo = ((t >> ls) << (ls + 1)) | (t & (stride - 1)), hi = lo + stride;
-                const bool up = ((lo & size) == 0);
-                const double a = key[lo], b = key[hi];
-                const int ia = idx[lo], ib = idx[hi];
-                const bool gt = (a > b) || (a == b && ia > ib) || (a != a && b == b);
-                if (gt == up) { key[lo] = b; key[hi] = a; idx[lo] = ib; idx[hi] = ia; }
-            }
-        }
-    }
-    __syncthreads();
-}
-
+// (kg_bitonic, the any-address-space sort: lwplsr_dev.h — shared with knn.hip; KG_NT == 256 threads)
 struct kg_scratch {
     double *d2;     // [nblk][n]
     double *skey;   // [nblk][K2]

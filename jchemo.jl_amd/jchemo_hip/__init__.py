@@ -11,3 +11,5 @@ from .pca import Pca, Pcr, pca_summary, pca_transform, pcaeigen, pcaeigen_, pcae
 from .occ import Occod, OccPred, Occsd, Occsdod, occ_predict, occod, occsd, occsdod, row_resid_ss  # noqa: F401
 from .stah import Occstah, Stah, col_median_mad, colmad, occstah, stah  # noqa: F401
 from .samp import Samp, Sampcla, Sampdp, farthest_pair, maxmin_select, sampcla, sampdp, sampks, sampsys  # noqa: F401
+from .knn import (KnnPred, Knnda, Knnr, Occknndis, Occlknndis, getknn, knn_gather_median, knn_prepare, knn_release, knn_search, knn_vote, knn_wmean,  # noqa: F401
+                  knnda, knnda_predict, knnr, knnr_predict, occknn_predict, occknndis, occlknndis)

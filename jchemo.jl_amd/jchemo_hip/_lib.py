@@ -35,6 +35,7 @@ SYMBOLS = (
     "jch_rows_standardize", "jch_rows_project_out", "jch_rows_fir", "jch_covsel_fit", "jch_covsel_pass",
     "jch_xtdx", "jch_pca_fit", "jch_row_resid_ss", "jch_col_median_mad", "jch_stah",
     "jch_farthest_pair", "jch_maxmin_select",
+    "jch_knn_prepare", "jch_knn_release", "jch_knn_search", "jch_knn_wmean", "jch_knn_vote", "jch_knn_gather_median", "jch_ctx_synchronize",
 )
 
 
@@ -138,8 +139,15 @@ def load():
     L.jch_stah.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, dp, i64, i64, i32, dp, dp, dp]
     L.jch_farthest_pair.argtypes = [vp, i32, dp, i64, i64, i64, dp, i32, dp, dp]
     L.jch_maxmin_select.argtypes = [vp, i32, dp, i64, i64, i64, i32, dp, i64, dp, dp]
+    L.jch_knn_prepare.argtypes = [vp, i32, dp, i64, i64, i64, C.POINTER(vp)]
+    L.jch_knn_release.argtypes = [vp, vp]
+    L.jch_knn_search.argtypes = [vp, vp, i32, dp, i64, i64, i32, dp, f64, f64, i32, dp, dp, dp, dp]
+    L.jch_knn_wmean.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i32, dp]
+    L.jch_knn_vote.argtypes = [vp, i32, dp, i64, i32, dp, dp, i64, i32, dp, dp]
+    L.jch_knn_gather_median.argtypes = [vp, i32, dp, i64, dp, i64, i32, dp]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]
     L.jch_ctx_set_profiling.argtypes = [vp, i32]
+    L.jch_ctx_synchronize.argtypes = [vp]
     L.jch_ctx_get_profile.argtypes = [vp, C.POINTER(Profile)]
     L.jch_ctx_get_counter.argtypes = [vp, i32, C.POINTER(i64)]
     L.jch_ctx_allreduce_probe.argtypes = [vp, i32, dp, i64, i32, C.POINTER(C.c_double)]
@@ -233,6 +241,10 @@ class Context:
         us = C.c_double(0.0)
         self.check(load().jch_ctx_allreduce_probe(self._h, transport, v.ctypes.data, v.size, iters, C.byref(us)))
         return v, float(us.value)
+
+    def synchronize(self):
+        """Waits for everything queued on the ctx stream (jch_ctx_synchronize)."""
+        self.check(load().jch_ctx_synchronize(self._h))
 
     def profile(self) -> Profile:
         pr = Profile()

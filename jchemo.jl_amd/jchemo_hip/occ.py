@@ -314,6 +314,9 @@ def occ_predict(obj, X, *, ctx: Optional[Context] = None) -> OccPred:
     if kind == "Occstah":
         from .stah import _predict_stah
         return _predict_stah(obj, X, ctx)
+    if kind in ("Occknndis", "Occlknndis"):
+        from .knn import occknn_predict
+        return occknn_predict(obj, X, ctx=ctx)
     if kind == "Occsd":
         tab = _predict_sd(obj, X, ctx)
     elif kind == "Occod":

@@ -428,13 +428,17 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
     value -> matrix, several -> list of matrices.  All values are computed in ONE pass over X.
     `rank` / `world` (kNN-LWPLSR only): split the queries over `world` replicas, see lwplsr_predict.
     A Covselr model: src/covselr.jl:61-64 (covselr_predict).  An Occsd, Occod or Occsdod model: src/occsd.jl:153-164, src/occod.jl:65-75,
-    src/occsdod.jl:60-74; an Occstah model: src/occstah.jl:55-73 (occ_predict)."""
+    src/occsdod.jl:60-74; an Occstah model: src/occstah.jl:55-73 (occ_predict).  A Knnr or Knnda model: src/knnr.jl:137-169, src/knnda.jl:108-138; an
+    Occknndis or Occlknndis model: src/occknndis.jl:157-171, src/occlknndis.jl:173-199 (knn.py)."""
     if type(fm).__name__ == "Covselr":
         from .covsel import covselr_predict
         return covselr_predict(fm, X, ctx=ctx)
     if type(fm).__name__ in ("Occsd", "Occod", "Occsdod", "Occstah"):
         from .occ import occ_predict
         return occ_predict(fm, X, ctx=ctx)
+    if type(fm).__name__ in ("Knnr", "Knnda", "Occknndis", "Occlknndis"):
+        from . import knn
+        return {"Knnr": knn.knnr_predict, "Knnda": knn.knnda_predict}.get(type(fm).__name__, knn.occknn_predict)(fm, X, ctx=ctx)
     if isinstance(fm, Lwplsr):
         return lwplsr_predict(fm, X, nlv=nlv, ctx=ctx, rank=rank, world=world)
     if isinstance(fm, Plsrda):

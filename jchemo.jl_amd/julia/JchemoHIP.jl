@@ -39,7 +39,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Pca, Pcr, pcasvd, pcasvd!, pcaeigen, pcaeigen!, pcaeigenk, pcaeigenk!, pcr, pcr!, xtdx,
        Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss,
        Occstah, occstah, stah, colmad, col_median_mad,
-       sampks, sampdp, sampsys, sampcla, farthest_pair, maxmin_select
+       sampks, sampdp, sampsys, sampcla, farthest_pair, maxmin_select,
+       Knnr, Knnda, Occknndis, Occlknndis, getknn, knnr, knnda, occknndis, occlknndis, knn_search, knn_wmean, knn_vote, knn_gather_median
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -1956,6 +1957,223 @@ function sampcla(x, y = nothing; k, seed = nothing)
         end
     end
     (train = s, test = setdiff(1:n, s), lev = lev, ni = ni, k = kk)
+end
+
+# ---- the kNN search on its own and what the reference builds on it (src/getknn.jl, src/knnr.jl, src/knnda.jl, src/occknndis.jl,
+# src/occlknndis.jl; DESIGN.md 20).  Row indices are 1-based here; the C ABI is 0-based.  NOT EXECUTED in the build image (no Julia toolchain).
+mutable struct KnnHandle
+    h::Ptr{Cvoid}                # jch_knn_model*
+    n::Int
+    ctx::JchCtx
+end
+function knn_release!(kh::KnnHandle)
+    kh.h == C_NULL && return nothing
+    ccall((:jch_knn_release, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), C_NULL, kh.h)
+    kh.h = C_NULL
+    nothing
+end
+"`knn_prepare(Zt)`: the device handle of a search space (jch_knn_prepare); released by the GC or `knn_release!`."
+function knn_prepare(Zt; ctx = default_ctx())
+    Zt = _in(Zt); n, dd = size(Zt)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve Zt check(ctx, ccall((:jch_knn_prepare, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ref{Ptr{Cvoid}}),
+        ctx.h, _loc(Zt), pointer(Zt), n, dd, max(stride(Zt, 2), n), r))
+    kh = KnnHandle(r[], n, ctx)
+    finalizer(knn_release!, kh)
+    kh
+end
+
+"""`knn_search(kh, Zq, k; self = nothing, h = Inf, tol = 0)` — jch_knn_search with host outputs: (ind, d, w, dmed); ind, d, w are k x m (one column
+per query, the C layout [m][k]), rows 1-based.  `self`: one training row per query (0: none) that is taken out of that query's candidates."""
+function knn_search(kh::KnnHandle, Zq, k; self = nothing, h = Inf, tol = 0.0)
+    ctx = kh.ctx
+    Zq = _in(Zq); m = size(Zq, 1)
+    k = min(Int(k), self === nothing ? kh.n : kh.n - 1)
+    k >= 1 || throw(ArgumentError("k = $k must be >= 1"))
+    sr = self === nothing ? Int64[] : Vector{Int64}(collect(self) .- 1)
+    srd = (self === nothing || Zq isa Array) ? sr : copyto!(similar(Zq, Int64, m), sr)
+    ind = zeros(Int32, k, m); dist = zeros(k, m); w = zeros(k, m); dmed = zeros(m)
+    GC.@preserve Zq srd ind dist w dmed begin
+        check(ctx, ccall((:jch_knn_search, LIB), Int32,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int32, Ptr{Int64}, Float64, Float64, Int32, Ptr{Int32}, Ptr{Float64},
+                          Ptr{Float64}, Ptr{Float64}),
+                         ctx.h, kh.h, _loc(Zq), pointer(Zq), m, max(stride(Zq, 2), m), Int32(k), self === nothing ? Ptr{Int64}(C_NULL) : pointer(srd),
+                         Float64(h), Float64(tol), Int32(0), pointer(ind), pointer(dist), pointer(w), pointer(dmed)))
+    end
+    (ind = Int.(ind) .+ 1, d = dist, w = w, dmed = dmed)
+end
+
+"`knn_wmean(Y, ind, w)` — jch_knn_wmean on host arrays: m x q, row i = sum_j (w[j, i] / sum_j w[j, i]) Y[ind[j, i], :]; ind, w: k x m."
+function knn_wmean(Y, ind, w; ctx = default_ctx())
+    Y = Matrix{Float64}(Array(_in(Y))); n, q = size(Y); k, m = size(ind)
+    i0 = Matrix{Int32}(ind .- 1); wm = Matrix{Float64}(w); pred = zeros(m, q)
+    GC.@preserve Y i0 wm pred begin
+        check(ctx, ccall((:jch_knn_wmean, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int32}, Ptr{Float64}, Int64, Int32, Ptr{Float64}),
+                         ctx.h, Int32(0), pointer(Y), n, q, n, pointer(i0), pointer(wm), m, Int32(k), pointer(pred)))
+    end
+    pred
+end
+
+"`knn_vote(cls, ncls, ind, w)` — jch_knn_vote on host arrays: (pred, score); cls: class codes 1 .. ncls of the n training rows; ties go to the lowest code."
+function knn_vote(cls, ncls, ind, w; ctx = default_ctx())
+    c0 = Vector{Int32}(vec(cls) .- 1); n = length(c0); k, m = size(ind)
+    i0 = Matrix{Int32}(ind .- 1); wm = Matrix{Float64}(w); pred = zeros(Int32, m); score = zeros(m, ncls)
+    GC.@preserve c0 i0 wm pred score begin
+        check(ctx, ccall((:jch_knn_vote, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Int32}, Int64, Int32, Ptr{Int32}, Ptr{Float64}, Int64, Int32, Ptr{Int32}, Ptr{Float64}),
+                         ctx.h, Int32(0), pointer(c0), n, Int32(ncls), pointer(i0), pointer(wm), m, Int32(k), pointer(pred), pointer(score)))
+    end
+    (pred = Int.(pred) .+ 1, score = score)
+end
+
+"`knn_gather_median(v, ind)` — jch_knn_gather_median on host arrays: the median of v[ind[:, i]] per query, `middle` for even k, NaN last."
+function knn_gather_median(v, ind; ctx = default_ctx())
+    vv = Vector{Float64}(vec(v)); n = length(vv); k, m = size(ind)
+    i0 = Matrix{Int32}(ind .- 1); out = zeros(m)
+    GC.@preserve vv i0 out begin
+        check(ctx, ccall((:jch_knn_gather_median, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Int32, Ptr{Float64}),
+                         ctx.h, Int32(0), pointer(vv), n, pointer(i0), m, Int32(k), pointer(out)))
+    end
+    out
+end
+
+_knn_lists(res) = (listnn = [res.ind[:, i] for i in 1:size(res.ind, 2)], listd = [res.d[:, i] for i in 1:size(res.d, 2)],
+                   listw = [res.w[:, i] for i in 1:size(res.w, 2)])
+
+"""`getknn(Xtrain, X; k = 1, metric = "eucl")` — src/getknn.jl:29-57: (ind, d) as lists, one vector per query, in (distance, row) order."""
+function getknn(Xtrain, X; k = 1, metric = "eucl", ctx = default_ctx())
+    Xt = _in(Xtrain); X = _in(X)
+    Zt, qmap, _ = _knn_train_space((fm = nothing, scal = false, metric = metric), Xt, ctx)
+    kh = knn_prepare(Zt; ctx = ctx)
+    res = knn_search(kh, qmap(X), k)
+    knn_release!(kh)
+    l = _knn_lists(res)
+    (ind = l.listnn, d = l.listd)
+end
+
+struct Knnr                       # src/knnr.jl:1-11
+    X; Y; fm; nlvdis::Int; metric::String; h::Real; k::Int; tol::Real; scal::Bool
+end
+struct Knnda                      # src/knnda.jl:1-13
+    X; y; fm; nlvdis::Int; metric::String; h::Real; k::Int; tol::Real; lev; ni; scal::Bool
+end
+"`knnr(X, Y; nlvdis = 0, metric = \"eucl\", h = Inf, k = 1, tol = 1e-4, scal = false)` — src/knnr.jl:119-130."
+function knnr(X, Y; nlvdis = 0, metric = "eucl", h = Inf, k = 1, tol = 1e-4, scal = false, ctx = default_ctx())
+    X = _in(X); Y = _in(Y)
+    fm = nlvdis == 0 ? nothing : plskern(X, Y; nlv = nlvdis, scal = scal, ctx = ctx)
+    Knnr(X, Y, fm, nlvdis, metric, h, k, tol, scal)
+end
+"`knnda(X, y; nlvdis = 0, metric = \"eucl\", h = Inf, k = 1, tol = 1e-4, scal = false)` — src/knnda.jl:87-100."
+function knnda(X, y; nlvdis = 0, metric = "eucl", h = Inf, k = 1, tol = 1e-4, scal = false, ctx = default_ctx())
+    X = _in(X); res = dummy(y); yv = vec(Array(y))
+    ni = [count(==(l), yv) for l in res.lev]
+    fm = nlvdis == 0 ? nothing : plskern(X, _colocate_mat(res.Y, X); nlv = nlvdis, scal = scal, ctx = ctx)
+    Knnda(X, y, fm, nlvdis, metric, h, k, tol, res.lev, ni, scal)
+end
+function _knn_model_search(object, X, ctx)       # src/knnr.jl:142-160: the search space of lwplsr, one search with the weights
+    Xt = _in(object.X); X = _in(X)
+    Zt, qmap, _ = _knn_train_space(object, Xt, ctx)
+    kh = knn_prepare(Zt; ctx = ctx)
+    res = knn_search(kh, qmap(X), object.k; h = object.h, tol = object.tol)
+    knn_release!(kh)
+    res
+end
+"`predict(object::Knnr, X)` — src/knnr.jl:137-169."
+function predict(object::Knnr, X; ctx = default_ctx())
+    res = _knn_model_search(object, X, ctx)
+    merge((pred = knn_wmean(object.Y, res.ind, res.w; ctx = ctx),), _knn_lists(res))
+end
+"`predict(object::Knnda, X)` — src/knnda.jl:108-138."
+function predict(object::Knnda, X; ctx = default_ctx())
+    res = _knn_model_search(object, X, ctx)
+    yv = vec(Array(object.y))
+    cls = [searchsortedfirst(object.lev, v) for v in yv]
+    code = knn_vote(cls, length(object.lev), res.ind, res.w; ctx = ctx).pred
+    merge((pred = reshape(object.lev[code], :, 1),), _knn_lists(res))
+end
+
+struct Occknndis                  # src/occknndis.jl:1-9 (e_cdf: the sorted training d), then the search handle
+    d; fm; T; tscales; k::Int; e_cdf; cutoff::Float64; kh
+end
+struct Occlknndis                 # src/occlknndis.jl:1-9, then the handle and the cache of the rows' leave-one-out medians (NaN: not yet computed)
+    d; fm; T; tscales; k::Int; e_cdf; cutoff::Float64; kh; dk_train::Vector{Float64}
+end
+function _occ_knn_scores(X, nlv, scal, ctx)      # src/occknndis.jl:131-134
+    fm = pcasvd(X; nlv = nlv, scal = scal, ctx = ctx)
+    tscales = col_stats(fm.T; ctx = ctx).stds
+    (fm, tscales, _affine(fm.T, nothing, nothing, Matrix(Diagonal(1 ./ tscales)), nothing, ctx))
+end
+_occ_knn_query(object, X, ctx) = _affine(transform(object.fm, X; ctx = ctx), nothing, nothing, Matrix(Diagonal(1 ./ object.tscales)), nothing, ctx)
+_median_of_sorted_cols(D) = [_median_sorted(D[:, i]) for i in 1:size(D, 2)]
+function _occ_knn_table(d, typc, cri, alpha)
+    e_cdf = sort(d)
+    cutoff = _occ_cutoff(e_cdf, typc, cri, alpha)
+    (_table((d = d, dstand = d ./ cutoff, pval = _occ_pval(e_cdf, d))), e_cdf, cutoff)
+end
+
+"""`occknndis(X; nlv, nsamp, k, typc = "mad", cri = 3, alpha = .025, scal = false)` — src/occknndis.jl:125-149.  `samp` (rows) may be given: the
+reference's `sample` draws from a stream it does not pin."""
+function occknndis(X; nlv, nsamp = nothing, k, typc = "mad", cri = 3, alpha = .025, scal = false, samp = nothing, ctx = default_ctx())
+    X = _in(X); k = Int64(k)
+    fm, tscales, T = _occ_knn_scores(X, nlv, scal, ctx); n = size(T, 1)
+    samp = samp === nothing ? Random.shuffle(1:n)[1:nsamp] : collect(samp)
+    kh = knn_prepare(T; ctx = ctx)
+    res = knn_search(kh, Array(T)[samp, :], k + 1)
+    d = _median_of_sorted_cols(res.d[2:end, :])                          # :141
+    tab, e_cdf, cutoff = _occ_knn_table(d, typc, cri, alpha)
+    Occknndis(tab, fm, T, tscales, k, e_cdf, cutoff, kh)
+end
+"`predict(object::Occknndis, X)` — src/occknndis.jl:157-171."
+function predict(object::Occknndis, X; ctx = default_ctx())
+    d = knn_search(object.kh, _occ_knn_query(object, X, ctx), object.k).dmed
+    cols = (d = d, dstand = d ./ object.cutoff, pval = _occ_pval(object.e_cdf, d))
+    (pred = _occ_pred(cols.dstand), d = _table(cols))
+end
+
+# d = dmed / zd for the queries Zq: one search, the cache fill for the neighbour rows not in it yet (one search with `self` = the rows themselves,
+# only dmed read), then zd = the median of dk_train over each neighbourhood (jch_knn_gather_median)
+function _occl_ratio(kh, Th, dk_train, k, Zq, self, literal, ctx)
+    res = knn_search(kh, Zq, k; self = self)
+    ind = res.ind
+    if literal                                                           # rows of the row-removed matrix, used unshifted (src/occlknndis.jl:152-153)
+        ind = ind .- (ind .> permutedims(collect(self)))
+    end
+    need = [j for j in unique(vec(ind)) if isnan(dk_train[j])]
+    if !isempty(need)
+        dk_train[need] = knn_search(kh, Th[need, :], k; self = need).dmed
+    end
+    res.dmed ./ knn_gather_median(dk_train, ind; ctx = ctx)
+end
+
+"""`occlknndis(X; nlv, nsamp, k, typc = "mad", cri = 3, alpha = .025, scal = false, reading = "literal")` — src/occlknndis.jl:132-165.  "literal"
+follows :146-157 with its two slips (the query is row i while row samp[i] is removed; the row-removed indices are used unshifted); "doc" does what the
+docstring says."""
+function occlknndis(X; nlv, nsamp = nothing, k, typc = "mad", cri = 3, alpha = .025, scal = false, samp = nothing, reading = "literal", ctx = default_ctx())
+    reading in ("literal", "doc") || throw(ArgumentError("reading = $reading must be \"literal\" or \"doc\""))
+    X = _in(X); k = Int64(k)
+    fm, tscales, T = _occ_knn_scores(X, nlv, scal, ctx); n = size(T, 1)
+    samp = samp === nothing ? Random.shuffle(1:n)[1:nsamp] : collect(samp)
+    kh = knn_prepare(T; ctx = ctx)
+    Th = Array(T); dk_train = fill(NaN, n); kk = min(k, n - 1)
+    q = reading == "literal" ? collect(1:length(samp)) : samp
+    d = _occl_ratio(kh, Th, dk_train, kk, Th[q, :], samp, reading == "literal", ctx)
+    tab, e_cdf, cutoff = _occ_knn_table(d, typc, cri, alpha)
+    Occlknndis(tab, fm, T, tscales, k, e_cdf, cutoff, kh, dk_train)
+end
+"`predict(object::Occlknndis, X)` — src/occlknndis.jl:173-199, from the cache."
+function predict(object::Occlknndis, X; ctx = default_ctx())
+    Th = Array(object.T); n = size(Th, 1)
+    res = knn_search(object.kh, _occ_knn_query(object, X, ctx), object.k)
+    need = [j for j in unique(vec(res.ind)) if isnan(object.dk_train[j])]
+    if !isempty(need)
+        object.dk_train[need] = knn_search(object.kh, Th[need, :], min(object.k, n - 1); self = need).dmed
+    end
+    d = res.dmed ./ knn_gather_median(object.dk_train, res.ind; ctx = ctx)
+    cols = (d = d, dstand = d ./ object.cutoff, pval = _occ_pval(object.e_cdf, d))
+    (pred = _occ_pred(cols.dstand), d = _table(cols))
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
