@@ -1216,9 +1216,13 @@ int32_t jch_fit_plskern_bf16(jch_ctx *ctx, const jch_pls_desc &d, const void *Xv
         const int k2panel = jch_knob("JCH_BF16_K2_PANEL", 1);
         const int NHv = jch_knob("JCH_BF16_K2_NH", 2) == 4 ? 4 : 2, THv = 32 * NHv;
         const int64_t nfull = (n / THv) * THv;
-        const bool panel = k2panel && v8 && qpad == 16 && ldy % 8 == 0 && ((uintptr_t)Yc) % 16 == 0 && ((uintptr_t)dn) % 16 == 0 && nfull > 0;
-        // unit weights, raw mode: the products on the bf16 matrix pipe (k_xty_bf16_panel_m32; JCH_BF16_K2_M32=0: the f64 products)
-        m32 = panel && raw_b && !wdev && jch_knob("JCH_BF16_K2_M32", 1) != 0 && NHv == 2;
+        const bool panel_ok = k2panel && v8 && qpad == 16 && ldy % 8 == 0 && ((uintptr_t)Yc) % 16 == 0 && ((uintptr_t)dn) % 16 == 0;
+        const bool panel = panel_ok && nfull > 0;
+        // unit weights, raw mode: the products on the bf16 matrix pipe (k_xty_bf16_panel_m32; JCH_BF16_K2_M32=0: the f64 products).
+        // This path sums RAW X'[Y | 1] into K where every other one sums (X - pivot)'D[Yc | 1], and K is all-reduced: the choice
+        // must not depend on the shard.  A shard without a full row tile (nfull == 0) of a sharded fit therefore takes the path's
+        // tail kernel alone instead of the tile kernel, as its neighbours with a full tile take the panel.
+        m32 = panel_ok && raw_b && !wdev && jch_knob("JCH_BF16_K2_M32", 1) != 0 && NHv == 2 && (nfull > 0 || ctx->nranks > 1);
         if (m32) {
             const int ncg = (ldr_b + 511) / 512;
             const int wmax = std::min(ldr_b, 512), ntile = (wmax + 63) / 64;
@@ -1235,7 +1239,8 @@ int32_t jch_fit_plskern_bf16(jch_ctx *ctx, const jch_pls_desc &d, const void *Xv
                 static jch_per_device_once once_; \
                 if (!once_.done(ctx->device)) { JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_xty_bf16_panel_m32<NT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once_.mark(ctx->device); } \
                 hipLaunchKernelGGL((k_xty_bf16_panel_m32<NT, 2>), dim3(G, ncg), dim3(256), lds, ctx->stream, Xc, ldx, Yc, ldy, nfull, p, q, Xr, ldr_b, Kpart, kpr); } while (0)
-            if (NTv == 1) JCH_K2M(1); else if (NTv == 2) JCH_K2M(2); else if (NTv == 4) JCH_K2M(4); else JCH_K2M(8);
+            if (nfull == 0) { /* G == 0: every row is the tail's */ }
+            else if (NTv == 1) JCH_K2M(1); else if (NTv == 2) JCH_K2M(2); else if (NTv == 4) JCH_K2M(4); else JCH_K2M(8);
 #undef JCH_K2M
             JCH_HIP(ctx, hipGetLastError());
             if (tail)
