@@ -651,6 +651,25 @@ JCH_API int32_t jch_knn_vote(jch_ctx *ctx, int32_t loc, const int32_t *cls, int6
                              int32_t k, int32_t *pred, double *score);
 JCH_API int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double *v, int64_t n, const int32_t *ind, int64_t m, int32_t k, double *out);
 
+/* ---- Gaussian kernel density estimates: what the reference's `dmkern`, `kdeda` and `plskdeda` evaluate (src/dmkern.jl:151-163,
+ * src/kdeda.jl:81-97, src/plskdeda.jl:52-64 with the prediction of src/plslda.jl:107-130) -- DESIGN.md §21.
+ * jch_kde_dens -- for the m queries Xq (m x d) against the n training rows Z (n x d) GROUPED BY CLASS (class c owns the rows
+ * cls_start[c] .. cls_start[c + 1] - 1; cls_start[0] = 0, cls_start[ncls] = n, no class empty) and nmod nested models:
+ *     out[i, c, a] = coef[a, c] * sum_{r in class c} exp(-0.5 * v2[a, c] * sum_{j < dims[a]} ((Xq[i, j] - Z[r, j]) * u[j, c])^2)
+ *   The inverse bandwidth of model a, class c, column j is u[j, c] * sqrt(v2[a, c]); dims[a] is the number of leading columns model a
+ *   reads, 1 <= dims[0] <= ... <= dims[nmod - 1] <= d (equal values allowed).  One pass over the (query, row) pairs serves every model:
+ *   the squared distance over the first dims[a] columns is a running prefix of the one over dims[a + 1]; nothing of size m x n is stored.
+ *   Differences are taken before scaling ((x - z) * u, never x * u - z * u) and the sum is a plain sum of `exp` terms, as in the reference:
+ *   a query far from every row of a class gives exactly 0.  Fixed summation order, no atomics: the same call gives the same bits.
+ *   Z, Xq, out [loc], column-major, ld >= rows; out is m x (ncls * nmod), element (i, c, a) at out[i + ldo * (c + ncls * a)].
+ *   cls_start (ncls + 1), u (d x ncls), v2 and coef (nmod x ncls, both column-major: element (a, c) at [a + nmod * c]) and dims (nmod) are
+ *   HOST arrays whatever loc is.  Any m, n, d, ncls, nmod >= 1 (ncls <= 65535).  JCH_EINVAL before any device work for a NULL pointer,
+ *   ld < rows, dims decreasing or outside [1, d], an empty class, or cls_start not running from 0 to n.  The workspace is the ctx's own
+ *   (the X copy a fit left for JCH_REUSE_XCOPY is not touched); the call ends synchronised with the ctx stream. */
+JCH_API int32_t jch_kde_dens(jch_ctx *ctx, int32_t loc, const double *Z, int64_t n, int64_t d, int64_t ldz, const double *Xq, int64_t m, int64_t ldq,
+                             const int64_t *cls_start, int32_t ncls, const double *u, const double *v2, const double *coef, const int32_t *dims,
+                             int32_t nmod, double *out, int64_t ldo);
+
 typedef struct jch_profile {
     double fit_ms;        /* device time of the last fit, first kernel -> last kernel (HIP events)   */
     double prologue_ms;   /* weights + means (+ var) + centre/transpose/XtY                           */

@@ -98,6 +98,7 @@ struct jch_ctx {
     jch_buf st_t, st_ms;   // stah.hip: one panel of projections; [mu | s | d of a host call]
     jch_buf sp_ws;   // samp.hip: row flags, per-workgroup triples and the result of a farthest-pair search; running minima, partials and targets of a max-min selection
     jch_buf kn_ws;   // knn.hip: the search's lists ahead of the drop of `self`, the results of a host call, the sort buffers and class accumulators of shapes beyond the LDS
+    jch_buf kd_ws;   // kde.hip: the bandwidth factors, class offsets and model dimensions of a call, the per-split partial sums, the staging of a host call
     const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
     int64_t chol_n = 0, chol_ld = 0;
     // profiling

@@ -13,3 +13,4 @@ from .stah import Occstah, Stah, col_median_mad, colmad, occstah, stah  # noqa: 
 from .samp import Samp, Sampcla, Sampdp, farthest_pair, maxmin_select, sampcla, sampdp, sampks, sampsys  # noqa: F401
 from .knn import (KnnPred, Knnda, Knnr, Occknndis, Occlknndis, getknn, knn_gather_median, knn_prepare, knn_release, knn_search, knn_vote, knn_wmean,  # noqa: F401
                   knnda, knnda_predict, knnr, knnr_predict, occknn_predict, occknndis, occlknndis)
+from .kde import Dmkern, Kernda, dmkern, dmkern_predict, kde_dens, kdeda, kdeda_predict, plskdeda, plskdeda_predict  # noqa: F401

@@ -40,7 +40,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss,
        Occstah, occstah, stah, colmad, col_median_mad,
        sampks, sampdp, sampsys, sampcla, farthest_pair, maxmin_select,
-       Knnr, Knnda, Occknndis, Occlknndis, getknn, knnr, knnda, occknndis, occlknndis, knn_search, knn_wmean, knn_vote, knn_gather_median
+       Knnr, Knnda, Occknndis, Occlknndis, getknn, knnr, knnda, occknndis, occlknndis, knn_search, knn_wmean, knn_vote, knn_gather_median,
+       Dmkern, Kernda, dmkern, kdeda, plskdeda, kde_dens
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -2174,6 +2175,150 @@ function predict(object::Occlknndis, X; ctx = default_ctx())
     d = res.dmed ./ knn_gather_median(object.dk_train, res.ind; ctx = ctx)
     cols = (d = d, dstand = d ./ object.cutoff, pval = _occ_pval(object.e_cdf, d))
     (pred = _occ_pred(cols.dstand), d = _table(cols))
+end
+
+# ---- kernel density estimation and the discrimination on it (src/dmkern.jl, src/kdeda.jl, src/plskdeda.jl) over jch_kde_dens; DESIGN.md §21.
+# The inverse bandwidth of model a (the first dims[a] columns), class c, column j separates into u[j, c] * v[a, c]: one device pass over the
+# (query, training row) pairs serves a dmkern, the classes of a kdeda, or the nlv x nlev densities of a plskdeda prediction.
+struct Dmkern                     # src/dmkern.jl:1-6
+    X; H; Hinv; detH
+end
+struct Kernda                     # src/kdeda.jl:1-6, then the rows grouped by class and the class offsets (0-based, nlev + 1)
+    fm; wprior; lev; ni; Z; cs
+end
+struct Plslda                     # src/plslda.jl:1-5 (fm = (fm_pls, fm_da)), then what a plskdeda prediction needs: (Z, cs, u, v2)
+    fm; lev; ni; kde
+end
+
+"""`kde_dens(Z, Xq, cls_start, u, v2, coef, dims)` — jch_kde_dens: out[i, c, a] = coef[a, c] * sum over the rows r of class c of
+exp(-0.5 * v2[a, c] * sum_{j <= dims[a]} ((Xq[i, j] - Z[r, j]) * u[j, c])^2), an m x ncls x nmod array where Xq lives.  Z: the training rows
+grouped by class, class c in rows cls_start[c] + 1 : cls_start[c + 1] (0-based offsets, ncls + 1 of them); u (d x ncls), v2 and coef
+(nmod x ncls) and dims (nmod, non-decreasing within 1:d) are host arrays."""
+function kde_dens(Z, Xq, cls_start, u, v2, coef, dims; ctx = default_ctx())
+    Z = _in(Z); Xq = _in(Xq); n, d = size(Z); m = size(Xq, 1)
+    size(Xq, 2) == d || throw(DimensionMismatch("Z has $d columns, Xq has $(size(Xq, 2))"))
+    cs = Vector{Int64}(vec(cls_start)); dm = Vector{Int32}(vec(dims)); ncls = length(cs) - 1; nmod = length(dm)
+    um = Matrix{Float64}(reshape(u, d, ncls)); vm = Matrix{Float64}(reshape(v2, nmod, ncls)); cm = Matrix{Float64}(reshape(coef, nmod, ncls))
+    out = _similar(Xq, m, ncls, nmod)
+    GC.@preserve Z Xq cs um vm cm dm out begin
+        check(ctx, ccall((:jch_kde_dens, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Int64}, Int32, Ptr{Float64}, Ptr{Float64},
+                          Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Float64}, Int64),
+                         ctx.h, _loc(Xq), pointer(Z), n, d, stride(Z, 2), pointer(Xq), m, stride(Xq, 2), pointer(cs), Int32(ncls), pointer(um),
+                         pointer(vm), pointer(cm), pointer(dm), Int32(nmod), pointer(out), max(m, 1)))
+    end
+    out
+end
+
+_kde_bandwidths(std, n, p, h, a) = h === nothing ? a * n^(-1 / (p + 4)) .* std[1:p] : (h isa Real ? fill(Float64(h), p) : Vector{Float64}(vec(h)))
+function _dm_record(X, hv)                       # src/dmkern.jl:135-142
+    any(==(0), hv) && throw(LinearAlgebra.SingularException(1))
+    detH = prod(hv)
+    Dmkern(X, Matrix(Diagonal(hv)), Matrix(Diagonal(1 ./ hv)), detH == 0 ? 1e-20 : detH)
+end
+_kde_coef(n, p, detH) = 1 / n * (2 * pi)^(-p / 2) * (1 / detH)
+function _kde_check_default(X, n)
+    (n == 1 || any(maximum(Array(X); dims = 1) .== minimum(Array(X); dims = 1))) && throw(LinearAlgebra.SingularException(1))
+end
+
+"`dmkern(X; h = nothing, a = 1)` — src/dmkern.jl:124-143; the default bandwidth's colstd comes from the device."
+function dmkern(X; h = nothing, a = 1, ctx = default_ctx())
+    X = _in(X); n, p = size(X)
+    (h === nothing || h isa Real || length(h) == p) || throw(DimensionMismatch("h has $(length(h)) entries, X has $p columns"))
+    std = nothing
+    if h === nothing
+        _kde_check_default(X, n)
+        std = col_stats(X; ctx = ctx).stds
+    end
+    _dm_record(X, _kde_bandwidths(std, n, p, h, a))
+end
+"`predict(object::Dmkern, X)` — src/dmkern.jl:151-163."
+function predict(object::Dmkern, X; ctx = default_ctx())
+    n, p = size(object.X)
+    out = kde_dens(object.X, X, [0, n], reshape(diag(object.Hinv), p, 1), ones(1, 1), fill(_kde_coef(n, p, object.detH), 1, 1), [p]; ctx = ctx)
+    (pred = reshape(out, :, 1),)
+end
+
+function _kde_prior(prior, ni)
+    prior == "unif" && return ones(length(ni)) ./ length(ni)
+    prior == "prop" && return ni ./ sum(ni)
+    throw(ArgumentError("prior must be \"unif\" or \"prop\""))
+end
+# the rows grouped by level (stable), the 0-based class offsets, the per-class colstd (nlev x p) when the bandwidth is the default
+function _kde_prepare(X, y, h, prior, ctx)
+    yv = vec(Array(y)); n = size(X, 1)
+    length(yv) == n || throw(DimensionMismatch("X has $n rows, y has $(length(yv))"))
+    lev = sort(unique(yv)); ni = [count(==(l), yv) for l in lev]
+    wprior = _kde_prior(prior, ni)
+    (h === nothing && any(==(1), ni)) && throw(LinearAlgebra.SingularException(1))
+    order = sortperm([searchsortedfirst(lev, v) for v in yv]; alg = MergeSort)
+    (yv, lev, ni, wprior, order, vcat(0, cumsum(ni)))
+end
+function _kde_class_stds(Zg, cs, ctx)
+    stds = zeros(length(cs) - 1, size(Zg, 2))
+    for c in 1:length(cs) - 1
+        blk = Zg[cs[c] + 1:cs[c + 1], :]
+        _kde_check_default(blk, size(blk, 1))
+        stds[c, :] = col_stats(blk; ctx = ctx).stds
+    end
+    stds
+end
+_kernda_model(Zg, cs, stds, p, h, a, wprior, lev, ni) =
+    Kernda([_dm_record(Zg[cs[c] + 1:cs[c + 1], 1:p], _kde_bandwidths(stds === nothing ? nothing : stds[c, :], ni[c], p, h, a)) for c in 1:length(lev)],
+           wprior, lev, ni, Zg[:, 1:p], cs)
+
+"`kdeda(X, y; prior = \"unif\", h = nothing, a = 1)` — src/kdeda.jl:62-79: one dmkern per class on that class's rows."
+function kdeda(X, y; prior = "unif", h = nothing, a = 1, ctx = default_ctx())
+    X = _in(X); p = size(X, 2)
+    (h === nothing || h isa Real || length(h) == p) || throw(DimensionMismatch("h has $(length(h)) entries, X has $p columns"))
+    yv, lev, ni, wprior, order, cs = _kde_prepare(X, y, h, prior, ctx)
+    Zg = X[order, :]
+    stds = h === nothing ? _kde_class_stds(Zg, cs, ctx) : nothing
+    _kernda_model(Zg, cs, stds, p, h, a, wprior, lev, ni)
+end
+function _kde_posterior(wprior, dens, lev)       # src/kdeda.jl:91-95 (argmax: the first level on ties and on a NaN row)
+    A = Array(dens) .* permutedims(wprior)
+    posterior = A ./ sum(A; dims = 2)
+    z = [argmax(posterior[i, :]) for i in 1:size(posterior, 1)]
+    (reshape(lev[z], :, 1), posterior)
+end
+"`predict(object::Kernda, X)` — src/kdeda.jl:81-97: (pred, dens, posterior), one jch_kde_dens call for all classes."
+function predict(object::Kernda, X; ctx = default_ctx())
+    p = size(object.Z, 2); nlev = length(object.lev)
+    u = hcat([diag(f.Hinv) for f in object.fm]...)
+    coef = reshape([_kde_coef(object.ni[c], p, object.fm[c].detH) for c in 1:nlev], 1, nlev)
+    dens = reshape(kde_dens(object.Z, X, object.cs, u, ones(1, nlev), coef, [p]; ctx = ctx), :, nlev)
+    pred, posterior = _kde_posterior(object.wprior, dens, object.lev)
+    (pred = pred, dens = dens, posterior = posterior)
+end
+
+"""`plskdeda(X, y, weights = ones(n); nlv, prior = "unif", h = nothing, a = 1, scal = false)` — src/plskdeda.jl:52-64: plskern on `dummy(y)`,
+then kdeda(T[:, 1:i], y) for i = 1:nlv.  `h`: nothing or a real (a vector fits the model of one nlv only)."""
+function plskdeda(X, y, weights = nothing; nlv, prior = "unif", h = nothing, a = 1, scal = false, ctx = default_ctx())
+    (h === nothing || h isa Real) || throw(DimensionMismatch("plskdeda: a vector h fits the model of one nlv only"))
+    X = _in(X)
+    yv, lev, ni, wprior, order, cs = _kde_prepare(X, y, h, prior, ctx)
+    fm_pls = plskern(X, _colocate_mat(dummy(yv).Y, X), weights; nlv = nlv, scal = scal, ctx = ctx)
+    k = size(fm_pls.T, 2); nlev = length(lev)
+    Zg = fm_pls.T[order, :]
+    stds = h === nothing ? _kde_class_stds(Zg, cs, ctx) : nothing
+    fm_da = [_kernda_model(Zg, cs, stds, i, h, a, wprior, lev, ni) for i in 1:k]
+    u = h === nothing ? permutedims(1 ./ stds) : fill(1 / h, k, nlev)
+    v = h === nothing ? [ni[c]^(1 / (i + 4)) / a for i in 1:k, c in 1:nlev] : ones(k, nlev)
+    Plslda((fm_pls = fm_pls, fm_da = fm_da), lev, ni, (Z = Zg, cs = cs, u = u, v2 = v .* v))
+end
+"""`predict(object::Plslda, X; nlv = nothing)` — src/plslda.jl:107-130 for a plskdeda model: one transform at the largest nlv, then one
+jch_kde_dens call with dims = the clamped nlv range."""
+function predict(object::Plslda, X; nlv = nothing, ctx = default_ctx())
+    a = size(object.fm.fm_pls.T, 2)
+    rng = nlv === nothing ? (a:a) : (max(minimum(nlv), 1):min(maximum(nlv), a))      # (:114 clamps to 0:a; there is no model 0)
+    isempty(rng) && throw(BoundsError(object.fm.fm_da, 0))
+    kmax = last(rng); nlev = length(object.lev); st = object.kde
+    T = transform(object.fm.fm_pls, X; nlv = kmax, ctx = ctx)
+    coef = [_kde_coef(object.ni[c], k, object.fm.fm_da[k].fm[c].detH) for k in rng, c in 1:nlev]
+    dens = kde_dens(st.Z[:, 1:kmax], T, st.cs, st.u[1:kmax, :], st.v2[collect(rng), :], coef, collect(rng); ctx = ctx)
+    res = [_kde_posterior(object.fm.fm_da[k].wprior, dens[:, :, i], object.lev) for (i, k) in enumerate(rng)]
+    length(rng) == 1 ? (pred = res[1][1], posterior = res[1][2]) : (pred = [r[1] for r in res], posterior = [r[2] for r in res])
 end
 
 # ---- P2P inbox transport (include/jchemo_hip.h): export -> all-gather the handles (MPI) -> import -> agree -> enable
