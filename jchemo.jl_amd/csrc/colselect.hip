@@ -217,17 +217,13 @@ extern "C" int32_t jch_col_median_mad(jch_ctx *ctx, int32_t loc, const double *X
     if ((loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) || (out_loc != JCH_LOC_HOST && out_loc != JCH_LOC_DEVICE))
         return jch_fail(ctx, JCH_EINVAL, "jch_col_median_mad: bad loc");
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    // every reservation first: nothing but a launch may fail between the first queued copy and the synchronisation
     JCH_TRY(jch_colselect_reserve(ctx, p));
     if (loc == JCH_LOC_HOST) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)n * (size_t)p));
     if (out_loc == JCH_LOC_HOST) JCH_TRY(jch_reserve(ctx, ctx->sel_out, sizeof(double) * 2 * (size_t)p));
-    auto run = [&]() -> int32_t {
+    return jch_synced(ctx, loc == JCH_LOC_HOST || out_loc == JCH_LOC_HOST, [&]() -> int32_t {
         const double *dX = X;
         int64_t ldxd = ldx;
-        if (loc == JCH_LOC_HOST) {
-            JCH_TRY(jch_copy2d(ctx, (double *)ctx->xq.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
-            dX = (const double *)ctx->xq.ptr; ldxd = n;
-        }
+        JCH_TRY(jch_stage_in(ctx, loc == JCH_LOC_HOST, (double *)ctx->xq.ptr, n, p, &dX, &ldxd));
         double *dmed = med, *dmad = mad;
         if (out_loc == JCH_LOC_HOST) { dmed = (double *)ctx->sel_out.ptr; dmad = mad ? dmed + p : nullptr; }
         JCH_TRY(jch_launch_col_median_mad(ctx, dX, n, p, ldxd, dmed, dmad));
@@ -236,11 +232,5 @@ extern "C" int32_t jch_col_median_mad(jch_ctx *ctx, int32_t loc, const double *X
             if (mad) JCH_HIP(ctx, hipMemcpyAsync(mad, dmad, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
         }
         return JCH_OK;
-    };
-    const int32_t st = run();
-    if (loc == JCH_LOC_DEVICE && out_loc == JCH_LOC_DEVICE) return st;   // device to device: enqueued, no host synchronisation
-    const hipError_t es = hipStreamSynchronize(ctx->stream);             // on the failure paths too: host memory has copies queued
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
-    return JCH_OK;
+    });
 }

@@ -529,14 +529,6 @@ extern "C" int32_t jch_covsel_fit(jch_ctx *ctx, int32_t loc, double *X, int64_t 
     const int ldpart = std::max(a, qi + 1);
     if (nblk > INT32_MAX) return jch_fail(ctx, JCH_EINVAL, "%s: n=%lld too large", who, (long long)n);
     if (inplace) ctx->xcopy_valid = false;   // X is about to be rewritten: a working copy a fit left of it is stale (JCH_REUSE_XCOPY)
-    // ---- device views of X and Y
-    double *dX = X;
-    int64_t ldxd = ldx;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)ldw * (size_t)p));
-        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, ldw, X, ldx, n, p, hipMemcpyHostToDevice));
-        dX = (double *)ctx->dk_x.ptr; ldxd = ldw;
-    }
     jch_carve cv;
     const size_t oW = cv.take((size_t)ldw * (size_t)(qi + a)), oY = cv.take(host ? (size_t)n * qi : 0), omu = cv.take(pi), ocss0 = cv.take(pi), ocss = cv.take(pi),
                  oKG = cv.take((size_t)(qi + 2) * ldp), oG = cv.take((size_t)pi * a), oC = cv.take((size_t)pi * a), ocov2 = cv.take(pi), oselcov = cv.take(a),
@@ -549,57 +541,63 @@ extern "C" int32_t jch_covsel_fit(jch_ctx *ctx, int32_t loc, double *X, int64_t 
            *Cd = ws + oC, *cov2d = ws + ocov2, *selcovd = ws + oselcov, *xss = ws + oxss, *yss = ws + oyss, *ycs = ws + oycs, *tq = ws + otq, *hd = ws + oh,
            *vals = ws + ovals, *QtYd = ws + oQtY, *ymd = ws + oym, *ysd = ws + oys, *sc = ws + osc, *part = ws + opart;
     int *flag = (int *)(ws + oflag), *seld = (int *)(ws + osel);
-    const double *dY = Y;
-    int64_t ldyd = ldy;
-    if (host) {
-        JCH_TRY(jch_copy2d(ctx, Ystage, n, Y, ldy, n, q, hipMemcpyHostToDevice));
-        dY = Ystage; ldyd = n;
-    }
-    // ---- everything from oG up to the partials starts as zero (G, C, cov2, the tables, the scalars and the flags)
-    JCH_HIP(ctx, hipMemsetAsync(ws + oG, 0, sizeof(double) * (opart - oG), ctx->stream));
-    if (ldw > n) {
-        hipLaunchKernelGGL(k_cs_zero_pad, dim3(jch_grid1(ctx, (ldw - n) * (qi + a))), dim3(CS_NT), 0, ctx->stream, W, n, ldw, qi + a);
-        JCH_HIP(ctx, hipGetLastError());
-    }
-    // ---- xmeans (a pass against a column of ones), ymeans / yscales / Yd, then K = Xc'Yd with the centred column sums of squares (:64-72)
-    JCH_TRY(cs_pass(ctx, dX, n, pi, ldxd, nullptr, nullptr, 0, nullptr, 1, ldw, false, KG, ldp, nullptr));
-    hipLaunchKernelGGL(k_cs_means, dim3((pi + CS_NT - 1) / CS_NT), dim3(CS_NT), 0, ctx->stream, KG, pi, (double)n, mu);
-    hipLaunchKernelGGL(k_cs_ystats, dim3(qi), dim3(1024), 0, ctx->stream, dY, n, qi, ldyd, W, ldw, ymd, ysd, ycs);
-    JCH_HIP(ctx, hipGetLastError());
-    JCH_TRY(cs_pass(ctx, dX, n, pi, ldxd, mu, W, qi, nullptr, qi, ldw, true, KG, ldp, flag));
-    const dim3 gn((unsigned)nblk);
-    for (int i = 0; i < a; ++i) {
-        hipLaunchKernelGGL(k_cs_select, dim3(1), dim3(CS_NT), 0, ctx->stream, i, pi, qi, (double)n, (int)typ, 1, KG, ldp, css0, css, Gd, Cd, xss, yss, ycs, part,
-                           nblk, ldpart, flag, sc);
-        hipLaunchKernelGGL(k_cs_xd, gn, dim3(CS_NT), 0, ctx->stream, dX, n, ldxd, mu, Gd, pi, Qd, ldw, i, flag, part, ldpart);
-        if (i > 0) hipLaunchKernelGGL(k_cs_sum_part, dim3(1), dim3(1024), 0, ctx->stream, part, nblk, ldpart, i, hd, flag);
-        hipLaunchKernelGGL(k_cs_reorth, gn, dim3(CS_NT), 0, ctx->stream, W, n, ldw, i, qi, hd, flag, part, ldpart);
-        hipLaunchKernelGGL(k_cs_commit, dim3(1), dim3(1024), 0, ctx->stream, part, nblk, ldpart, qi, i, a, css0, flag, sc, vals, tq, QtYd, seld, selcovd, cov2d);
-        hipLaunchKernelGGL(k_cs_update, gn, dim3(CS_NT), 0, ctx->stream, W, n, ldw, i, qi, sc, tq, flag, part, ldpart);
-        hipLaunchKernelGGL(k_cs_qty2, dim3(1), dim3(1024), 0, ctx->stream, part, nblk, ldpart, qi, i, a, flag, tq, QtYd);
-        hipLaunchKernelGGL(k_cs_update2, gn, dim3(CS_NT), 0, ctx->stream, W, n, ldw, i, qi, tq, flag, part, ldpart);
-        JCH_HIP(ctx, hipGetLastError());
-        // the next K = Xc'Yd and G[:, i] = Xc'q_i in one read of X; after the last step only G[:, a - 1] is left to fetch
-        if (i + 1 < a) JCH_TRY(cs_pass(ctx, dX, n, pi, ldxd, mu, W, qi, Qd + (size_t)i * (size_t)ldw, qi + 1, ldw, false, KG, ldp, flag));
-        else JCH_TRY(cs_pass(ctx, dX, n, pi, ldxd, mu, nullptr, 0, Qd + (size_t)i * (size_t)ldw, 1, ldw, false, KG + (size_t)qi * ldp, ldp, flag));
-    }
-    hipLaunchKernelGGL(k_cs_select, dim3(1), dim3(CS_NT), 0, ctx->stream, a, pi, qi, (double)n, (int)typ, 0, KG, ldp, css0, css, Gd, Cd, xss, yss, ycs, part, nblk,
-                       ldpart, flag, sc);
-    JCH_HIP(ctx, hipGetLastError());
-    if (inplace) {   // X <- Xc - Q G', Y <- Yd (:112-113)
-        const dim3 gd((unsigned)((n + CS_NT - 1) / CS_NT), (unsigned)std::min(1024, (pi + 3) / 4));
-        hipLaunchKernelGGL(k_cs_deflate_x, gd, dim3(CS_NT), 0, ctx->stream, dX, n, pi, ldxd, mu, Qd, ldw, Gd, flag);
-        JCH_HIP(ctx, hipGetLastError());
-        if (host) JCH_TRY(jch_copy2d(ctx, X, ldx, dX, ldxd, n, p, hipMemcpyDeviceToHost));
-        JCH_TRY(jch_copy2d(ctx, Y, ldy, W, ldw, n, q, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
-    }
-    if (Q) JCH_TRY(jch_copy2d(ctx, Q, n, Qd, ldw, n, a, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
-    // ---- the small results: one copy of the zero-initialised region, then the host picks them apart
     std::vector<double> small(opart - oG);
-    std::vector<double> xm(xmeans ? pi : 0);
-    JCH_HIP(ctx, hipMemcpyAsync(small.data(), ws + oG, sizeof(double) * small.size(), hipMemcpyDeviceToHost, ctx->stream));
-    if (xmeans) JCH_HIP(ctx, hipMemcpyAsync(xmeans, mu, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        // ---- device views of X and Y
+        double *dX = X;
+        int64_t ldxd = ldx;
+        if (host) {
+            JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)ldw * (size_t)p));
+            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, ldw, X, ldx, n, p, hipMemcpyHostToDevice));
+            dX = (double *)ctx->dk_x.ptr; ldxd = ldw;
+        }
+        const double *dY = Y;
+        int64_t ldyd = ldy;
+        JCH_TRY(jch_stage_in(ctx, host, Ystage, n, q, &dY, &ldyd));
+        // ---- everything from oG up to the partials starts as zero (G, C, cov2, the tables, the scalars and the flags)
+        JCH_HIP(ctx, hipMemsetAsync(ws + oG, 0, sizeof(double) * (opart - oG), ctx->stream));
+        if (ldw > n) {
+            hipLaunchKernelGGL(k_cs_zero_pad, dim3(jch_grid1(ctx, (ldw - n) * (qi + a))), dim3(CS_NT), 0, ctx->stream, W, n, ldw, qi + a);
+            JCH_HIP(ctx, hipGetLastError());
+        }
+        // ---- xmeans (a pass against a column of ones), ymeans / yscales / Yd, then K = Xc'Yd with the centred column sums of squares (:64-72)
+        JCH_TRY(cs_pass(ctx, dX, n, pi, ldxd, nullptr, nullptr, 0, nullptr, 1, ldw, false, KG, ldp, nullptr));
+        hipLaunchKernelGGL(k_cs_means, dim3((pi + CS_NT - 1) / CS_NT), dim3(CS_NT), 0, ctx->stream, KG, pi, (double)n, mu);
+        hipLaunchKernelGGL(k_cs_ystats, dim3(qi), dim3(1024), 0, ctx->stream, dY, n, qi, ldyd, W, ldw, ymd, ysd, ycs);
+        JCH_HIP(ctx, hipGetLastError());
+        JCH_TRY(cs_pass(ctx, dX, n, pi, ldxd, mu, W, qi, nullptr, qi, ldw, true, KG, ldp, flag));
+        const dim3 gn((unsigned)nblk);
+        for (int i = 0; i < a; ++i) {
+            hipLaunchKernelGGL(k_cs_select, dim3(1), dim3(CS_NT), 0, ctx->stream, i, pi, qi, (double)n, (int)typ, 1, KG, ldp, css0, css, Gd, Cd, xss, yss, ycs, part,
+                               nblk, ldpart, flag, sc);
+            hipLaunchKernelGGL(k_cs_xd, gn, dim3(CS_NT), 0, ctx->stream, dX, n, ldxd, mu, Gd, pi, Qd, ldw, i, flag, part, ldpart);
+            if (i > 0) hipLaunchKernelGGL(k_cs_sum_part, dim3(1), dim3(1024), 0, ctx->stream, part, nblk, ldpart, i, hd, flag);
+            hipLaunchKernelGGL(k_cs_reorth, gn, dim3(CS_NT), 0, ctx->stream, W, n, ldw, i, qi, hd, flag, part, ldpart);
+            hipLaunchKernelGGL(k_cs_commit, dim3(1), dim3(1024), 0, ctx->stream, part, nblk, ldpart, qi, i, a, css0, flag, sc, vals, tq, QtYd, seld, selcovd, cov2d);
+            hipLaunchKernelGGL(k_cs_update, gn, dim3(CS_NT), 0, ctx->stream, W, n, ldw, i, qi, sc, tq, flag, part, ldpart);
+            hipLaunchKernelGGL(k_cs_qty2, dim3(1), dim3(1024), 0, ctx->stream, part, nblk, ldpart, qi, i, a, flag, tq, QtYd);
+            hipLaunchKernelGGL(k_cs_update2, gn, dim3(CS_NT), 0, ctx->stream, W, n, ldw, i, qi, tq, flag, part, ldpart);
+            JCH_HIP(ctx, hipGetLastError());
+            // the next K = Xc'Yd and G[:, i] = Xc'q_i in one read of X; after the last step only G[:, a - 1] is left to fetch
+            if (i + 1 < a) JCH_TRY(cs_pass(ctx, dX, n, pi, ldxd, mu, W, qi, Qd + (size_t)i * (size_t)ldw, qi + 1, ldw, false, KG, ldp, flag));
+            else JCH_TRY(cs_pass(ctx, dX, n, pi, ldxd, mu, nullptr, 0, Qd + (size_t)i * (size_t)ldw, 1, ldw, false, KG + (size_t)qi * ldp, ldp, flag));
+        }
+        hipLaunchKernelGGL(k_cs_select, dim3(1), dim3(CS_NT), 0, ctx->stream, a, pi, qi, (double)n, (int)typ, 0, KG, ldp, css0, css, Gd, Cd, xss, yss, ycs, part, nblk,
+                           ldpart, flag, sc);
+        JCH_HIP(ctx, hipGetLastError());
+        if (inplace) {   // X <- Xc - Q G', Y <- Yd (:112-113)
+            const dim3 gd((unsigned)((n + CS_NT - 1) / CS_NT), (unsigned)std::min(1024, (pi + 3) / 4));
+            hipLaunchKernelGGL(k_cs_deflate_x, gd, dim3(CS_NT), 0, ctx->stream, dX, n, pi, ldxd, mu, Qd, ldw, Gd, flag);
+            JCH_HIP(ctx, hipGetLastError());
+            if (host) JCH_TRY(jch_copy2d(ctx, X, ldx, dX, ldxd, n, p, hipMemcpyDeviceToHost));
+            JCH_TRY(jch_copy2d(ctx, Y, ldy, W, ldw, n, q, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        }
+        if (Q) JCH_TRY(jch_copy2d(ctx, Q, n, Qd, ldw, n, a, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        // ---- the small results: one copy of the zero-initialised region, then the host picks them apart
+        JCH_HIP(ctx, hipMemcpyAsync(small.data(), ws + oG, sizeof(double) * small.size(), hipMemcpyDeviceToHost, ctx->stream));
+        if (xmeans) JCH_HIP(ctx, hipMemcpyAsync(xmeans, mu, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
+        return JCH_OK;
+    }));
     auto at = [&](size_t off) { return small.data() + (off - oG); };
     const int *hflag = (const int *)at(oflag);
     const int done = hflag[CS_DONE];

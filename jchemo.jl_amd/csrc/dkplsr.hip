@@ -46,28 +46,24 @@ extern "C" int32_t jch_kernel_gram(jch_ctx *ctx, int32_t loc, int32_t kind, cons
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const bool same_scales = zscale == xscale || (zscale && xscale && memcmp(zscale, xscale, sizeof(double) * (size_t)p) == 0);
     const bool sym = Z == X && ldz == ldx && m == n && same_scales;
-    const double *dZ = Z, *dX = X;
-    int64_t ldzd = ldz, ldxd = ldx;
-    double *dK = K;
-    int64_t ldkd = ldk;
-    if (loc == JCH_LOC_HOST) {
+    const bool host = loc == JCH_LOC_HOST;
+    if (host) {
         JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
-        dX = (const double *)ctx->dk_x.ptr; ldxd = n;
-        if (sym) {
-            dZ = dX; ldzd = ldxd;
-        } else {
-            JCH_TRY(jch_reserve(ctx, ctx->dk_q, sizeof(double) * (size_t)m * p));
-            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_q.ptr, m, Z, ldz, m, p, hipMemcpyHostToDevice));
-            dZ = (const double *)ctx->dk_q.ptr; ldzd = m;
-        }
+        if (!sym) JCH_TRY(jch_reserve(ctx, ctx->dk_q, sizeof(double) * (size_t)m * p));
         JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * (size_t)m * n));
-        dK = (double *)ctx->dk_k.ptr; ldkd = m;
     }
-    JCH_TRY(jch_launch_kgram(ctx, kind, dZ, m, ldzd, zscale, dX, n, ldxd, xscale, p, gamma, coef0, degree, sym, dK, ldkd));
-    if (loc == JCH_LOC_HOST) JCH_TRY(jch_copy2d(ctx, K, ldk, dK, ldkd, m, n, hipMemcpyDeviceToHost));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JCH_OK;
+    return jch_synced(ctx, true, [&]() -> int32_t {
+        const double *dZ = Z, *dX = X;
+        int64_t ldzd = ldz, ldxd = ldx;
+        JCH_TRY(jch_stage_in(ctx, host, (double *)ctx->dk_x.ptr, n, p, &dX, &ldxd));
+        if (host && sym) { dZ = dX; ldzd = ldxd; }
+        else JCH_TRY(jch_stage_in(ctx, host, (double *)ctx->dk_q.ptr, m, p, &dZ, &ldzd));
+        double *dK = host ? (double *)ctx->dk_k.ptr : K;
+        const int64_t ldkd = host ? m : ldk;
+        JCH_TRY(jch_launch_kgram(ctx, kind, dZ, m, ldzd, zscale, dX, n, ldxd, xscale, p, gamma, coef0, degree, sym, dK, ldkd));
+        if (host) JCH_TRY(jch_copy2d(ctx, K, ldk, dK, ldkd, m, n, hipMemcpyDeviceToHost));
+        return JCH_OK;
+    });
 }
 
 extern "C" int32_t jch_dkplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t kind, double gamma, double coef0, int32_t degree,
@@ -90,64 +86,66 @@ extern "C" int32_t jch_dkplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_
     const int64_t n = d.n, p = d.p, q = d.q;
     const bool host = d.loc == JCH_LOC_HOST, inplace = d.inplace != 0, scal = d.scal != 0;
     const int64_t kcap = std::min<int64_t>(n, d.nlv);
-    // ---- device views: X (read; scaled in place only for dkplsr!), Y (the inner plskern! centres it: a working copy unless dkplsr!)
-    double *dX = (double *)X, *dY = (double *)Y;
-    const double *dw = weights;
-    int64_t ldxd = ldx, ldyd = ldy;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, (const double *)X, ldx, n, p, hipMemcpyHostToDevice));
-        dX = (double *)ctx->dk_x.ptr; ldxd = n;
-    }
-    if (host || !inplace) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_y, sizeof(double) * (size_t)n * q));
-        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_y.ptr, n, (const double *)Y, ldy, n, q, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
-        dY = (double *)ctx->dk_y.ptr; ldyd = n;
-    }
-    // ---- outer scales (src/dkplsr.jl:112-119): the only use of the weights
     std::vector<double> xs((size_t)p, 1.0), ys((size_t)q, 1.0), mtmp((size_t)std::max(p, q));
-    JCH_TRY(jch_reserve(ctx, ctx->dk_s, sizeof(double) * ((size_t)p + q + (size_t)n)));
-    double *xs_dev = (double *)ctx->dk_s.ptr, *ys_dev = xs_dev + p, *w_dev = ys_dev + q;
-    if (scal) {
-        if (host && weights) {
-            JCH_HIP(ctx, hipMemcpyAsync(w_dev, weights, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            dw = w_dev;
-        }
-        JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, mtmp.data(), xs.data()));
-        JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dY, n, q, ldyd, dw, mtmp.data(), ys.data()));
-        JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
-        JCH_HIP(ctx, hipMemcpyAsync(ys_dev, ys.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
-        JCH_TRY(jch_launch_divcols(ctx, dY, ldyd, n, q, ys_dev));
-        if (inplace) JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));   // dkplsr! hands X back scaled; otherwise the Gram divides on the fly
-    }
-    // ---- K = kern(X, X) (src/dkplsr.jl:121), the symmetric path
-    double *Kd = K_out;
-    if (!Kd) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * (size_t)n * n));
-        Kd = (double *)ctx->dk_k.ptr;
-    }
-    const double *gdiv = scal && !inplace ? xs.data() : nullptr;
-    JCH_TRY(jch_launch_kgram(ctx, kind, dX, n, ldxd, gdiv, dX, n, ldxd, gdiv, p, gamma, coef0, degree, true, Kd, n));
-    // ---- plskern!(K, Y; nlv) (:122): no weights, in place on K and on the (scaled) Y
-    double *Tdev = T, *wn = weights_norm;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_o, sizeof(double) * (size_t)n * (kcap + 1)));
-        Tdev = T ? (double *)ctx->dk_o.ptr : nullptr;
-        wn = weights_norm ? (double *)ctx->dk_o.ptr + (size_t)n * kcap : nullptr;
-    }
-    jch_pls_desc di{};
-    di.n = n; di.p = n; di.q = q; di.nlv = d.nlv; di.scal = 0; di.dtype = JCH_F64; di.loc = JCH_LOC_DEVICE; di.inplace = 1; di.reserved = 0;
     int32_t got = 0;
-    JCH_TRY(jch_plskern_fit(ctx, &di, Kd, n, dY, ldyd, nullptr, Tdev, P, R, W, C, TT, xmeans, xscales, ymeans, yscales, wn, &got));
-    if (host) {
-        if (T) JCH_TRY(jch_copy2d(ctx, T, n, Tdev, n, n, got, hipMemcpyDeviceToHost));
-        if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        if (inplace) {
-            JCH_TRY(jch_copy2d(ctx, (double *)X, ldx, dX, ldxd, n, p, hipMemcpyDeviceToHost));
-            JCH_TRY(jch_copy2d(ctx, (double *)Y, ldy, dY, ldyd, n, q, hipMemcpyDeviceToHost));
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        // ---- device views: X (read; scaled in place only for dkplsr!), Y (the inner plskern! centres it: a working copy unless dkplsr!)
+        double *dX = (double *)X, *dY = (double *)Y;
+        const double *dw = weights;
+        int64_t ldxd = ldx, ldyd = ldy;
+        if (host) {
+            JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
+            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, (const double *)X, ldx, n, p, hipMemcpyHostToDevice));
+            dX = (double *)ctx->dk_x.ptr; ldxd = n;
         }
-    }
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (host || !inplace) {
+            JCH_TRY(jch_reserve(ctx, ctx->dk_y, sizeof(double) * (size_t)n * q));
+            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_y.ptr, n, (const double *)Y, ldy, n, q, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+            dY = (double *)ctx->dk_y.ptr; ldyd = n;
+        }
+        // ---- outer scales (src/dkplsr.jl:112-119): the only use of the weights
+        JCH_TRY(jch_reserve(ctx, ctx->dk_s, sizeof(double) * ((size_t)p + q + (size_t)n)));
+        double *xs_dev = (double *)ctx->dk_s.ptr, *ys_dev = xs_dev + p, *w_dev = ys_dev + q;
+        if (scal) {
+            if (host && weights) {
+                JCH_HIP(ctx, hipMemcpyAsync(w_dev, weights, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+                dw = w_dev;
+            }
+            JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, mtmp.data(), xs.data()));
+            JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dY, n, q, ldyd, dw, mtmp.data(), ys.data()));
+            JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
+            JCH_HIP(ctx, hipMemcpyAsync(ys_dev, ys.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
+            JCH_TRY(jch_launch_divcols(ctx, dY, ldyd, n, q, ys_dev));
+            if (inplace) JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));   // dkplsr! hands X back scaled; otherwise the Gram divides on the fly
+        }
+        // ---- K = kern(X, X) (src/dkplsr.jl:121), the symmetric path
+        double *Kd = K_out;
+        if (!Kd) {
+            JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * (size_t)n * n));
+            Kd = (double *)ctx->dk_k.ptr;
+        }
+        const double *gdiv = scal && !inplace ? xs.data() : nullptr;
+        JCH_TRY(jch_launch_kgram(ctx, kind, dX, n, ldxd, gdiv, dX, n, ldxd, gdiv, p, gamma, coef0, degree, true, Kd, n));
+        // ---- plskern!(K, Y; nlv) (:122): no weights, in place on K and on the (scaled) Y
+        double *Tdev = T, *wn = weights_norm;
+        if (host) {
+            JCH_TRY(jch_reserve(ctx, ctx->dk_o, sizeof(double) * (size_t)n * (kcap + 1)));
+            Tdev = T ? (double *)ctx->dk_o.ptr : nullptr;
+            wn = weights_norm ? (double *)ctx->dk_o.ptr + (size_t)n * kcap : nullptr;
+        }
+        jch_pls_desc di{};
+        di.n = n; di.p = n; di.q = q; di.nlv = d.nlv; di.scal = 0; di.dtype = JCH_F64; di.loc = JCH_LOC_DEVICE; di.inplace = 1; di.reserved = 0;
+        JCH_TRY(jch_plskern_fit(ctx, &di, Kd, n, dY, ldyd, nullptr, Tdev, P, R, W, C, TT, xmeans, xscales, ymeans, yscales, wn, &got));
+        if (host) {
+            if (T) JCH_TRY(jch_copy2d(ctx, T, n, Tdev, n, n, got, hipMemcpyDeviceToHost));
+            if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+            if (inplace) {
+                JCH_TRY(jch_copy2d(ctx, (double *)X, ldx, dX, ldxd, n, p, hipMemcpyDeviceToHost));
+                JCH_TRY(jch_copy2d(ctx, (double *)Y, ldy, dY, ldyd, n, q, hipMemcpyDeviceToHost));
+            }
+        }
+        return JCH_OK;
+    }));
     if (dk_xscales) std::copy(xs.begin(), xs.end(), dk_xscales);
     if (dk_yscales) std::copy(ys.begin(), ys.end(), dk_yscales);
     if (nlv_out) *nlv_out = got;

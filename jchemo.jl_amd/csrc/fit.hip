@@ -68,26 +68,6 @@ int32_t validate(jch_ctx *ctx, const fit_io &io, const char *who)
     return JCH_OK;
 }
 
-struct carve {
-    char *base; size_t off;
-    double *take(size_t count) { double *p = (double *)(base + off); off += ((count * sizeof(double)) + 255) & ~(size_t)255; return p; }
-};
-
-int32_t h2d_matrix(jch_ctx *ctx, double *dst, const double *src, int64_t n, int64_t cols, int64_t ld)
-{
-    if (ld == n) JCH_HIP(ctx, hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n * cols, hipMemcpyHostToDevice, ctx->stream));
-    else JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * n, src, sizeof(double) * ld, sizeof(double) * n, cols,
-                                       hipMemcpyHostToDevice, ctx->stream));
-    return JCH_OK;
-}
-int32_t d2h_matrix(jch_ctx *ctx, double *dst, const double *src, int64_t n, int64_t cols, int64_t ld)
-{
-    if (ld == n) JCH_HIP(ctx, hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n * cols, hipMemcpyDeviceToHost, ctx->stream));
-    else JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * ld, src, sizeof(double) * n, sizeof(double) * n, cols,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-    return JCH_OK;
-}
-
 float ev_ms(hipEvent_t a, hipEvent_t b)
 {
     float ms = 0.f;
@@ -249,8 +229,8 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         JCH_TRY(jch_reserve_xstage(ctx, sizeof(double) * (size_t)n * p, /*keep_copy =*/reuse_x));
         JCH_TRY(jch_reserve(ctx, ctx->ystage, sizeof(double) * (size_t)n * q));
         Xc = (double *)ctx->xstage.ptr; Yc = (double *)ctx->ystage.ptr; ldxc = n; ldyc = n;
-        if (!reuse_x) JCH_TRY(h2d_matrix(ctx, Xc, (const double *)io.X, n, p, io.ldx));   // (reuse: the staging copy of the previous fit is this X)
-        JCH_TRY(h2d_matrix(ctx, Yc, (const double *)io.Y, n, q, io.ldy));
+        if (!reuse_x) JCH_TRY(jch_copy2d(ctx, Xc, n, (const double *)io.X, io.ldx, n, p, hipMemcpyHostToDevice));   // (reuse: the staging copy of the previous fit is this X)
+        JCH_TRY(jch_copy2d(ctx, Yc, n, (const double *)io.Y, io.ldy, n, q, hipMemcpyHostToDevice));
         if (io.weights) {
             JCH_TRY(jch_reserve(ctx, ctx->wstage, sizeof(double) * (size_t)n));
             JCH_HIP(ctx, hipMemcpyAsync(ctx->wstage.ptr, io.weights, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -277,23 +257,24 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
                                                          (size_t)nlv_cap * q + 36 * nlv_cap + 1024 + (JCH_ZT_SLICES + 1) * ((size_t)ldr + 8 + qpad) + 2 * (size_t)(p + q) + 8 + 2 * (size_t)ldr + 128 +
                                                          (p <= JCH_SWEEP_MAXP ? jch_lv_split_doubles(p, nlv_cap) + 128 : 0));
     JCH_TRY(jch_reserve(ctx, ctx->small, small_bytes));
-    carve cv{(char *)ctx->small.ptr, 0};
+    jch_carve cv;
+    auto take = [&](size_t count) { return (double *)ctx->small.ptr + cv.take(count); };
     jch_small s;
-    s.K = cv.take((size_t)p * qpad); s.w = cv.take(ldr); s.r = cv.take(ldr);
+    s.K = take((size_t)p * qpad); s.w = take(ldr); s.r = take(ldr);
     // everything the caller gets back lives in ONE contiguous range [P .. niter]: fetched with a single D2H copy
-    s.P = cv.take((size_t)nlv_cap * p); s.R = cv.take((size_t)nlv_cap * p); s.W = cv.take((size_t)nlv_cap * p);
-    s.C = cv.take((size_t)nlv_cap * q); s.TT = cv.take(nlv_cap);
-    s.mom = cv.take(p + q); s.scl = cv.take(p + q);
-    double *niter_dev = cv.take(nlv_cap);
-    double *qual_dev = cv.take(8);   // [0]: pivot quality of the raw mode (fetched with the results)
-    double *mshift_buf = cv.take((size_t)ldr + 2);   // raw mode: means - pivot (both zeroed by the weights launch)
+    s.P = take((size_t)nlv_cap * p); s.R = take((size_t)nlv_cap * p); s.W = take((size_t)nlv_cap * p);
+    s.C = take((size_t)nlv_cap * q); s.TT = take(nlv_cap);
+    s.mom = take(p + q); s.scl = take(p + q);
+    double *niter_dev = take(nlv_cap);
+    double *qual_dev = take(8);   // [0]: pivot quality of the raw mode (fetched with the results)
+    double *mshift_buf = take((size_t)ldr + 2);   // raw mode: means - pivot (both zeroed by the weights launch)
     s.mshift = nullptr; s.rs = nullptr;
     const size_t out_bytes = (size_t)((char *)(qual_dev + 8) - (char *)s.P);
     double qual_host = 0.0;
-    s.Z = cv.take((size_t)nlv_cap * 16);
+    s.Z = take((size_t)nlv_cap * 16);
     const int ldz = (ldr + 1 + qpad + 7) & ~7;
-    s.zt = cv.take((size_t)JCH_ZT_SLICES * ldz); s.zpc = cv.take((size_t)ldr + qpad);
-    s.hdr = cv.take(8);
+    s.zt = take((size_t)JCH_ZT_SLICES * ldz); s.zpc = take((size_t)ldr + qpad);
+    s.hdr = take(8);
     s.variant = 0;
     s.niter = algo == ALGO_WOLD ? niter_dev : nullptr;
     s.kr = nullptr; s.gpart = nullptr; s.lvctr = nullptr;
@@ -314,14 +295,14 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         memcpy(&qual_host, h + ((const char *)qual_dev - (const char *)s.P), sizeof(double));
         return JCH_OK;
     };
-    s.dbg = jch_knob_set("JCH_LV_DEBUG") ? cv.take(512 + 16 * (nlv_cap + 2)) : nullptr;
+    s.dbg = jch_knob_set("JCH_LV_DEBUG") ? take(512 + 16 * (nlv_cap + 2)) : nullptr;
     // plsnipals / plswold with a narrow Y: the rewrite of X after every LV is postponed and done every `defer_m`-th LV
     // (k_sweep_lazy / k_kpass_lazy; JCH_NIPALS_DEFER=1 restores the eager deflation)
     int defer_m = 1;
     double *pend_p = nullptr;
     if (!kern_like && d.dtype == JCH_F64) {
         defer_m = std::max(1, std::min(jch_knob("JCH_NIPALS_DEFER", JCH_NIPALS_DEFER_DEFAULT), jch_nipals_lazy_capacity(ldr, q)));
-        if (defer_m > 1) pend_p = cv.take((size_t)defer_m * jch_nipals_lazy_pitch(ldr));
+        if (defer_m > 1) pend_p = take((size_t)defer_m * jch_nipals_lazy_pitch(ldr));
     }
 
     // OPT-IN one-pass NIPALS (JCH_NIPALS_ONE_PASS): the next X'DY by a rank-one update in the small-state kernel, rows written back
@@ -330,14 +311,14 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     double *zero16 = nullptr;
     if ((d.reserved & JCH_NIPALS_ONE_PASS) && !(onepass && pend_p && !inplace))
         return jch_fail(ctx, JCH_EINVAL, "%s: JCH_NIPALS_ONE_PASS needs plsnipals / plswold with q <= 16, p <= 2048, inplace = 0, Float64", who);
-    if (onepass) { zero16 = cv.take(16); JCH_HIP(ctx, hipMemsetAsync(zero16, 0, sizeof(double) * 16, ctx->stream)); s.variant = 3; }
+    if (onepass) { zero16 = take(16); JCH_HIP(ctx, hipMemsetAsync(zero16, 0, sizeof(double) * 16, ctx->stream)); s.variant = 3; }
     if (s.dbg) JCH_HIP(ctx, hipMemsetAsync(s.dbg, 0, sizeof(double) * (512 + 16 * (nlv_cap + 2)), ctx->stream));
     if (d.dtype == JCH_BF16) {   // bf16 storage mode (plskern only): its own prologue + sweep, same small-state kernels
         const bool fastb = q <= 16 && p <= JCH_SWEEP_MAXP && jch_lv_fast_lds_bytes(p, q, qpad, ldr, nlv_cap) <= 150 * 1024;
         {   // split small-state path (see the f64 loop below); the fused inbox exchange keeps the one-kernel path
             const bool fuse_b = ctx->p2p.ready && !ctx->loop;
             if (fastb && (!fuse_b || jch_lv_split_p2p_ok(ctx, p)) && jch_knob("JCH_LV_SPLIT", 1) != 0 && jch_lv_solve_lds_bytes(p, q, ldr, nlv_cap) <= 150 * 1024) {
-                s.kr = cv.take(16); JCH_TRY(jch_lv_split_begin_fit(ctx, s, cv.take(jch_lv_split_doubles(p, nlv_cap)), p, nlv_cap));
+                s.kr = take(16); JCH_TRY(jch_lv_split_begin_fit(ctx, s, take(jch_lv_split_doubles(p, nlv_cap)), p, nlv_cap));
             }
         }
         hipEvent_t evb = jch_ev(ctx);
@@ -401,7 +382,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         // (mshift and the pivot-quality word were zeroed by the weights launch above; the divisor slots `s.mom` handed to K2
         // as `scl` are never read with SCAL = false; k_extract_means moves the Y means and resets s.scl to ones)
         s.mshift = mshift_buf;
-        double *spread2 = cv.take(p);
+        double *spread2 = take(p);
         JCH_TRY(jch_launch_pivot(ctx, Xc, ldxc, n, p, s.hdr, s.scl, spread2));                      // scl[0..p): the pivot K2 subtracts
         JCH_TRY(jch_launch_moments(ctx, Yc, ldyc, nullptr, 0, dn, n, q, 0, nullptr, s.scl + p));  // Y means -> scl[p..p+q)
         bool from_copy = false;
@@ -414,7 +395,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         ctx->xcopy = xkey; ctx->xcopy_valid = true;   // the raw copy x - pivot of THIS X now sits in the workspace
         }
         if (d.scal) {   // stds from ONE streaming pass over the row-major copy; the scaling itself is folded into r / s and zp / s
-            s.rs = cv.take((size_t)ldr + 2);
+            s.rs = take((size_t)ldr + 2);
             JCH_HIP(ctx, hipMemsetAsync(s.rs, 0, sizeof(double) * ((size_t)ldr + 2), ctx->stream));
             JCH_TRY(jch_launch_raw_scales(ctx, Xr, n, p, ldr, dn, s.mshift, Yr, qpad, q, s.zt, s.scl, s.K));
         }
@@ -465,7 +446,7 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         // plsrosa on the fast path; not with the inbox all-reduce fused into the one-kernel path.  JCH_LV_SPLIT=0: the one-kernel path.
         split = (algo == ALGO_KERN || algo == ALGO_ROSA) && fast && jch_knob("JCH_LV_SPLIT", 1) != 0 &&
                 jch_lv_solve_lds_bytes(p, q, ldr, nlv) <= 150 * 1024 && (!fuse_inbox || jch_lv_split_p2p_ok(ctx, p));
-        if (split) { s.kr = cv.take(16); JCH_TRY(jch_lv_split_begin_fit(ctx, s, cv.take(jch_lv_split_doubles(p, nlv)), p, nlv)); }
+        if (split) { s.kr = take(16); JCH_TRY(jch_lv_split_begin_fit(ctx, s, take(jch_lv_split_doubles(p, nlv)), p, nlv)); }
         JCH_TRY(jch_launch_lv_update(ctx, s, p, q, qpad, ldr, -1, nlv, kern_like ? 0 : 1, 1, ldz, fast));
     }
     int npend = 0, pend_a0 = 0;   // postponed deflations: LVs pend_a0 .. pend_a0 + npend - 1
@@ -579,8 +560,8 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
         if (!tcopy.active() || variant2) JCH_TRY(d2h(io.T, Tdev, (size_t)n * nlv));
         JCH_TRY(d2h(io.weights_norm, dn, (size_t)n));
         if (inplace) {
-            JCH_TRY(d2h_matrix(ctx, (double *)io.X, Xc, n, p, io.ldx));
-            JCH_TRY(d2h_matrix(ctx, (double *)io.Y, Yc, n, q, io.ldy));
+            JCH_TRY(jch_copy2d(ctx, (double *)io.X, io.ldx, Xc, n, n, p, hipMemcpyDeviceToHost));
+            JCH_TRY(jch_copy2d(ctx, (double *)io.Y, io.ldy, Yc, n, n, q, hipMemcpyDeviceToHost));
         }
     }
     tl_enq = now_ms();
@@ -637,6 +618,14 @@ int32_t fit_impl(jch_ctx *ctx, const fit_io &io, int algo, bool allow_raw = true
     return JCH_OK;
 }
 
+// The seven fits below: fit_impl ends synchronised on every success path; a host call that failed drains the copies it queued on the
+// caller's arrays (jch_synced_on_failure), so a successful fit does exactly the stream operations of fit_impl.
+int32_t fit_entry(jch_ctx *ctx, const fit_io &io, int algo)
+{
+    if (!ctx) return JCH_EINVAL;
+    return jch_synced_on_failure(ctx, io.d && io.d->loc == JCH_LOC_HOST, [&]() -> int32_t { return fit_impl(ctx, io, algo); });
+}
+
 }  // namespace
 
 extern "C" int32_t jch_plskern_fit(jch_ctx *ctx, const jch_pls_desc *desc, void *X, int64_t ldx, void *Y, int64_t ldy,
@@ -645,7 +634,7 @@ extern "C" int32_t jch_plskern_fit(jch_ctx *ctx, const jch_pls_desc *desc, void 
                                    int32_t *nlv_out)
 {
     fit_io io{desc, X, ldx, Y, ldy, weights, T, P, R, W, C, TT, xmeans, xscales, ymeans, yscales, weights_norm, nlv_out};
-    return fit_impl(ctx, io, 0);
+    return fit_entry(ctx, io, 0);
 }
 
 extern "C" int32_t jch_plsnipals_fit(jch_ctx *ctx, const jch_pls_desc *desc, void *X, int64_t ldx, void *Y, int64_t ldy,
@@ -654,7 +643,7 @@ extern "C" int32_t jch_plsnipals_fit(jch_ctx *ctx, const jch_pls_desc *desc, voi
                                      int32_t *nlv_out)
 {
     fit_io io{desc, X, ldx, Y, ldy, weights, T, P, R, W, C, TT, xmeans, xscales, ymeans, yscales, weights_norm, nlv_out};
-    return fit_impl(ctx, io, 1);
+    return fit_entry(ctx, io, 1);
 }
 
 extern "C" int32_t jch_plssimp_fit(jch_ctx *ctx, const jch_pls_desc *desc, void *X, int64_t ldx, void *Y, int64_t ldy,
@@ -663,7 +652,7 @@ extern "C" int32_t jch_plssimp_fit(jch_ctx *ctx, const jch_pls_desc *desc, void 
                                    int32_t *nlv_out)
 {
     fit_io io{desc, X, ldx, Y, ldy, weights, T, P, R, W, C, TT, xmeans, xscales, ymeans, yscales, weights_norm, nlv_out};
-    return fit_impl(ctx, io, ALGO_SIMP);
+    return fit_entry(ctx, io, ALGO_SIMP);
 }
 
 extern "C" int32_t jch_plsrosa_fit(jch_ctx *ctx, const jch_pls_desc *desc, void *X, int64_t ldx, void *Y, int64_t ldy,
@@ -672,7 +661,7 @@ extern "C" int32_t jch_plsrosa_fit(jch_ctx *ctx, const jch_pls_desc *desc, void 
                                    int32_t *nlv_out)
 {
     fit_io io{desc, X, ldx, Y, ldy, weights, T, P, R, W, C, TT, xmeans, xscales, ymeans, yscales, weights_norm, nlv_out};
-    return fit_impl(ctx, io, ALGO_ROSA);
+    return fit_entry(ctx, io, ALGO_ROSA);
 }
 
 extern "C" int32_t jch_plswold_fit(jch_ctx *ctx, const jch_pls_desc *desc, void *X, int64_t ldx, void *Y, int64_t ldy,
@@ -682,7 +671,7 @@ extern "C" int32_t jch_plswold_fit(jch_ctx *ctx, const jch_pls_desc *desc, void 
 {
     fit_io io{desc, X, ldx, Y, ldy, weights, T, P, R, W, C, TT, xmeans, xscales, ymeans, yscales, weights_norm, nlv_out};
     io.tol = tol; io.maxit = maxit; io.niter = niter;
-    return fit_impl(ctx, io, ALGO_WOLD);
+    return fit_entry(ctx, io, ALGO_WOLD);
 }
 
 extern "C" int32_t jch_plskern_fit_scaled(jch_ctx *ctx, const jch_pls_desc *desc, void *X, int64_t ldx, void *Y, int64_t ldy,
@@ -694,7 +683,7 @@ extern "C" int32_t jch_plskern_fit_scaled(jch_ctx *ctx, const jch_pls_desc *desc
     if (ctx && !xscales_in) return jch_fail(ctx, JCH_EINVAL, "jch_plskern_fit_scaled: xscales_in is NULL");
     if (ctx && desc && desc->dtype != JCH_F64) return jch_fail(ctx, JCH_EINVAL, "jch_plskern_fit_scaled: Float64 only");
     io.xscales_in = xscales_in; io.yscales_in = yscales_in;
-    return fit_impl(ctx, io, ALGO_KERN);
+    return fit_entry(ctx, io, ALGO_KERN);
 }
 
 // Weighted column means and (optionally) uncorrected standard deviations: `colmean` / `colstd` (src/utility.jl:193-195,
@@ -707,27 +696,28 @@ extern "C" int32_t jch_col_stats(jch_ctx *ctx, int32_t loc, const double *X, int
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "jch_col_stats: bad loc");
     if (p > (1 << 20)) return jch_fail(ctx, JCH_EINVAL, "jch_col_stats: p too large");
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    const double *dX = X, *dw = weights;
-    int64_t ldxd = ldx;
-    if (loc == JCH_LOC_HOST) {
+    const bool host = loc == JCH_LOC_HOST;
+    if (host) {
         JCH_TRY(jch_reserve_xstage(ctx, sizeof(double) * (size_t)n * p));   // (the staging buffer a host-array fit would re-use is overwritten)
-        JCH_TRY(h2d_matrix(ctx, (double *)ctx->xstage.ptr, X, n, p, ldx));
-        dX = (const double *)ctx->xstage.ptr; ldxd = n;
-        if (weights) {
-            JCH_TRY(jch_reserve(ctx, ctx->wstage, sizeof(double) * (size_t)n));
-            JCH_HIP(ctx, hipMemcpyAsync(ctx->wstage.ptr, weights, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            dw = (const double *)ctx->wstage.ptr;
-        }
+        if (weights) JCH_TRY(jch_reserve(ctx, ctx->wstage, sizeof(double) * (size_t)n));
     }
     JCH_TRY(jch_reserve(ctx, ctx->dnorm, sizeof(double) * (size_t)n));
     JCH_TRY(jch_reserve(ctx, ctx->small, sizeof(double) * (2 * (size_t)p + 64)));
-    double *mom = (double *)ctx->small.ptr, *scl = mom + p, *hdr = scl + p;
-    double *dn = (double *)ctx->dnorm.ptr;
-    JCH_TRY(jch_launch_weights(ctx, dw, n, dn, hdr));
-    JCH_TRY(jch_launch_moments(ctx, dX, ldxd, nullptr, 0, dn, n, (int)p, 0, nullptr, mom));
-    if (stds) JCH_TRY(jch_launch_moments(ctx, dX, ldxd, nullptr, 0, dn, n, (int)p, 0, mom, scl));
-    JCH_HIP(ctx, hipMemcpyAsync(means, mom, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
-    if (stds) JCH_HIP(ctx, hipMemcpyAsync(stds, scl, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JCH_OK;
+    return jch_synced(ctx, true, [&]() -> int32_t {
+        const double *dX = X, *dw = weights;
+        int64_t ldxd = ldx;
+        JCH_TRY(jch_stage_in(ctx, host, (double *)ctx->xstage.ptr, n, p, &dX, &ldxd));
+        if (host && weights) {
+            JCH_HIP(ctx, hipMemcpyAsync(ctx->wstage.ptr, weights, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+            dw = (const double *)ctx->wstage.ptr;
+        }
+        double *mom = (double *)ctx->small.ptr, *scl = mom + p, *hdr = scl + p;
+        double *dn = (double *)ctx->dnorm.ptr;
+        JCH_TRY(jch_launch_weights(ctx, dw, n, dn, hdr));
+        JCH_TRY(jch_launch_moments(ctx, dX, ldxd, nullptr, 0, dn, n, (int)p, 0, nullptr, mom));
+        if (stds) JCH_TRY(jch_launch_moments(ctx, dX, ldxd, nullptr, 0, dn, n, (int)p, 0, mom, scl));
+        JCH_HIP(ctx, hipMemcpyAsync(means, mom, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+        if (stds) JCH_HIP(ctx, hipMemcpyAsync(stds, scl, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+        return JCH_OK;
+    });
 }

@@ -519,28 +519,24 @@ extern "C" int32_t jch_affine_gemm(jch_ctx *ctx, int32_t loc, const double *X, i
         }
         b2[c] = acc;
     }
+    const bool host = loc == JCH_LOC_HOST;
     JCH_TRY(jch_reserve(ctx, ctx->gemm_b, sizeof(double) * hb.size()));
-    double *dB = (double *)ctx->gemm_b.ptr;
-    JCH_HIP(ctx, hipMemcpyAsync(dB, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, ctx->stream));
-    const double *dX = X;
-    double *dO = out;
-    int64_t ldxd = ldx, ldod = ldo;
-    if (loc == JCH_LOC_HOST) {
+    if (host) {
         JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)m * p));
         JCH_TRY(jch_reserve(ctx, ctx->gemm_out, sizeof(double) * (size_t)m * k));
-        if (ldx == m) JCH_HIP(ctx, hipMemcpyAsync(ctx->xq.ptr, X, sizeof(double) * (size_t)m * p, hipMemcpyHostToDevice, ctx->stream));
-        else JCH_HIP(ctx, hipMemcpy2DAsync(ctx->xq.ptr, sizeof(double) * m, X, sizeof(double) * ldx, sizeof(double) * m, p,
-                                           hipMemcpyHostToDevice, ctx->stream));
-        dX = (const double *)ctx->xq.ptr; dO = (double *)ctx->gemm_out.ptr; ldxd = m; ldod = m;
     }
-    JCH_TRY(jch_launch_affine_gemm(ctx, dX, m, (int)p, ldxd, dB, (int)k, kpad, dB + (size_t)p * kpad, dO, ldod));
-    if (loc == JCH_LOC_HOST) {
-        if (ldo == m) JCH_HIP(ctx, hipMemcpyAsync(out, dO, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, ctx->stream));
-        else JCH_HIP(ctx, hipMemcpy2DAsync(out, sizeof(double) * ldo, dO, sizeof(double) * m, sizeof(double) * m, k,
-                                           hipMemcpyDeviceToHost, ctx->stream));
-    }
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // also keeps `hb` alive until the H2D copy is done
-    return JCH_OK;
+    return jch_synced(ctx, true, [&]() -> int32_t {
+        double *dB = (double *)ctx->gemm_b.ptr;
+        JCH_HIP(ctx, hipMemcpyAsync(dB, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, ctx->stream));
+        const double *dX = X;
+        int64_t ldxd = ldx;
+        JCH_TRY(jch_stage_in(ctx, host, (double *)ctx->xq.ptr, m, p, &dX, &ldxd));
+        double *dO = host ? (double *)ctx->gemm_out.ptr : out;
+        const int64_t ldod = host ? m : ldo;
+        JCH_TRY(jch_launch_affine_gemm(ctx, dX, m, (int)p, ldxd, dB, (int)k, kpad, dB + (size_t)p * kpad, dO, ldod));
+        if (host) JCH_TRY(jch_copy2d(ctx, out, ldo, dO, m, m, k, hipMemcpyDeviceToHost));
+        return JCH_OK;
+    });
 }
 
 // sstot of `summary` (src/plskern.jl:250-251): sum_j (1/scale_j^2) * sum_i d_i (x_ij - shift_j)^2 — the K1
@@ -552,26 +548,28 @@ extern "C" int32_t jch_weighted_ss(jch_ctx *ctx, int32_t loc, const double *X, i
     if (!X || !d || !sstot || n < 1 || p < 1 || ldx < n) return jch_fail(ctx, JCH_EINVAL, "jch_weighted_ss: bad arguments");
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "jch_weighted_ss: bad loc");
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    const double *dX = X, *dd = d;
-    int64_t ldxd = ldx;
-    if (loc == JCH_LOC_HOST) {
+    const bool host = loc == JCH_LOC_HOST;
+    if (host) {
         JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)n * p));
         JCH_TRY(jch_reserve(ctx, ctx->wstage, sizeof(double) * (size_t)n));
-        if (ldx == n) JCH_HIP(ctx, hipMemcpyAsync(ctx->xq.ptr, X, sizeof(double) * (size_t)n * p, hipMemcpyHostToDevice, ctx->stream));
-        else JCH_HIP(ctx, hipMemcpy2DAsync(ctx->xq.ptr, sizeof(double) * n, X, sizeof(double) * ldx, sizeof(double) * n, p,
-                                           hipMemcpyHostToDevice, ctx->stream));
-        JCH_HIP(ctx, hipMemcpyAsync(ctx->wstage.ptr, d, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        dX = (const double *)ctx->xq.ptr; dd = (const double *)ctx->wstage.ptr; ldxd = n;
     }
     JCH_TRY(jch_reserve(ctx, ctx->gemm_b, sizeof(double) * 2 * (size_t)p));
-    double *dshift = (double *)ctx->gemm_b.ptr, *dvar = dshift + p;
-    std::vector<double> hs((size_t)p, 0.0);
+    std::vector<double> hs((size_t)p, 0.0), hv((size_t)p);
     if (shift) for (int64_t j = 0; j < p; ++j) hs[j] = shift[j];
-    JCH_HIP(ctx, hipMemcpyAsync(dshift, hs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
-    JCH_TRY(jch_launch_moments(ctx, dX, ldxd, nullptr, 0, dd, n, (int)p, 0, dshift, dvar, false));
-    std::vector<double> hv((size_t)p);
-    JCH_HIP(ctx, hipMemcpyAsync(hv.data(), dvar, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        const double *dX = X, *dd = d;
+        int64_t ldxd = ldx;
+        JCH_TRY(jch_stage_in(ctx, host, (double *)ctx->xq.ptr, n, p, &dX, &ldxd));
+        if (host) {
+            JCH_HIP(ctx, hipMemcpyAsync(ctx->wstage.ptr, d, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+            dd = (const double *)ctx->wstage.ptr;
+        }
+        double *dshift = (double *)ctx->gemm_b.ptr, *dvar = dshift + p;
+        JCH_HIP(ctx, hipMemcpyAsync(dshift, hs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
+        JCH_TRY(jch_launch_moments(ctx, dX, ldxd, nullptr, 0, dd, n, (int)p, 0, dshift, dvar, false));
+        JCH_HIP(ctx, hipMemcpyAsync(hv.data(), dvar, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+        return JCH_OK;
+    }));
     double s = 0.0;
     for (int64_t j = 0; j < p; ++j) { const double sc = scale ? scale[j] : 1.0; s += hv[j] / (sc * sc); }
     *sstot = s;
@@ -703,32 +701,27 @@ extern "C" int32_t jch_predict(jch_ctx *ctx, int32_t loc, const double *X, int64
             for (int64_t k = 0; k < q; ++k) Cs[(size_t)c * q + k] = C[k + (size_t)c * q] * (yscales ? yscales[k] : 1.0);
         }
         for (int64_t k = 0; k < q; ++k) y0[k] = ymeans ? ymeans[k] : 0.0;
+        const bool host = loc == JCH_LOC_HOST;
+        const int64_t ldt = (m + 1) & ~(int64_t)1, ldod = host ? ldt : ldo;
         JCH_TRY(jch_reserve(ctx, ctx->gemm_b, sizeof(double) * hb.size()));
-        double *dB = (double *)ctx->gemm_b.ptr;
-        JCH_HIP(ctx, hipMemcpyAsync(dB, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, ctx->stream));
-        const int64_t ldt = (m + 1) & ~(int64_t)1;
         JCH_TRY(jch_reserve(ctx, ctx->tbuf, sizeof(double) * (size_t)ldt * kh));
-        double *Tq = (double *)ctx->tbuf.ptr;
-        const double *dX = X;
-        double *dO = pred;
-        int64_t ldxd = ldx, ldod = ldo;
-        if (loc == JCH_LOC_HOST) {
-            ldod = ldt;
+        if (host) {
             JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)m * p));
             JCH_TRY(jch_reserve(ctx, ctx->gemm_out, sizeof(double) * (size_t)ldod * kcols));
-            if (ldx == m) JCH_HIP(ctx, hipMemcpyAsync(ctx->xq.ptr, X, sizeof(double) * (size_t)m * p, hipMemcpyHostToDevice, ctx->stream));
-            else JCH_HIP(ctx, hipMemcpy2DAsync(ctx->xq.ptr, sizeof(double) * m, X, sizeof(double) * ldx, sizeof(double) * m, p,
-                                               hipMemcpyHostToDevice, ctx->stream));
-            dX = (const double *)ctx->xq.ptr; dO = (double *)ctx->gemm_out.ptr; ldxd = m;
         }
-        JCH_TRY(jch_launch_affine_gemm(ctx, dX, m, (int)p, ldxd, dB, kh, kpad, dB + (size_t)p * kpad, Tq, ldt));
-        JCH_TRY(jch_launch_predict_prefix(ctx, Tq, m, ldt, dB + (size_t)p * kpad + kpad, dB + (size_t)p * kpad + kpad + (size_t)kh * q, (int)q,
-                                          nlv_lo, nlv_hi, dO, ldod));
-        if (loc == JCH_LOC_HOST)
-            JCH_HIP(ctx, hipMemcpy2DAsync(pred, sizeof(double) * ldo, dO, sizeof(double) * ldod, sizeof(double) * m, kcols,
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // also keeps `hb` alive until the H2D copy is done
-        return JCH_OK;
+        return jch_synced(ctx, true, [&]() -> int32_t {
+            double *dB = (double *)ctx->gemm_b.ptr, *Tq = (double *)ctx->tbuf.ptr;
+            JCH_HIP(ctx, hipMemcpyAsync(dB, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, ctx->stream));
+            const double *dX = X;
+            int64_t ldxd = ldx;
+            JCH_TRY(jch_stage_in(ctx, host, (double *)ctx->xq.ptr, m, p, &dX, &ldxd));
+            double *dO = host ? (double *)ctx->gemm_out.ptr : pred;
+            JCH_TRY(jch_launch_affine_gemm(ctx, dX, m, (int)p, ldxd, dB, kh, kpad, dB + (size_t)p * kpad, Tq, ldt));
+            JCH_TRY(jch_launch_predict_prefix(ctx, Tq, m, ldt, dB + (size_t)p * kpad + kpad, dB + (size_t)p * kpad + kpad + (size_t)kh * q, (int)q,
+                                              nlv_lo, nlv_hi, dO, ldod));
+            if (host) JCH_TRY(jch_copy2d(ctx, pred, ldo, dO, ldod, m, kcols, hipMemcpyDeviceToHost));
+            return JCH_OK;
+        });
     }
     std::vector<double> B((size_t)p * kcols, 0.0), b0((size_t)kcols, 0.0), cur((size_t)p * q, 0.0);
     for (int a = 0; a <= nlv_hi; ++a) {

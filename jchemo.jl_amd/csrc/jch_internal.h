@@ -352,9 +352,6 @@ int32_t jch_colselect_reserve(jch_ctx *ctx, int64_t p);
 int32_t jch_launch_col_median_mad(jch_ctx *ctx, const double *X, int64_t n, int64_t p, int64_t ldx, double *med, double *mad);
 // kmethod.hip: what the kernel-method entry points (dkplsr.hip, kplsr.hip, kpca.hip, krr.hip) share
 int32_t jch_check_kernel(jch_ctx *ctx, const char *who, int32_t kind, int32_t degree);   // kernel kind / degree, one rank only
-// column-major rows x cols matrix from src (ld lds) to dst (ld ldd) on ctx->stream
-int32_t jch_copy2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols, hipMemcpyKind kind);
-unsigned jch_grid1(const jch_ctx *ctx, int64_t work);   // workgroups of 256 threads of a grid-stride element-wise launch
 int32_t jch_launch_divcols(jch_ctx *ctx, double *A, int64_t lda, int64_t n, int64_t cols, const double *s_dev);   // A[:, k] /= s[k]
 int32_t jch_launch_sqrt(jch_ctx *ctx, const double *w, int64_t n, double *sw);                                    // sw = sqrt(w)
 // rows of new data per Gram block of a transform / predict over n training rows: knob (the caller's JCH_*_QBLOCK) when >= 1, else 1 GiB of Gram
@@ -377,6 +374,35 @@ int32_t jch_launch_chol_solve(jch_ctx *ctx, const double *L, int64_t n, int64_t 
 int32_t jch_launch_chol_inv_fro2(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *out_dev, const int *info_dev);
 int32_t jch_chol_info_word(jch_ctx *ctx, int **info_dev);   // the ctx's own device info word
 // util.hip
+unsigned jch_grid1(const jch_ctx *ctx, int64_t work);   // workgroups of 256 threads of a grid-stride element-wise launch
+// The only strided matrix copy of the library: column-major rows x cols from src (ld lds) to dst (ld ldd) on ctx->stream; one
+// contiguous copy when both pitches equal rows.
+int32_t jch_copy2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols, hipMemcpyKind kind);
+// A matrix operand (rows x cols) of an entry with a `loc`: a host call uploads *src (ld *ld) into dst (ld rows) and leaves *src = dst,
+// *ld = rows; a device call leaves both as they are.  Vectors and index lists stay plain hipMemcpyAsync lines.
+int32_t jch_stage_in(jch_ctx *ctx, bool host, double *dst, int64_t rows, int64_t cols, const double **src, int64_t *ld);
+// The frame of a host-array call.  Such a call queues asynchronous copies on the caller's pageable arrays and on its own local host
+// images, and none of that memory may be released before the stream has drained, on the failure paths too.  So: between the first copy
+// queued on host memory and this synchronisation, nothing returns except through the frame.  Runs body(); with `sync`, synchronises
+// ctx->stream whatever body returned; returns body's failure if there was one, else the synchronisation's status.  sync == false (device
+// in, device out: enqueued only) returns body's status unchanged.
+template <class F> int32_t jch_synced(jch_ctx *ctx, bool sync, F &&body)
+{
+    const int32_t st = body();
+    if (!sync) return st;
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (st != JCH_OK) return st;
+    JCH_HIP(ctx, es);
+    return JCH_OK;
+}
+// The same frame around a body that ends synchronised on every success path of its own (fit_impl, lw_run): the success path does exactly
+// the stream operations of the body; the stream is drained here only when body failed (and `sync`: host memory may have copies queued).
+template <class F> int32_t jch_synced_on_failure(jch_ctx *ctx, bool sync, F &&body)
+{
+    const int32_t st = body();
+    if (st != JCH_OK && sync) (void)hipStreamSynchronize(ctx->stream);
+    return st;
+}
 int32_t jch_launch_fill(jch_ctx *ctx, double *out, int64_t n, int64_t p, int64_t ld, int64_t row0, int64_t n_total,
                         uint64_t seed);
 

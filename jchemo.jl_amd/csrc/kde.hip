@@ -256,7 +256,7 @@ extern "C" int32_t jch_kde_dens(jch_ctx *ctx, int32_t loc, const double *Z, int6
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     JCH_TRY(jch_reserve(ctx, ctx->kd_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kd_ws.ptr;
-    auto run = [&]() -> int32_t {
+    return jch_synced(ctx, true, [&]() -> int32_t {
         JCH_HIP(ctx, hipMemcpyAsync(ws, small.data(), sizeof(double) * n_small, hipMemcpyHostToDevice, ctx->stream));
         kde_args g;
         g.Xq = Xq; g.ldq = ldq; g.m = m; g.Z = Z; g.ldz = ldz;
@@ -282,10 +282,5 @@ extern "C" int32_t jch_kde_dens(jch_ctx *ctx, int32_t loc, const double *Z, int6
         JCH_HIP(ctx, hipGetLastError());
         if (host) JCH_TRY(jch_copy2d(ctx, out, ldo, dout, m, m, ncm, hipMemcpyDeviceToHost));
         return JCH_OK;
-    };
-    const int32_t st = run();
-    const hipError_t es = hipStreamSynchronize(ctx->stream);   // on the failure paths too: `small` and a host call's arrays have copies queued
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
-    return JCH_OK;
+    });
 }

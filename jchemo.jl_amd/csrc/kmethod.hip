@@ -1,5 +1,5 @@
-// What the kernel-method entry points share (dkplsr.hip, kplsr.hip, kpca.hip, krr.hip): the kernel / rank check, strided copies,
-// the grid of an element-wise launch, the column divide and sqrt kernels, and transform / predict over Gram blocks of new rows.
+// What the kernel-method entry points share (dkplsr.hip, kplsr.hip, kpca.hip, krr.hip): the kernel / rank check,
+// the column divide and sqrt kernels, and transform / predict over Gram blocks of new rows.
 #include <math.h>
 
 #include <algorithm>
@@ -27,17 +27,6 @@ int32_t jch_check_kernel(jch_ctx *ctx, const char *who, int32_t kind, int32_t de
     if (kind == JCH_KERN_POL && degree < 1) return jch_fail(ctx, JCH_EINVAL, "%s: degree = %d must be >= 1", who, degree);
     if (ctx->nranks > 1) return jch_fail(ctx, JCH_EINVAL, "%s: the Gram matrix is not sharded: one rank only (communicator of %d)", who, ctx->nranks);
     return JCH_OK;
-}
-
-int32_t jch_copy2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols, hipMemcpyKind kind)
-{
-    JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * ldd, src, sizeof(double) * lds, sizeof(double) * rows, cols, kind, ctx->stream));
-    return JCH_OK;
-}
-
-unsigned jch_grid1(const jch_ctx *ctx, int64_t work)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, (int64_t)ctx->cus * 16));
 }
 
 int32_t jch_launch_divcols(jch_ctx *ctx, double *A, int64_t lda, int64_t n, int64_t cols, const double *s_dev)
@@ -81,32 +70,28 @@ int32_t jch_kblocks_run(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, d
                         int64_t ldo, const jch_kblock_step &step)
 {
     const bool host = loc == JCH_LOC_HOST;
-    const double *dXt = Xt;
-    int64_t ldxtd = ldxt;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, Xt, ldxt, n, p, hipMemcpyHostToDevice));
-        dXt = (const double *)ctx->dk_x.ptr; ldxtd = n;
-        JCH_TRY(jch_reserve(ctx, ctx->dk_q, sizeof(double) * (size_t)mb * p));
-        JCH_TRY(jch_reserve(ctx, ctx->dk_o, sizeof(double) * (size_t)mb * ncols));
-    }
-    JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * (size_t)mb * n));
-    double *Kb = (double *)ctx->dk_k.ptr;
-    for (int64_t r0 = 0; r0 < m; r0 += mb) {
-        const int64_t rows = std::min(mb, m - r0);
-        const double *Zb = X + r0;
-        int64_t ldz = ldx;
-        double *ob = out + r0;
-        int64_t ldob = ldo;
+    return jch_synced(ctx, true, [&]() -> int32_t {   // (from the top: the caller may have queued uploads of its model's host vectors)
         if (host) {
-            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_q.ptr, rows, X + r0, ldx, rows, p, hipMemcpyHostToDevice));
-            Zb = (const double *)ctx->dk_q.ptr; ldz = rows;
-            ob = (double *)ctx->dk_o.ptr; ldob = rows;
+            JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
+            JCH_TRY(jch_reserve(ctx, ctx->dk_q, sizeof(double) * (size_t)mb * p));
+            JCH_TRY(jch_reserve(ctx, ctx->dk_o, sizeof(double) * (size_t)mb * ncols));
         }
-        JCH_TRY(jch_launch_kgram(ctx, kind, Zb, rows, ldz, xscale, dXt, n, ldxtd, nullptr, p, gamma, coef0, degree, false, Kb, rows));
-        JCH_TRY(step(Kb, rows, ob, ldob));
-        if (host) JCH_TRY(jch_copy2d(ctx, out + r0, ldo, ob, ldob, rows, ncols, hipMemcpyDeviceToHost));
-    }
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JCH_OK;
+        JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * (size_t)mb * n));
+        const double *dXt = Xt;
+        int64_t ldxtd = ldxt;
+        JCH_TRY(jch_stage_in(ctx, host, (double *)ctx->dk_x.ptr, n, p, &dXt, &ldxtd));
+        double *Kb = (double *)ctx->dk_k.ptr;
+        for (int64_t r0 = 0; r0 < m; r0 += mb) {
+            const int64_t rows = std::min(mb, m - r0);
+            const double *Zb = X + r0;
+            int64_t ldz = ldx;
+            JCH_TRY(jch_stage_in(ctx, host, (double *)ctx->dk_q.ptr, rows, p, &Zb, &ldz));
+            double *ob = host ? (double *)ctx->dk_o.ptr : out + r0;
+            const int64_t ldob = host ? rows : ldo;
+            JCH_TRY(jch_launch_kgram(ctx, kind, Zb, rows, ldz, xscale, dXt, n, ldxtd, nullptr, p, gamma, coef0, degree, false, Kb, rows));
+            JCH_TRY(step(Kb, rows, ob, ldob));
+            if (host) JCH_TRY(jch_copy2d(ctx, out + r0, ldo, ob, ldob, rows, ncols, hipMemcpyDeviceToHost));
+        }
+        return JCH_OK;
+    });
 }

@@ -209,8 +209,7 @@ extern "C" int32_t jch_knn_prepare(jch_ctx *ctx, int32_t loc, const double *Ztra
     auto fail = [&](int32_t st) { (void)hipFree(mo->Zt); (void)hipFree(mo->screen_mem); delete mo; return st; };
     if (hipMalloc((void **)&mo->Zt, sizeof(double) * (size_t)n * (size_t)dd) != hipSuccess)
         return fail(jch_fail(ctx, JCH_ENOMEM, "jch_knn_prepare: device allocation failed (%lld x %lld search space)", (long long)n, (long long)dd));
-    if (hipMemcpy2DAsync(mo->Zt, sizeof(double) * n, Ztrain, sizeof(double) * ldzt, sizeof(double) * n, dd,
-                         loc == JCH_LOC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+    if (jch_copy2d(ctx, mo->Zt, n, Ztrain, ldzt, n, dd, loc == JCH_LOC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice) != JCH_OK)
         return fail(jch_fail(ctx, JCH_EHIP, "jch_knn_prepare: copy of the search space failed"));
     if (dd <= 62 && n < ((int64_t)1 << 26)) {   // (whether a call is screened also depends on its k: jch_knn_screen_shape_ok)
         // (no memory for the operand copy: the handle works without it — every screened call then builds it in the ctx workspace)
@@ -269,18 +268,17 @@ extern "C" int32_t jch_knn_search(jch_ctx *ctx, const jch_knn_model *model, int3
     const size_t o_sc = big ? cv.take((size_t)post_blocks * 2 * (size_t)k) : 0;
     JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kn_ws.ptr;
-    const double *dZq = Zq;
-    const int64_t *dself = self;
-    int64_t ldq = ldzq;
-    auto run = [&](int **sflags) -> int32_t {
-        if (hin) {
-            JCH_TRY(jch_copy2d(ctx, ws + o_zq, m, Zq, ldzq, m, dd, hipMemcpyHostToDevice));
-            dZq = ws + o_zq; ldq = m;
-            if (self) {
-                JCH_HIP(ctx, hipMemcpyAsync(ws + o_self, self, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-                dself = (const int64_t *)(ws + o_self);
-            }
+    std::vector<int> hsf;   // the screen's per-query flags, fetched by a host-output call that was screened
+    JCH_TRY(jch_synced(ctx, hin || hout, [&]() -> int32_t {
+        const double *dZq = Zq;
+        const int64_t *dself = self;
+        int64_t ldq = ldzq;
+        JCH_TRY(jch_stage_in(ctx, hin, ws + o_zq, m, dd, &dZq, &ldq));
+        if (hin && self) {
+            JCH_HIP(ctx, hipMemcpyAsync(ws + o_self, self, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+            dself = (const int64_t *)(ws + o_self);
         }
+        int *sflags = nullptr;
         knn_args a;
         a.Zt = model->Zt; a.ldzt = n; a.n = n; a.Zq = dZq; a.ldzq = ldq; a.m = (int)m; a.dd = (int)dd; a.k = k1;
         a.h = h; a.cri = 4.0; a.tol = tol;
@@ -290,7 +288,7 @@ extern "C" int32_t jch_knn_search(jch_ctx *ctx, const jch_knn_model *model, int3
             if (dist) a.dist = dist;
             if (w) a.w = w;
         }
-        JCH_TRY(jch_knn_dispatch(ctx, a, model->has_screen ? &model->screen : nullptr, &model->screen_off, sflags));
+        JCH_TRY(jch_knn_dispatch(ctx, a, model->has_screen ? &model->screen : nullptr, &model->screen_off, &sflags));
         const int *rind = a.ind;
         const double *rdist = a.dist, *rw = a.w, *rmed = nullptr;
         if (post) {
@@ -313,21 +311,12 @@ extern "C" int32_t jch_knn_search(jch_ctx *ctx, const jch_knn_model *model, int3
             if (w) JCH_HIP(ctx, hipMemcpyAsync(w, rw, sizeof(double) * mk, hipMemcpyDeviceToHost, ctx->stream));
             if (dmed) JCH_HIP(ctx, hipMemcpyAsync(dmed, rmed, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         }
+        if (sflags && hout) {
+            hsf.resize((size_t)m);
+            JCH_HIP(ctx, hipMemcpyAsync(hsf.data(), sflags, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        }
         return JCH_OK;
-    };
-    int *sflags = nullptr;
-    const int32_t st = run(&sflags);
-    if (!hin && !hout) return st;                              // device in, device out: enqueued only
-    std::vector<int> hsf;
-    hipError_t ef = hipSuccess;
-    if (st == JCH_OK && sflags && hout) {
-        hsf.resize((size_t)m);
-        ef = hipMemcpyAsync(hsf.data(), sflags, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);   // on the failure paths too: the caller's host arrays must outlive every copy queued on them
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, ef);
-    JCH_HIP(ctx, es);
+    }));
     if (!hsf.empty()) {
         long long redone = 0;
         for (int64_t i = 0; i < m; ++i) redone += hsf[(size_t)i] ? 1 : 0;
@@ -362,29 +351,23 @@ extern "C" int32_t jch_knn_wmean(jch_ctx *ctx, int32_t loc, const double *Y, int
     const size_t o_y = host ? cv.take((size_t)n * q) : 0, o_i = host ? cv.take(ints_as_doubles(mk)) : 0, o_w = host ? cv.take(mk) : 0, o_p = host ? cv.take((size_t)m * q) : 0;
     if (host) JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kn_ws.ptr;
-    auto run = [&]() -> int32_t {
+    return jch_synced(ctx, host, [&]() -> int32_t {
         const double *dY = Y, *dw = w;
         const int *di = ind;
         double *dp = pred;
         int64_t ldyd = ldy;
+        JCH_TRY(jch_stage_in(ctx, host, ws + o_y, n, q, &dY, &ldyd));
         if (host) {
-            JCH_TRY(jch_copy2d(ctx, ws + o_y, n, Y, ldy, n, q, hipMemcpyHostToDevice));
             JCH_HIP(ctx, hipMemcpyAsync(ws + o_i, ind, sizeof(int) * mk, hipMemcpyHostToDevice, ctx->stream));
             JCH_HIP(ctx, hipMemcpyAsync(ws + o_w, w, sizeof(double) * mk, hipMemcpyHostToDevice, ctx->stream));
-            dY = ws + o_y; ldyd = n; di = (const int *)(ws + o_i); dw = ws + o_w; dp = ws + o_p;
+            di = (const int *)(ws + o_i); dw = ws + o_w; dp = ws + o_p;
         }
         const unsigned nb = (unsigned)std::min<int64_t>((m + 3) / 4, (int64_t)ctx->cus * 8);
         hipLaunchKernelGGL(k_knn_wmean, dim3(nb), dim3(256), 0, ctx->stream, dY, n, (int)q, ldyd, di, dw, (int)m, (int)k, dp);
         JCH_HIP(ctx, hipGetLastError());
         if (host) JCH_HIP(ctx, hipMemcpyAsync(pred, dp, sizeof(double) * (size_t)m * q, hipMemcpyDeviceToHost, ctx->stream));
         return JCH_OK;
-    };
-    const int32_t st = run();
-    if (!host) return st;
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
-    return JCH_OK;
+    });
 }
 
 extern "C" int32_t jch_knn_vote(jch_ctx *ctx, int32_t loc, const int32_t *cls, int64_t n, int32_t ncls, const int32_t *ind, const double *w, int64_t m,
@@ -404,7 +387,7 @@ extern "C" int32_t jch_knn_vote(jch_ctx *ctx, int32_t loc, const int32_t *cls, i
     const size_t o_ga = glob ? cv.take((size_t)nb * ncls) : 0, o_gc = glob ? cv.take(ints_as_doubles((size_t)nb * ncls)) : 0;
     if (cv.off) JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kn_ws.ptr;
-    auto run = [&]() -> int32_t {
+    return jch_synced(ctx, host, [&]() -> int32_t {
         const int *dc = cls, *di = ind;
         const double *dw = w;
         int *dp = pred;
@@ -423,13 +406,7 @@ extern "C" int32_t jch_knn_vote(jch_ctx *ctx, int32_t loc, const int32_t *cls, i
             if (score) JCH_HIP(ctx, hipMemcpyAsync(score, ds, sizeof(double) * (size_t)m * ncls, hipMemcpyDeviceToHost, ctx->stream));
         }
         return JCH_OK;
-    };
-    const int32_t st = run();
-    if (!host) return st;
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
-    return JCH_OK;
+    });
 }
 
 extern "C" int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double *v, int64_t n, const int32_t *ind, int64_t m, int32_t k, double *out)
@@ -447,7 +424,7 @@ extern "C" int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double
     const size_t o_gk = glob ? cv.take((size_t)nb * cap) : 0, o_gi = glob ? cv.take(ints_as_doubles((size_t)nb * cap)) : 0;
     if (cv.off) JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kn_ws.ptr;
-    auto run = [&]() -> int32_t {
+    return jch_synced(ctx, host, [&]() -> int32_t {
         const double *dv = v;
         const int *di = ind;
         double *dout = out;
@@ -461,11 +438,5 @@ extern "C" int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double
         JCH_HIP(ctx, hipGetLastError());
         if (host) JCH_HIP(ctx, hipMemcpyAsync(out, dout, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         return JCH_OK;
-    };
-    const int32_t st = run();
-    if (!host) return st;
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
-    return JCH_OK;
+    });
 }

@@ -599,62 +599,64 @@ extern "C" int32_t jch_kpca_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double 
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const bool host = loc == JCH_LOC_HOST;
     const size_t nn = (size_t)n;
-    // ---- device views of X and the raw weights
-    double *dX = X;
-    int64_t ldxd = ldx;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * nn * p));
-        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
-        dX = (double *)ctx->dk_x.ptr; ldxd = n;
-    }
-    // ---- the fit's own vectors (the eigensolver's panels live in ctx->pc_ws)
-    jch_carve cv;
-    const size_t ow = cv.take(nn), osw = cv.take(nn), ovt = cv.take(nn), owr = cv.take(nn), ohdr = cv.take(8), os = cv.take(8), oxs = cv.take((size_t)p),
-                 otr = cv.take(8);
-    JCH_TRY(jch_reserve(ctx, ctx->pc_vec, sizeof(double) * cv.off));
-    double *ws = (double *)ctx->pc_vec.ptr;
-    double *wn = ws + ow, *sw = ws + osw, *vt = ws + ovt, *wraw = ws + owr, *hdr = ws + ohdr, *sdev = ws + os, *xs_dev = ws + oxs, *trd = ws + otr;
-    const double *dw = weights;
-    if (host && weights) {
-        JCH_HIP(ctx, hipMemcpyAsync(wraw, weights, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
-        dw = wraw;
-    }
-    JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/kpca.jl:93)
-    JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
-    // ---- scal: xscales = colstd(X, w), X divided by them in place (:94-98)
     std::vector<double> xs((size_t)p, 1.0), xm((size_t)p);
-    if (scal) {
-        JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, xm.data(), xs.data()));
-        JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
-        JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));
-        if (host) JCH_TRY(jch_copy2d(ctx, X, ldx, dX, n, n, p, hipMemcpyDeviceToHost));
-    }
-    // ---- K = kern(X, X), vtot = K w, Kc = K - vtot' - vtot + w'vtot (:99-103)
-    JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * nn * nn));
-    double *Kc = (double *)ctx->dk_k.ptr;
-    JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, nullptr, p, wn, K_out ? K_out : Kc, Kc, vt, sdev));
-    // ---- the nlv leading eigenpairs of Kd = sqrtD Kc sqrtD
     jch_eig_lead_out eg;
-    JCH_TRY(jch_eig_lead(ctx, Kc, n, n, sw, A, tol, maxit, &eg));
+    double trh = NAN;
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        // ---- device views of X and the raw weights
+        double *dX = X;
+        int64_t ldxd = ldx;
+        if (host) {
+            JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * nn * p));
+            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
+            dX = (double *)ctx->dk_x.ptr; ldxd = n;
+        }
+        // ---- the fit's own vectors (the eigensolver's panels live in ctx->pc_ws)
+        jch_carve cv;
+        const size_t ow = cv.take(nn), osw = cv.take(nn), ovt = cv.take(nn), owr = cv.take(nn), ohdr = cv.take(8), os = cv.take(8), oxs = cv.take((size_t)p),
+                     otr = cv.take(8);
+        JCH_TRY(jch_reserve(ctx, ctx->pc_vec, sizeof(double) * cv.off));
+        double *ws = (double *)ctx->pc_vec.ptr;
+        double *wn = ws + ow, *sw = ws + osw, *vt = ws + ovt, *wraw = ws + owr, *hdr = ws + ohdr, *sdev = ws + os, *xs_dev = ws + oxs, *trd = ws + otr;
+        const double *dw = weights;
+        if (host && weights) {
+            JCH_HIP(ctx, hipMemcpyAsync(wraw, weights, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
+            dw = wraw;
+        }
+        JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/kpca.jl:93)
+        JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
+        // ---- scal: xscales = colstd(X, w), X divided by them in place (:94-98)
+        if (scal) {
+            JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, xm.data(), xs.data()));
+            JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
+            JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));
+            if (host) JCH_TRY(jch_copy2d(ctx, X, ldx, dX, n, n, p, hipMemcpyDeviceToHost));
+        }
+        // ---- K = kern(X, X), vtot = K w, Kc = K - vtot' - vtot + w'vtot (:99-103)
+        JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * nn * nn));
+        double *Kc = (double *)ctx->dk_k.ptr;
+        JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, nullptr, p, wn, K_out ? K_out : Kc, Kc, vt, sdev));
+        // ---- the nlv leading eigenpairs of Kd = sqrtD Kc sqrtD
+        JCH_TRY(jch_eig_lead(ctx, Kc, n, n, sw, A, tol, maxit, &eg));
+        // ---- outputs (:104-114): U = sign-fixed Ritz vectors, P = sqrtD U / sv, T = Kc P; eig = |theta|, sv = sqrt(eig)
+        double *Pd = eg.scratch, *WSd = eg.AX;
+        hipLaunchKernelGGL(k_pc_out, dim3(jch_grid1(ctx, n * A)), dim3(PC_NT), 0, ctx->stream, eg.X, WSd, n, A, eg.theta_dev, sw, Pd, WSd);
+        JCH_HIP(ctx, hipGetLastError());
+        const bool psd = psd_kernel(kind, gamma, coef0, degree);
+        if (psd) {
+            hipLaunchKernelGGL(k_pc_trace, dim3(1), dim3(PC_NT), 0, ctx->stream, Kc, n, wn, trd);
+            JCH_HIP(ctx, hipGetLastError());
+        }
+        const hipMemcpyKind dir = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (T) JCH_HIP(ctx, hipMemcpyAsync(T, WSd, sizeof(double) * nn * A, dir, ctx->stream));
+        if (P) JCH_HIP(ctx, hipMemcpyAsync(P, Pd, sizeof(double) * nn * A, dir, ctx->stream));
+        if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, dir, ctx->stream));
+        if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, dir, ctx->stream));
+        if (psd) JCH_HIP(ctx, hipMemcpyAsync(&trh, trd, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        return JCH_OK;
+    }));
     const std::vector<double> &th = eg.theta, &res = eg.resid;
     const int it = eg.niter;
-    // ---- outputs (:104-114): U = sign-fixed Ritz vectors, P = sqrtD U / sv, T = Kc P; eig = |theta|, sv = sqrt(eig)
-    double *Pd = eg.scratch, *WSd = eg.AX;
-    hipLaunchKernelGGL(k_pc_out, dim3(jch_grid1(ctx, n * A)), dim3(PC_NT), 0, ctx->stream, eg.X, WSd, n, A, eg.theta_dev, sw, Pd, WSd);
-    JCH_HIP(ctx, hipGetLastError());
-    const bool psd = psd_kernel(kind, gamma, coef0, degree);
-    if (psd) {
-        hipLaunchKernelGGL(k_pc_trace, dim3(1), dim3(PC_NT), 0, ctx->stream, Kc, n, wn, trd);
-        JCH_HIP(ctx, hipGetLastError());
-    }
-    const hipMemcpyKind dir = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (T) JCH_HIP(ctx, hipMemcpyAsync(T, WSd, sizeof(double) * nn * A, dir, ctx->stream));
-    if (P) JCH_HIP(ctx, hipMemcpyAsync(P, Pd, sizeof(double) * nn * A, dir, ctx->stream));
-    if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, dir, ctx->stream));
-    if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, dir, ctx->stream));
-    double trh = NAN;
-    if (psd) JCH_HIP(ctx, hipMemcpyAsync(&trh, trd, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int e = 0; e < A; ++e) {
         const double ev = fabs(th[e]);
         if (eig) eig[e] = ev;

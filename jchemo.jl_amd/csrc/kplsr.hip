@@ -440,109 +440,111 @@ extern "C" int32_t jch_kplsr_fit(jch_ctx *ctx, const jch_pls_desc *desc, int32_t
     if ((int64_t)A * n >= ((int64_t)1 << 31)) return jch_fail(ctx, JCH_EINVAL, "%s: n * nlv too large", who);
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const bool host = d.loc == JCH_LOC_HOST, inplace = d.inplace != 0, scal = d.scal != 0;
-    // ---- device views of X and the raw weights
-    double *dX = (double *)X;
-    int64_t ldxd = ldx;
-    const double *dw = weights;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
-        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, (const double *)X, ldx, n, p, hipMemcpyHostToDevice));
-        dX = (double *)ctx->dk_x.ptr; ldxd = n;
-    }
-    // ---- workspace (doubles, ld n): Ya | Wb (adjacent: one reduction gives Y_a'DM and M'DM) | Vb | T | U | DU, then the vectors and
-    // the small state
-    const int pc = kp_padcols(std::max<int>((int)q, A));
-    const int ldp = (int)std::max<int64_t>({(int64_t)A * q, 2 * q * q, (int64_t)A + 1});
-    const size_t nn = (size_t)n;
-    jch_carve cv;
-    const size_t oY = cv.take(nn * (q + pc)), oV = cv.take(nn * pc), oT = cv.take(nn * A), oU = cv.take(nn * A), oDU = cv.take(nn * A);
-    const size_t ow = cv.take(nn), ovt = cv.take(nn), ohdr = cv.take(8), os = cv.take(8), oms = cv.take(2 * q + (size_t)p), oS = cv.take((size_t)A * A),
-                 ocoef = cv.take((size_t)A * q), ost = cv.take(3 * (size_t)q + 1), omat = cv.take(3 * (size_t)q * q), oC = cv.take((size_t)A * q),
-                 oit = cv.take(A), op1 = cv.take((size_t)KP_RED_NB * ldp), op2 = cv.take((size_t)KP_RED_NB * ldp), op3 = cv.take((size_t)KP_RED_NB * ldp),
-                 op4 = cv.take((size_t)KP_RED_NB * ldp), op5 = cv.take((size_t)KP_RED_NB * ldp);
-    JCH_TRY(jch_reserve(ctx, ctx->kp_ws, sizeof(double) * cv.off));
-    double *ws = (double *)ctx->kp_ws.ptr;
-    double *Ya = ws + oY, *Wb = ws + oY + nn * q, *Vb = ws + oV, *Td = ws + oT, *Ud = ws + oU, *DU = ws + oDU, *wn = ws + ow, *vt = ws + ovt,
-           *hdr = ws + ohdr, *sdev = ws + os, *ms = ws + oms, *Sd = ws + oS, *coef = ws + ocoef, *st = ws + ost, *mat = ws + omat,
-           *Cd = ws + oC, *itd = ws + oit, *part1 = ws + op1, *part2 = ws + op2, *part3 = ws + op3, *part4 = ws + op4, *part5 = ws + op5;
-    if (host && weights) {
-        JCH_HIP(ctx, hipMemcpyAsync(Vb, weights, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));   // (Vb: free until the LV loop)
-        dw = Vb;
-    }
-    JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/kplsr.jl:124)
-    // ---- Y: ymeans = colmean(Y, w); with scal, xscales = colstd(X, w), yscales = colstd(Y, w) (:125-135)
-    if (host) JCH_TRY(jch_copy2d(ctx, Ya, n, (const double *)Y, ldy, n, q, hipMemcpyHostToDevice));
-    const double *ysrc = host ? Ya : (const double *)Y;
-    const int64_t ldys = host ? n : ldy;
     std::vector<double> xs((size_t)p, 1.0), ym((size_t)q), ys((size_t)q, 1.0), xm((size_t)p);
-    JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, ysrc, n, q, ldys, dw, ym.data(), scal ? ys.data() : nullptr));
-    if (scal) JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, xm.data(), xs.data()));
-    double *ym_dev = ms, *ys_dev = ms + q, *xs_dev = ms + 2 * q;
-    JCH_HIP(ctx, hipMemcpyAsync(ym_dev, ym.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
-    JCH_HIP(ctx, hipMemcpyAsync(ys_dev, ys.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
-    JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_kp_cscale, dim3(jch_grid1(ctx, n * q)), dim3(KP_NT), 0, ctx->stream, ysrc, ldys, Ya, n, n, q, ym_dev, ys_dev);
-    JCH_HIP(ctx, hipGetLastError());
-    if (scal && inplace) {   // kplsr! hands X back divided by xscales (`scale!`, :131); otherwise the Gram divides on the fly
-        hipLaunchKernelGGL(k_kp_cscale, dim3(jch_grid1(ctx, n * p)), dim3(KP_NT), 0, ctx->stream, dX, ldxd, dX, ldxd, n, p, nullptr, xs_dev);
-        JCH_HIP(ctx, hipGetLastError());
-    }
-    // ---- K = kern(X, X) (:137), symmetric path; Kc = K - vtot 1' - 1 vtot' + w'Kw (:138-142) formed in the workspace Gram
-    JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * nn * nn));
-    double *Kc = (double *)ctx->dk_k.ptr;
-    double *Kraw = K_out ? K_out : Kc;
-    const double *gdiv = scal && !inplace ? xs.data() : nullptr;
-    JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, gdiv, p, wn, Kraw, Kc, vt, sdev));
-    // ---- LV loop (:157-188): one pass over Kc per LV
-    const int nbr = (int)std::max<int64_t>(1, std::min<int64_t>(KP_RED_NB, (n + 255) / 256));
-    for (int a = 0; a < A; ++a) {
-        if (a > 0) {
-            JCH_TRY(launch_red(ctx, Td, n, a, Ya, n, (int)q, wn, n, nbr, part1, ldp));     // b = T'(D Y_a)
-            kp_small_args g{part5, part1, Sd, coef, a, (int)q, A, nbr, ldp, ldp};
-            hipLaunchKernelGGL(k_kp_proj, dim3(1), dim3(KP_NT), 0, ctx->stream, g, false);
-            JCH_HIP(ctx, hipGetLastError());
-        }
-        JCH_TRY(launch_apply(ctx, Vb, n, Ya, n, Td, n, a, coef, wn, n, (int)q));        // V = D (Y_a - T alpha) = Z_a' D Y_a
-        JCH_TRY(launch_pass(ctx, Kc, n, Vb, n, (int)q, Wb, n));                          // W = Kc V
-        if (a > 0) {
-            JCH_TRY(launch_red(ctx, Td, n, a, Wb, n, (int)q, wn, n, nbr, part2, ldp));     // c = T'(D W)
-            kp_small_args g{part5, part2, Sd, coef, a, (int)q, A, nbr, ldp, ldp};
-            hipLaunchKernelGGL(k_kp_proj, dim3(1), dim3(KP_NT), 0, ctx->stream, g, true);
-            JCH_HIP(ctx, hipGetLastError());
-            JCH_TRY(launch_apply(ctx, Wb, n, Wb, n, Td, n, a, coef, nullptr, n, (int)q)); // M = W - T beta = Z_a W
-        }
-        JCH_TRY(launch_red(ctx, Ya, n, 2 * (int)q, Wb, n, (int)q, wn, n, nbr, part3, ldp)); // [Y_a | M]' D M
-        JCH_TRY(launch_red(ctx, Ya, n, (int)q, Ya, n, (int)q, nullptr, n, nbr, part4, ldp)); // Y_a'Y_a
-        kp_iter_args gi{part3, part4, mat, st, Cd, itd, a, (int)q, nbr, ldp, ldp, maxit, tol};
-        hipLaunchKernelGGL(k_kp_iter, dim3(1), dim3(KP_NT), 0, ctx->stream, gi);
-        JCH_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_kp_rows, dim3(jch_grid1(ctx, n)), dim3(KP_NT), 0, ctx->stream, Wb, Ya, n, (int)q, st, Td + nn * a, Ud + nn * a);
-        JCH_HIP(ctx, hipGetLastError());
-        if (a + 1 < A) JCH_TRY(launch_red(ctx, Td, n, a + 1, Td + nn * a, n, 1, wn, n, nbr, part5, ldp));   // S row a = t_a' D T
-    }
-    // ---- R = DU inv(T' D Kc DU) (:189-190): P = Kc (D T) in one pass, then plsnipals' M = P'W, Gauss-Jordan, R = W Mi with W = DU
-    JCH_TRY(launch_apply(ctx, Vb, n, Td, n, nullptr, n, 0, nullptr, wn, n, A));
-    JCH_TRY(launch_apply(ctx, DU, n, Ud, n, nullptr, n, 0, nullptr, wn, n, A));
-    JCH_TRY(launch_pass(ctx, Kc, n, Vb, n, A, Wb, n));
-    double *Rd = Vb;   // (D T is consumed by the pass)
-    jch_small sm{};
-    sm.P = Wb; sm.W = DU; sm.R = Rd;
-    JCH_TRY(jch_launch_nipals_R(ctx, sm, (int)n, A));
-    // ---- outputs
-    const hipMemcpyKind dir = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (T) JCH_TRY(jch_copy2d(ctx, T, n, Td, n, n, A, dir));
-    if (U) JCH_TRY(jch_copy2d(ctx, U, n, Ud, n, n, A, dir));
-    if (R) JCH_TRY(jch_copy2d(ctx, R, n, Rd, n, n, A, dir));
-    if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, dir, ctx->stream));
-    if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, dir, ctx->stream));
-    if (inplace) {   // kplsr! hands X (scaled; already in place on the device) and Y (centred, scaled) back
-        if (host) JCH_TRY(jch_copy2d(ctx, (double *)X, ldx, dX, ldxd, n, p, dir));
-        JCH_TRY(jch_copy2d(ctx, (double *)Y, ldy, Ya, n, n, q, dir));
-    }
     std::vector<double> Ch((size_t)A * q), ith((size_t)A);
-    JCH_HIP(ctx, hipMemcpyAsync(Ch.data(), Cd, sizeof(double) * Ch.size(), hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipMemcpyAsync(ith.data(), itd, sizeof(double) * ith.size(), hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        // ---- device views of X and the raw weights
+        double *dX = (double *)X;
+        int64_t ldxd = ldx;
+        const double *dw = weights;
+        if (host) {
+            JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * (size_t)n * p));
+            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, (const double *)X, ldx, n, p, hipMemcpyHostToDevice));
+            dX = (double *)ctx->dk_x.ptr; ldxd = n;
+        }
+        // ---- workspace (doubles, ld n): Ya | Wb (adjacent: one reduction gives Y_a'DM and M'DM) | Vb | T | U | DU, then the vectors and
+        // the small state
+        const int pc = kp_padcols(std::max<int>((int)q, A));
+        const int ldp = (int)std::max<int64_t>({(int64_t)A * q, 2 * q * q, (int64_t)A + 1});
+        const size_t nn = (size_t)n;
+        jch_carve cv;
+        const size_t oY = cv.take(nn * (q + pc)), oV = cv.take(nn * pc), oT = cv.take(nn * A), oU = cv.take(nn * A), oDU = cv.take(nn * A);
+        const size_t ow = cv.take(nn), ovt = cv.take(nn), ohdr = cv.take(8), os = cv.take(8), oms = cv.take(2 * q + (size_t)p), oS = cv.take((size_t)A * A),
+                     ocoef = cv.take((size_t)A * q), ost = cv.take(3 * (size_t)q + 1), omat = cv.take(3 * (size_t)q * q), oC = cv.take((size_t)A * q),
+                     oit = cv.take(A), op1 = cv.take((size_t)KP_RED_NB * ldp), op2 = cv.take((size_t)KP_RED_NB * ldp), op3 = cv.take((size_t)KP_RED_NB * ldp),
+                     op4 = cv.take((size_t)KP_RED_NB * ldp), op5 = cv.take((size_t)KP_RED_NB * ldp);
+        JCH_TRY(jch_reserve(ctx, ctx->kp_ws, sizeof(double) * cv.off));
+        double *ws = (double *)ctx->kp_ws.ptr;
+        double *Ya = ws + oY, *Wb = ws + oY + nn * q, *Vb = ws + oV, *Td = ws + oT, *Ud = ws + oU, *DU = ws + oDU, *wn = ws + ow, *vt = ws + ovt,
+               *hdr = ws + ohdr, *sdev = ws + os, *ms = ws + oms, *Sd = ws + oS, *coef = ws + ocoef, *st = ws + ost, *mat = ws + omat,
+               *Cd = ws + oC, *itd = ws + oit, *part1 = ws + op1, *part2 = ws + op2, *part3 = ws + op3, *part4 = ws + op4, *part5 = ws + op5;
+        if (host && weights) {
+            JCH_HIP(ctx, hipMemcpyAsync(Vb, weights, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));   // (Vb: free until the LV loop)
+            dw = Vb;
+        }
+        JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/kplsr.jl:124)
+        // ---- Y: ymeans = colmean(Y, w); with scal, xscales = colstd(X, w), yscales = colstd(Y, w) (:125-135)
+        if (host) JCH_TRY(jch_copy2d(ctx, Ya, n, (const double *)Y, ldy, n, q, hipMemcpyHostToDevice));
+        const double *ysrc = host ? Ya : (const double *)Y;
+        const int64_t ldys = host ? n : ldy;
+        JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, ysrc, n, q, ldys, dw, ym.data(), scal ? ys.data() : nullptr));
+        if (scal) JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, xm.data(), xs.data()));
+        double *ym_dev = ms, *ys_dev = ms + q, *xs_dev = ms + 2 * q;
+        JCH_HIP(ctx, hipMemcpyAsync(ym_dev, ym.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(ys_dev, ys.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_kp_cscale, dim3(jch_grid1(ctx, n * q)), dim3(KP_NT), 0, ctx->stream, ysrc, ldys, Ya, n, n, q, ym_dev, ys_dev);
+        JCH_HIP(ctx, hipGetLastError());
+        if (scal && inplace) {   // kplsr! hands X back divided by xscales (`scale!`, :131); otherwise the Gram divides on the fly
+            hipLaunchKernelGGL(k_kp_cscale, dim3(jch_grid1(ctx, n * p)), dim3(KP_NT), 0, ctx->stream, dX, ldxd, dX, ldxd, n, p, nullptr, xs_dev);
+            JCH_HIP(ctx, hipGetLastError());
+        }
+        // ---- K = kern(X, X) (:137), symmetric path; Kc = K - vtot 1' - 1 vtot' + w'Kw (:138-142) formed in the workspace Gram
+        JCH_TRY(jch_reserve(ctx, ctx->dk_k, sizeof(double) * nn * nn));
+        double *Kc = (double *)ctx->dk_k.ptr;
+        double *Kraw = K_out ? K_out : Kc;
+        const double *gdiv = scal && !inplace ? xs.data() : nullptr;
+        JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, gdiv, p, wn, Kraw, Kc, vt, sdev));
+        // ---- LV loop (:157-188): one pass over Kc per LV
+        const int nbr = (int)std::max<int64_t>(1, std::min<int64_t>(KP_RED_NB, (n + 255) / 256));
+        for (int a = 0; a < A; ++a) {
+            if (a > 0) {
+                JCH_TRY(launch_red(ctx, Td, n, a, Ya, n, (int)q, wn, n, nbr, part1, ldp));     // b = T'(D Y_a)
+                kp_small_args g{part5, part1, Sd, coef, a, (int)q, A, nbr, ldp, ldp};
+                hipLaunchKernelGGL(k_kp_proj, dim3(1), dim3(KP_NT), 0, ctx->stream, g, false);
+                JCH_HIP(ctx, hipGetLastError());
+            }
+            JCH_TRY(launch_apply(ctx, Vb, n, Ya, n, Td, n, a, coef, wn, n, (int)q));        // V = D (Y_a - T alpha) = Z_a' D Y_a
+            JCH_TRY(launch_pass(ctx, Kc, n, Vb, n, (int)q, Wb, n));                          // W = Kc V
+            if (a > 0) {
+                JCH_TRY(launch_red(ctx, Td, n, a, Wb, n, (int)q, wn, n, nbr, part2, ldp));     // c = T'(D W)
+                kp_small_args g{part5, part2, Sd, coef, a, (int)q, A, nbr, ldp, ldp};
+                hipLaunchKernelGGL(k_kp_proj, dim3(1), dim3(KP_NT), 0, ctx->stream, g, true);
+                JCH_HIP(ctx, hipGetLastError());
+                JCH_TRY(launch_apply(ctx, Wb, n, Wb, n, Td, n, a, coef, nullptr, n, (int)q)); // M = W - T beta = Z_a W
+            }
+            JCH_TRY(launch_red(ctx, Ya, n, 2 * (int)q, Wb, n, (int)q, wn, n, nbr, part3, ldp)); // [Y_a | M]' D M
+            JCH_TRY(launch_red(ctx, Ya, n, (int)q, Ya, n, (int)q, nullptr, n, nbr, part4, ldp)); // Y_a'Y_a
+            kp_iter_args gi{part3, part4, mat, st, Cd, itd, a, (int)q, nbr, ldp, ldp, maxit, tol};
+            hipLaunchKernelGGL(k_kp_iter, dim3(1), dim3(KP_NT), 0, ctx->stream, gi);
+            JCH_HIP(ctx, hipGetLastError());
+            hipLaunchKernelGGL(k_kp_rows, dim3(jch_grid1(ctx, n)), dim3(KP_NT), 0, ctx->stream, Wb, Ya, n, (int)q, st, Td + nn * a, Ud + nn * a);
+            JCH_HIP(ctx, hipGetLastError());
+            if (a + 1 < A) JCH_TRY(launch_red(ctx, Td, n, a + 1, Td + nn * a, n, 1, wn, n, nbr, part5, ldp));   // S row a = t_a' D T
+        }
+        // ---- R = DU inv(T' D Kc DU) (:189-190): P = Kc (D T) in one pass, then plsnipals' M = P'W, Gauss-Jordan, R = W Mi with W = DU
+        JCH_TRY(launch_apply(ctx, Vb, n, Td, n, nullptr, n, 0, nullptr, wn, n, A));
+        JCH_TRY(launch_apply(ctx, DU, n, Ud, n, nullptr, n, 0, nullptr, wn, n, A));
+        JCH_TRY(launch_pass(ctx, Kc, n, Vb, n, A, Wb, n));
+        double *Rd = Vb;   // (D T is consumed by the pass)
+        jch_small sm{};
+        sm.P = Wb; sm.W = DU; sm.R = Rd;
+        JCH_TRY(jch_launch_nipals_R(ctx, sm, (int)n, A));
+        // ---- outputs
+        const hipMemcpyKind dir = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (T) JCH_TRY(jch_copy2d(ctx, T, n, Td, n, n, A, dir));
+        if (U) JCH_TRY(jch_copy2d(ctx, U, n, Ud, n, n, A, dir));
+        if (R) JCH_TRY(jch_copy2d(ctx, R, n, Rd, n, n, A, dir));
+        if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, dir, ctx->stream));
+        if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, dir, ctx->stream));
+        if (inplace) {   // kplsr! hands X (scaled; already in place on the device) and Y (centred, scaled) back
+            if (host) JCH_TRY(jch_copy2d(ctx, (double *)X, ldx, dX, ldxd, n, p, dir));
+            JCH_TRY(jch_copy2d(ctx, (double *)Y, ldy, Ya, n, n, q, dir));
+        }
+        JCH_HIP(ctx, hipMemcpyAsync(Ch.data(), Cd, sizeof(double) * Ch.size(), hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(ith.data(), itd, sizeof(double) * ith.size(), hipMemcpyDeviceToHost, ctx->stream));
+        return JCH_OK;
+    }));
     if (C) std::copy(Ch.begin(), Ch.end(), C);
     if (iter)
         for (int a = 0; a < A; ++a) iter[a] = (int32_t)ith[a];

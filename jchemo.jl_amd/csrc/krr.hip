@@ -47,55 +47,54 @@ extern "C" int32_t jch_krr_fit(jch_ctx *ctx, int32_t loc, int32_t kind, double g
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const bool host = loc == JCH_LOC_HOST;
     const size_t nn = (size_t)n;
-    // ---- device views of X, Y and the raw weights
-    double *dX = X;
-    int64_t ldxd = ldx;
-    if (host) {
-        JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * nn * p));
-        JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
-        dX = (double *)ctx->dk_x.ptr; ldxd = n;
-    }
-    jch_carve cv;
-    const size_t oY = cv.take(nn * q), oB = cv.take(nn * q), owr = cv.take(nn), ow = cv.take(nn), osw = cv.take(nn), ovt = cv.take(nn), ohdr = cv.take(8), os = cv.take(8),
-                 oxs = cv.take((size_t)p);
-    JCH_TRY(jch_reserve(ctx, ctx->kr_ws, sizeof(double) * cv.off));
-    double *ws = (double *)ctx->kr_ws.ptr;
-    double *Yd = ws + oY, *Bd = ws + oB, *wraw = ws + owr, *wn = ws + ow, *sw = ws + osw, *vt = ws + ovt, *hdr = ws + ohdr, *sdev = ws + os,
-           *xs_dev = ws + oxs;
-    const double *dY = Y;
-    int64_t ldyd = ldy;
-    if (host) {
-        JCH_TRY(jch_copy2d(ctx, Yd, n, Y, ldy, n, q, hipMemcpyHostToDevice));
-        dY = Yd; ldyd = n;
-    }
-    const double *dw = weights;
-    if (host && weights) {
-        JCH_HIP(ctx, hipMemcpyAsync(wraw, weights, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
-        dw = wraw;
-    }
-    JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/krr.jl:135)
-    JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
-    // ---- scal: xscales = colstd(X, w), X divided by them in place (:136-140; X is not centred); ymeans = colmean(Y, w) (:141)
     std::vector<double> xs((size_t)p, 1.0), xm((size_t)p), ym((size_t)q);
-    if (scal) {
-        JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, xm.data(), xs.data()));
-        JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
-        JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));
-        if (host) JCH_TRY(jch_copy2d(ctx, X, ldx, dX, n, n, p, hipMemcpyDeviceToHost));
-    }
-    JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dY, n, q, ldyd, dw, ym.data(), nullptr));
-    // ---- K = kern(X, X), vtot = K w, Kc = K - vtot' - vtot + w'vtot (:143-147) in the caller's buffer, then Kd = sqrtD Kc sqrtD (:150-151)
-    JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, nullptr, p, wn, K_out ? K_out : Kd, Kd, vt, sdev));
-    hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * n)), dim3(KR_NT), 0, ctx->stream, Kd, n, Kd, n, n, n, sw, sw);
-    JCH_HIP(ctx, hipGetLastError());
-    // ---- B = sqrtD Y (Y raw, as `U' * sqrtD * Y` :156)
-    hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * q)), dim3(KR_NT), 0, ctx->stream, dY, ldyd, Bd, n, n, q, sw, nullptr);
-    JCH_HIP(ctx, hipGetLastError());
-    const hipMemcpyKind dir = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (B) JCH_HIP(ctx, hipMemcpyAsync(B, Bd, sizeof(double) * nn * q, dir, ctx->stream));
-    if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, dir, ctx->stream));
-    if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, dir, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        // ---- device views of X, Y and the raw weights
+        double *dX = X;
+        int64_t ldxd = ldx;
+        if (host) {
+            JCH_TRY(jch_reserve(ctx, ctx->dk_x, sizeof(double) * nn * p));
+            JCH_TRY(jch_copy2d(ctx, (double *)ctx->dk_x.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
+            dX = (double *)ctx->dk_x.ptr; ldxd = n;
+        }
+        jch_carve cv;
+        const size_t oY = cv.take(nn * q), oB = cv.take(nn * q), owr = cv.take(nn), ow = cv.take(nn), osw = cv.take(nn), ovt = cv.take(nn), ohdr = cv.take(8), os = cv.take(8),
+                     oxs = cv.take((size_t)p);
+        JCH_TRY(jch_reserve(ctx, ctx->kr_ws, sizeof(double) * cv.off));
+        double *ws = (double *)ctx->kr_ws.ptr;
+        double *Yd = ws + oY, *Bd = ws + oB, *wraw = ws + owr, *wn = ws + ow, *sw = ws + osw, *vt = ws + ovt, *hdr = ws + ohdr, *sdev = ws + os,
+               *xs_dev = ws + oxs;
+        const double *dY = Y;
+        int64_t ldyd = ldy;
+        JCH_TRY(jch_stage_in(ctx, host, Yd, n, q, &dY, &ldyd));
+        const double *dw = weights;
+        if (host && weights) {
+            JCH_HIP(ctx, hipMemcpyAsync(wraw, weights, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
+            dw = wraw;
+        }
+        JCH_TRY(jch_launch_weights(ctx, dw, n, wn, hdr));   // `mweight` (src/krr.jl:135)
+        JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
+        // ---- scal: xscales = colstd(X, w), X divided by them in place (:136-140; X is not centred); ymeans = colmean(Y, w) (:141)
+        if (scal) {
+            JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dX, n, p, ldxd, dw, xm.data(), xs.data()));
+            JCH_HIP(ctx, hipMemcpyAsync(xs_dev, xs.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
+            JCH_TRY(jch_launch_divcols(ctx, dX, ldxd, n, p, xs_dev));
+            if (host) JCH_TRY(jch_copy2d(ctx, X, ldx, dX, n, n, p, hipMemcpyDeviceToHost));
+        }
+        JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dY, n, q, ldyd, dw, ym.data(), nullptr));
+        // ---- K = kern(X, X), vtot = K w, Kc = K - vtot' - vtot + w'vtot (:143-147) in the caller's buffer, then Kd = sqrtD Kc sqrtD (:150-151)
+        JCH_TRY(jch_launch_kp_centred_gram(ctx, kind, gamma, coef0, degree, dX, n, ldxd, nullptr, p, wn, K_out ? K_out : Kd, Kd, vt, sdev));
+        hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * n)), dim3(KR_NT), 0, ctx->stream, Kd, n, Kd, n, n, n, sw, sw);
+        JCH_HIP(ctx, hipGetLastError());
+        // ---- B = sqrtD Y (Y raw, as `U' * sqrtD * Y` :156)
+        hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * q)), dim3(KR_NT), 0, ctx->stream, dY, ldyd, Bd, n, n, q, sw, nullptr);
+        JCH_HIP(ctx, hipGetLastError());
+        const hipMemcpyKind dir = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (B) JCH_HIP(ctx, hipMemcpyAsync(B, Bd, sizeof(double) * nn * q, dir, ctx->stream));
+        if (vtot) JCH_HIP(ctx, hipMemcpyAsync(vtot, vt, sizeof(double) * nn, dir, ctx->stream));
+        if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, dir, ctx->stream));
+        return JCH_OK;
+    }));
     if (xscales) std::copy(xs.begin(), xs.end(), xscales);
     if (ymeans) std::copy(ym.begin(), ym.end(), ymeans);
     return JCH_OK;
@@ -124,34 +123,36 @@ extern "C" int32_t jch_krr_solve(jch_ctx *ctx, int32_t loc, const double *Kd, in
     double *Ad = ws + oA, *ald = ws + oal, *wn = ws + ow, *sw = ws + osw, *fro = ws + odf, *M = (double *)ctx->chol_a.ptr;
     int *idev = nullptr;
     JCH_TRY(jch_chol_info_word(ctx, &idev));
-    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    JCH_HIP(ctx, hipMemcpyAsync(Ad, B, sizeof(double) * nn * q, in, ctx->stream));
-    JCH_HIP(ctx, hipMemcpyAsync(wn, weights_norm, sizeof(double) * nn, in, ctx->stream));
-    JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
-    // ---- M = Kd + lb^2 I = L L'; A = M^-1 B (:170-172); alpha = sqrtD A (what predict multiplies with, :198)
-    JCH_HIP(ctx, hipMemcpyAsync(M, Kd, sizeof(double) * nn * nn, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_kr_adddiag, dim3((unsigned)((n + KR_NT - 1) / KR_NT)), dim3(KR_NT), 0, ctx->stream, M, n, lb * lb);
-    JCH_HIP(ctx, hipGetLastError());
-    JCH_TRY(jch_launch_chol_factor(ctx, M, n, n, idev));
-    JCH_TRY(jch_launch_chol_solve(ctx, M, n, n, Ad, q, n, idev));
-    hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * q)), dim3(KR_NT), 0, ctx->stream, Ad, n, ald, n, n, q, sw, nullptr);
-    JCH_HIP(ctx, hipGetLastError());
-    // ---- df = 1 + n - lb^2 trace(M^-1), trace(M^-1) = |L^-1|_F^2 (:175-176)
-    if (want_df) JCH_TRY(jch_launch_chol_inv_fro2(ctx, M, n, n, fro, idev));
     int hinfo = 0;
     double hfro = 0.0;
-    JCH_HIP(ctx, hipMemcpyAsync(&hinfo, idev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (want_df) JCH_HIP(ctx, hipMemcpyAsync(&hfro, fro, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (info) *info = hinfo;
-    if (hinfo != 0) {
-        ctx->chol_L = nullptr;
-        return jch_fail(ctx, JCH_EINVAL, "%s: Kd + lb^2 I is not positive definite (lb = %g): the pivot of column %d is not > 0; the kernel / its "
-                        "parameters are not PSD enough for this lb", who, lb, hinfo);
-    }
-    if (A) JCH_HIP(ctx, hipMemcpyAsync(A, Ad, sizeof(double) * nn * q, out, ctx->stream));
-    if (alpha) JCH_HIP(ctx, hipMemcpyAsync(alpha, ald, sizeof(double) * nn * q, out, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        JCH_HIP(ctx, hipMemcpyAsync(Ad, B, sizeof(double) * nn * q, in, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(wn, weights_norm, sizeof(double) * nn, in, ctx->stream));
+        JCH_TRY(jch_launch_sqrt(ctx, wn, n, sw));
+        // ---- M = Kd + lb^2 I = L L'; A = M^-1 B (:170-172); alpha = sqrtD A (what predict multiplies with, :198)
+        JCH_HIP(ctx, hipMemcpyAsync(M, Kd, sizeof(double) * nn * nn, hipMemcpyDeviceToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_kr_adddiag, dim3((unsigned)((n + KR_NT - 1) / KR_NT)), dim3(KR_NT), 0, ctx->stream, M, n, lb * lb);
+        JCH_HIP(ctx, hipGetLastError());
+        JCH_TRY(jch_launch_chol_factor(ctx, M, n, n, idev));
+        JCH_TRY(jch_launch_chol_solve(ctx, M, n, n, Ad, q, n, idev));
+        hipLaunchKernelGGL(k_kr_scale, dim3(jch_grid1(ctx, n * q)), dim3(KR_NT), 0, ctx->stream, Ad, n, ald, n, n, q, sw, nullptr);
+        JCH_HIP(ctx, hipGetLastError());
+        // ---- df = 1 + n - lb^2 trace(M^-1), trace(M^-1) = |L^-1|_F^2 (:175-176)
+        if (want_df) JCH_TRY(jch_launch_chol_inv_fro2(ctx, M, n, n, fro, idev));
+        JCH_HIP(ctx, hipMemcpyAsync(&hinfo, idev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        if (want_df) JCH_HIP(ctx, hipMemcpyAsync(&hfro, fro, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (info) *info = hinfo;
+        if (hinfo != 0) {
+            ctx->chol_L = nullptr;
+            return jch_fail(ctx, JCH_EINVAL, "%s: Kd + lb^2 I is not positive definite (lb = %g): the pivot of column %d is not > 0; the kernel / its "
+                            "parameters are not PSD enough for this lb", who, lb, hinfo);
+        }
+        if (A) JCH_HIP(ctx, hipMemcpyAsync(A, Ad, sizeof(double) * nn * q, out, ctx->stream));
+        if (alpha) JCH_HIP(ctx, hipMemcpyAsync(alpha, ald, sizeof(double) * nn * q, out, ctx->stream));
+        return JCH_OK;
+    }));
     if (want_df) *df = 1.0 + (double)n - lb * lb * hfro;
     return JCH_OK;
 }

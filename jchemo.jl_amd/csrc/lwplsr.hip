@@ -1041,32 +1041,31 @@ extern "C" int32_t jch_lwplsr_predict(jch_ctx *ctx, int32_t loc, const double *X
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "jch_lwplsr_predict: bad loc");
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const int ldr = ((int)p + 1) & ~1;
-    // ---- stage host inputs
-    const double *dX = Xtrain, *dY = Ytrain, *dZt = Ztrain, *dZq = Zq, *dXq = Xq;
-    int64_t ldxd = ldx, ldyd = ldy, ldztd = ldzt, ldzqd = ldzq, ldxqd = ldxq;
-    if (loc == JCH_LOC_HOST) {
-        const size_t need = sizeof(double) * ((size_t)n * p + (size_t)n * q + (size_t)n * dd + (size_t)m * dd + (size_t)m * p);
-        JCH_TRY(jch_reserve(ctx, ctx->xq, need));
-        double *b = (double *)ctx->xq.ptr;
-        auto up = [&](const double *src, int64_t rows, int64_t cols, int64_t ld, const double *&dst, int64_t &ldd) -> int32_t {
-            if (ld == rows) JCH_HIP(ctx, hipMemcpyAsync(b, src, sizeof(double) * (size_t)rows * cols, hipMemcpyHostToDevice, ctx->stream));
-            else JCH_HIP(ctx, hipMemcpy2DAsync(b, sizeof(double) * rows, src, sizeof(double) * ld, sizeof(double) * rows, cols, hipMemcpyHostToDevice, ctx->stream));
-            dst = b; ldd = rows; b += (size_t)rows * cols;
-            return JCH_OK;
-        };
-        JCH_TRY(up(Xtrain, n, p, ldx, dX, ldxd)); JCH_TRY(up(Ytrain, n, q, ldy, dY, ldyd)); JCH_TRY(up(Ztrain, n, dd, ldzt, dZt, ldztd));
-        JCH_TRY(up(Zq, m, dd, ldzq, dZq, ldzqd)); JCH_TRY(up(Xq, m, p, ldxq, dXq, ldxqd));
-    }
+    const bool host = loc == JCH_LOC_HOST;
+    if (host) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)n * p + (size_t)n * q + (size_t)n * dd + (size_t)m * dd + (size_t)m * p)));
     // ---- the model-constant piece, in the ctx workspace (rebuilt on every call: use jch_lwplsr_prepare to keep it)
     // (a buffer of its own: the per-query fits of the generic path use the fit workspace, ctx->xr included)
     JCH_TRY(jch_reserve(ctx, ctx->lw_xrm, sizeof(double) * (size_t)n * ldr));
-    double *Xrm = (double *)ctx->lw_xrm.ptr;
-    ctx->ev_used = 0;
-    ctx->prof = jch_profile{};
-    hipEvent_t ev0 = jch_ev(ctx);
-    jch_lw_to_rowmajor(ctx, dX, ldxd, n, (int)p, Xrm, ldr);
-    return lw_run(ctx, Xrm, ldr, n, p, dY, q, ldyd, dZt, ldztd, dZq, ldzqd, dd, dXq, m, ldxqd, k, h, tol, scal, nlv_lo, nlv_hi, pred,
-                  ind_out, dist_out, w_out, ev0, nullptr, nullptr);
+    return jch_synced_on_failure(ctx, true, [&]() -> int32_t {   // (lw_run ends synchronised)
+        // ---- stage host inputs
+        const double *dX = Xtrain, *dY = Ytrain, *dZt = Ztrain, *dZq = Zq, *dXq = Xq;
+        int64_t ldxd = ldx, ldyd = ldy, ldztd = ldzt, ldzqd = ldzq, ldxqd = ldxq;
+        if (host) {
+            double *b = (double *)ctx->xq.ptr;
+            JCH_TRY(jch_stage_in(ctx, host, b, n, p, &dX, &ldxd)); b += (size_t)n * p;
+            JCH_TRY(jch_stage_in(ctx, host, b, n, q, &dY, &ldyd)); b += (size_t)n * q;
+            JCH_TRY(jch_stage_in(ctx, host, b, n, dd, &dZt, &ldztd)); b += (size_t)n * dd;
+            JCH_TRY(jch_stage_in(ctx, host, b, m, dd, &dZq, &ldzqd)); b += (size_t)m * dd;
+            JCH_TRY(jch_stage_in(ctx, host, b, m, p, &dXq, &ldxqd));
+        }
+        double *Xrm = (double *)ctx->lw_xrm.ptr;
+        ctx->ev_used = 0;
+        ctx->prof = jch_profile{};
+        hipEvent_t ev0 = jch_ev(ctx);
+        jch_lw_to_rowmajor(ctx, dX, ldxd, n, (int)p, Xrm, ldr);
+        return lw_run(ctx, Xrm, ldr, n, p, dY, q, ldyd, dZt, ldztd, dZq, ldzqd, dd, dXq, m, ldxqd, k, h, tol, scal, nlv_lo, nlv_hi, pred,
+                      ind_out, dist_out, w_out, ev0, nullptr, nullptr);
+    });
 }
 
 extern "C" int32_t jch_lwplsr_prepare(jch_ctx *ctx, int32_t loc, const double *Xtrain, int64_t n, int64_t p, int64_t ldx,
@@ -1088,19 +1087,15 @@ extern "C" int32_t jch_lwplsr_prepare(jch_ctx *ctx, int32_t loc, const double *X
         hipMalloc((void **)&mo->Zt, sizeof(double) * (size_t)n * dd) != hipSuccess)
         return fail(jch_fail(ctx, JCH_ENOMEM, "jch_lwplsr_prepare: device allocation failed (%lld x %lld training rows)", (long long)n, (long long)p));
     const hipMemcpyKind kind = loc == JCH_LOC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    auto copy2d = [&](double *dst, const double *src, int64_t cols, int64_t ld) {
-        return hipMemcpy2DAsync(dst, sizeof(double) * n, src, sizeof(double) * ld, sizeof(double) * n, cols, kind, ctx->stream);
-    };
-    if (copy2d(mo->Y, Ytrain, q, ldy) != hipSuccess || copy2d(mo->Zt, Ztrain, dd, ldzt) != hipSuccess)
+    if (jch_copy2d(ctx, mo->Y, n, Ytrain, ldy, n, q, kind) != JCH_OK || jch_copy2d(ctx, mo->Zt, n, Ztrain, ldzt, n, dd, kind) != JCH_OK)
         return fail(jch_fail(ctx, JCH_EHIP, "jch_lwplsr_prepare: copy of Y / scores failed"));
     const double *dX = Xtrain;
     int64_t ldxd = ldx;
     if (loc == JCH_LOC_HOST) {   // stage the column-major X once, transpose on the device
         int32_t st = jch_reserve_xstage(ctx, sizeof(double) * (size_t)n * p);
         if (st != JCH_OK) return fail(st);
-        if (hipMemcpy2DAsync(ctx->xstage.ptr, sizeof(double) * n, Xtrain, sizeof(double) * ldx, sizeof(double) * n, p, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        if (jch_stage_in(ctx, true, (double *)ctx->xstage.ptr, n, p, &dX, &ldxd) != JCH_OK)
             return fail(jch_fail(ctx, JCH_EHIP, "jch_lwplsr_prepare: copy of X failed"));
-        dX = (const double *)ctx->xstage.ptr; ldxd = n;
     }
     jch_lw_to_rowmajor(ctx, dX, ldxd, n, (int)p, mo->Xrm, mo->ldr);
     if (dd <= 62 && n < ((int64_t)1 << 26)) {   // (whether a call is screened also depends on its k: jch_knn_screen_shape_ok)
@@ -1179,34 +1174,36 @@ extern "C" int32_t jch_lwplsr_predict_prepared(jch_ctx *ctx, const jch_lwplsr_mo
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "jch_lwplsr_predict_prepared: bad loc");
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t p = model->p, dd = model->dd;
-    const double *dZq = Zq, *dXq = Xq;
-    int64_t ldzqd = ldzq, ldxqd = ldxq;
-    if (loc == JCH_LOC_HOST) {
-        JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * dd + (size_t)m * p)));
-        double *b = (double *)ctx->xq.ptr;
-        if (Zq) JCH_HIP(ctx, hipMemcpy2DAsync(b, sizeof(double) * m, Zq, sizeof(double) * ldzq, sizeof(double) * m, dd, hipMemcpyHostToDevice, ctx->stream));
-        JCH_HIP(ctx, hipMemcpy2DAsync(b + (size_t)m * dd, sizeof(double) * m, Xq, sizeof(double) * ldxq, sizeof(double) * m, p, hipMemcpyHostToDevice, ctx->stream));
-        dZq = Zq ? b : nullptr; ldzqd = m; dXq = b + (size_t)m * dd; ldxqd = m;
-    }
-    ctx->ev_used = 0;
-    ctx->prof = jch_profile{};
-    hipEvent_t ev0 = jch_ev(ctx);
-    if (!Zq) {   // the model's query map: Xq -> the neighbour-search space, stage by stage in two alternating device buffers
-        size_t wmax = 0;
-        for (const auto &qm : model->qmaps) wmax = std::max(wmax, (size_t)qm.k_out);
-        JCH_TRY(jch_reserve(ctx, ctx->qz, sizeof(double) * 2 * (size_t)m * wmax));
-        double *zb[2] = {(double *)ctx->qz.ptr, (double *)ctx->qz.ptr + (size_t)m * wmax};
-        const double *src = dXq;
-        int64_t lds_ = ldxqd;
-        int w = 0;
-        for (const auto &qm : model->qmaps) {
-            JCH_TRY(jch_launch_affine_gemm(ctx, src, m, qm.p_in, lds_, qm.dB, qm.k_out, qm.kpad, qm.dB + (size_t)qm.p_in * qm.kpad, zb[w], m));
-            src = zb[w]; lds_ = m; w ^= 1;
+    const bool host = loc == JCH_LOC_HOST;
+    if (host) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * dd + (size_t)m * p)));
+    return jch_synced_on_failure(ctx, true, [&]() -> int32_t {   // (lw_run ends synchronised)
+        const double *dZq = Zq, *dXq = Xq;
+        int64_t ldzqd = ldzq, ldxqd = ldxq;
+        if (host) {
+            double *b = (double *)ctx->xq.ptr;
+            if (Zq) JCH_TRY(jch_stage_in(ctx, host, b, m, dd, &dZq, &ldzqd));
+            JCH_TRY(jch_stage_in(ctx, host, b + (size_t)m * dd, m, p, &dXq, &ldxqd));
         }
-        dZq = src; ldzqd = m;
-    }
-    return lw_run(ctx, model->Xrm, model->ldr, model->n, p, model->Y, model->q, model->n, model->Zt, model->n, dZq, ldzqd, dd, dXq, m, ldxqd, k, h, tol,
-                  scal, nlv_lo, nlv_hi, pred, ind_out, dist_out, w_out, ev0, model->has_screen ? &model->screen : nullptr, &model->screen_off);
+        ctx->ev_used = 0;
+        ctx->prof = jch_profile{};
+        hipEvent_t ev0 = jch_ev(ctx);
+        if (!Zq) {   // the model's query map: Xq -> the neighbour-search space, stage by stage in two alternating device buffers
+            size_t wmax = 0;
+            for (const auto &qm : model->qmaps) wmax = std::max(wmax, (size_t)qm.k_out);
+            JCH_TRY(jch_reserve(ctx, ctx->qz, sizeof(double) * 2 * (size_t)m * wmax));
+            double *zb[2] = {(double *)ctx->qz.ptr, (double *)ctx->qz.ptr + (size_t)m * wmax};
+            const double *src = dXq;
+            int64_t lds_ = ldxqd;
+            int w = 0;
+            for (const auto &qm : model->qmaps) {
+                JCH_TRY(jch_launch_affine_gemm(ctx, src, m, qm.p_in, lds_, qm.dB, qm.k_out, qm.kpad, qm.dB + (size_t)qm.p_in * qm.kpad, zb[w], m));
+                src = zb[w]; lds_ = m; w ^= 1;
+            }
+            dZq = src; ldzqd = m;
+        }
+        return lw_run(ctx, model->Xrm, model->ldr, model->n, p, model->Y, model->q, model->n, model->Zt, model->n, dZq, ldzqd, dd, dXq, m, ldxqd, k, h, tol,
+                      scal, nlv_lo, nlv_hi, pred, ind_out, dist_out, w_out, ev0, model->has_screen ? &model->screen : nullptr, &model->screen_off);
+    });
 }
 
 // Weighted (uncorrected) covariance of the columns of A (n x d, d <= 64): S = (A - 1 mu')' D (A - 1 mu'), the
@@ -1220,61 +1217,56 @@ extern "C" int32_t jch_weighted_cov(jch_ctx *ctx, int32_t loc, const double *A, 
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "jch_weighted_cov: bad loc");
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const int dd = (int)d, ldr = (dd + 1) & ~1, qpad = ((dd + 15) / 16) * 16;
-    const double *dA = A, *dw = weights;
-    int64_t ldad = lda;
-    if (loc == JCH_LOC_HOST) {
-        JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)n * d + (size_t)n)));
-        double *b = (double *)ctx->xq.ptr;
-        if (lda == n) JCH_HIP(ctx, hipMemcpyAsync(b, A, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, ctx->stream));
-        else JCH_HIP(ctx, hipMemcpy2DAsync(b, sizeof(double) * n, A, sizeof(double) * lda, sizeof(double) * n, d, hipMemcpyHostToDevice, ctx->stream));
-        dA = b; ldad = n;
-        if (weights) {
-            JCH_HIP(ctx, hipMemcpyAsync(b + (size_t)n * d, weights, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            dw = b + (size_t)n * d;
+    const bool host = loc == JCH_LOC_HOST, wide = d > JCH_MAXQ;
+    const int ldh = wide ? ldr : qpad;   // pitch of the rows of the result as it comes back
+    std::vector<double> hS((size_t)dd * ldh), hm(dd), ones(2 * (size_t)dd, 1.0);
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        const double *dA = A, *dw = weights;
+        int64_t ldad = lda;
+        if (host) {
+            JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)n * d + (size_t)n)));
+            double *b = (double *)ctx->xq.ptr;
+            JCH_TRY(jch_stage_in(ctx, host, b, n, d, &dA, &ldad));
+            if (weights) {
+                JCH_HIP(ctx, hipMemcpyAsync(b + (size_t)n * d, weights, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+                dw = b + (size_t)n * d;
+            }
         }
-    }
-    JCH_TRY(jch_reserve(ctx, ctx->dnorm, sizeof(double) * (size_t)n));
-    JCH_TRY(jch_reserve_xr(ctx, sizeof(double) * (size_t)n * ldr));   // (the fit workspace's row-major copy is overwritten here)
-    if (d > JCH_MAXQ) {
-        // wide A (round 4; the Mahalanobis branch of getknn on raw spectra, nlvdis = 0: src/getknn.jl:37-49, src/lwplsr.jl:21): the
-        // centred row-major copy from K2 (with A's first column standing in for Y), then the tiled MFMA SYRK of kern2.hip on it
-        JCH_TRY(jch_reserve(ctx, ctx->yr, sizeof(double) * (size_t)n * 16));
-        JCH_TRY(jch_reserve(ctx, ctx->small, sizeof(double) * ((size_t)dd * 16 + 4 * (size_t)dd + 64) + 4096));
-        JCH_TRY(jch_reserve(ctx, ctx->gram, sizeof(double) * (size_t)dd * ldr));
-        double *K1 = (double *)ctx->small.ptr, *mom1 = K1 + (size_t)dd * 16, *scl1 = mom1 + dd + 1, *hdr1 = scl1 + dd + 2;
-        double *dn1 = (double *)ctx->dnorm.ptr, *G = (double *)ctx->gram.ptr;
-        JCH_TRY(jch_launch_weights(ctx, dw, n, dn1, hdr1));
-        JCH_TRY(jch_launch_moments(ctx, dA, ldad, dA, ldad, dn1, n, dd, 1, nullptr, mom1));
-        std::vector<double> ones1((size_t)dd + 1, 1.0);
-        JCH_HIP(ctx, hipMemcpyAsync(scl1, ones1.data(), sizeof(double) * ((size_t)dd + 1), hipMemcpyHostToDevice, ctx->stream));
-        JCH_TRY(jch_launch_center_xty(ctx, const_cast<double *>(dA), ldad, const_cast<double *>(dA), ldad, dn1, n, dd, 1, mom1, scl1, false,
-                                      (double *)ctx->xr.ptr, ldr, (double *)ctx->yr.ptr, 16, K1, false));
-        JCH_TRY(jch_launch_syrk(ctx, (const double *)ctx->xr.ptr, n, dd, ldr, dn1, G, ldr));
-        std::vector<double> hG((size_t)dd * ldr), hm1(dd);
-        JCH_HIP(ctx, hipMemcpyAsync(hG.data(), G, sizeof(double) * hG.size(), hipMemcpyDeviceToHost, ctx->stream));
-        JCH_HIP(ctx, hipMemcpyAsync(hm1.data(), mom1, sizeof(double) * dd, hipMemcpyDeviceToHost, ctx->stream));
-        JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < dd; ++i)
-            for (int j = 0; j < dd; ++j) S[i + (size_t)j * dd] = hG[(size_t)i * ldr + j];
-        if (mu) for (int i = 0; i < dd; ++i) mu[i] = hm1[i];
+        JCH_TRY(jch_reserve(ctx, ctx->dnorm, sizeof(double) * (size_t)n));
+        JCH_TRY(jch_reserve_xr(ctx, sizeof(double) * (size_t)n * ldr));   // (the fit workspace's row-major copy is overwritten here)
+        double *dn = (double *)ctx->dnorm.ptr;
+        if (wide) {
+            // wide A (round 4; the Mahalanobis branch of getknn on raw spectra, nlvdis = 0: src/getknn.jl:37-49, src/lwplsr.jl:21): the
+            // centred row-major copy from K2 (with A's first column standing in for Y), then the tiled MFMA SYRK of kern2.hip on it
+            JCH_TRY(jch_reserve(ctx, ctx->yr, sizeof(double) * (size_t)n * 16));
+            JCH_TRY(jch_reserve(ctx, ctx->small, sizeof(double) * ((size_t)dd * 16 + 4 * (size_t)dd + 64) + 4096));
+            JCH_TRY(jch_reserve(ctx, ctx->gram, sizeof(double) * (size_t)dd * ldr));
+            double *K1 = (double *)ctx->small.ptr, *mom1 = K1 + (size_t)dd * 16, *scl1 = mom1 + dd + 1, *hdr1 = scl1 + dd + 2;
+            double *G = (double *)ctx->gram.ptr;
+            JCH_TRY(jch_launch_weights(ctx, dw, n, dn, hdr1));
+            JCH_TRY(jch_launch_moments(ctx, dA, ldad, dA, ldad, dn, n, dd, 1, nullptr, mom1));
+            JCH_HIP(ctx, hipMemcpyAsync(scl1, ones.data(), sizeof(double) * ((size_t)dd + 1), hipMemcpyHostToDevice, ctx->stream));
+            JCH_TRY(jch_launch_center_xty(ctx, const_cast<double *>(dA), ldad, const_cast<double *>(dA), ldad, dn, n, dd, 1, mom1, scl1, false,
+                                          (double *)ctx->xr.ptr, ldr, (double *)ctx->yr.ptr, 16, K1, false));
+            JCH_TRY(jch_launch_syrk(ctx, (const double *)ctx->xr.ptr, n, dd, ldr, dn, G, ldr));
+            JCH_HIP(ctx, hipMemcpyAsync(hS.data(), G, sizeof(double) * hS.size(), hipMemcpyDeviceToHost, ctx->stream));
+            JCH_HIP(ctx, hipMemcpyAsync(hm.data(), mom1, sizeof(double) * dd, hipMemcpyDeviceToHost, ctx->stream));
+            return JCH_OK;
+        }
+        JCH_TRY(jch_reserve(ctx, ctx->yr, sizeof(double) * (size_t)n * qpad));
+        JCH_TRY(jch_reserve(ctx, ctx->small, sizeof(double) * ((size_t)dd * qpad + 4 * (size_t)dd + 64) + 4096));
+        double *K = (double *)ctx->small.ptr, *mom = K + (size_t)dd * qpad, *scl = mom + 2 * dd, *hdr = scl + 2 * dd;
+        JCH_TRY(jch_launch_weights(ctx, dw, n, dn, hdr));
+        JCH_TRY(jch_launch_moments(ctx, dA, ldad, dA, ldad, dn, n, dd, dd, nullptr, mom));
+        JCH_HIP(ctx, hipMemcpyAsync(scl, ones.data(), sizeof(double) * 2 * dd, hipMemcpyHostToDevice, ctx->stream));
+        JCH_TRY(jch_launch_center_xty(ctx, const_cast<double *>(dA), ldad, const_cast<double *>(dA), ldad, dn, n, dd, dd, mom, scl, false,
+                                      (double *)ctx->xr.ptr, ldr, (double *)ctx->yr.ptr, qpad, K, false));
+        JCH_HIP(ctx, hipMemcpyAsync(hS.data(), K, sizeof(double) * hS.size(), hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(hm.data(), mom, sizeof(double) * dd, hipMemcpyDeviceToHost, ctx->stream));
         return JCH_OK;
-    }
-    JCH_TRY(jch_reserve(ctx, ctx->yr, sizeof(double) * (size_t)n * qpad));
-    JCH_TRY(jch_reserve(ctx, ctx->small, sizeof(double) * ((size_t)dd * qpad + 4 * (size_t)dd + 64) + 4096));
-    double *K = (double *)ctx->small.ptr, *mom = K + (size_t)dd * qpad, *scl = mom + 2 * dd, *hdr = scl + 2 * dd;
-    double *dn = (double *)ctx->dnorm.ptr;
-    JCH_TRY(jch_launch_weights(ctx, dw, n, dn, hdr));
-    JCH_TRY(jch_launch_moments(ctx, dA, ldad, dA, ldad, dn, n, dd, dd, nullptr, mom));
-    std::vector<double> ones(2 * (size_t)dd, 1.0);
-    JCH_HIP(ctx, hipMemcpyAsync(scl, ones.data(), sizeof(double) * 2 * dd, hipMemcpyHostToDevice, ctx->stream));
-    JCH_TRY(jch_launch_center_xty(ctx, const_cast<double *>(dA), ldad, const_cast<double *>(dA), ldad, dn, n, dd, dd, mom, scl, false,
-                                  (double *)ctx->xr.ptr, ldr, (double *)ctx->yr.ptr, qpad, K, false));
-    std::vector<double> hK((size_t)dd * qpad), hm(dd);
-    JCH_HIP(ctx, hipMemcpyAsync(hK.data(), K, sizeof(double) * hK.size(), hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipMemcpyAsync(hm.data(), mom, sizeof(double) * dd, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }));
     for (int i = 0; i < dd; ++i)
-        for (int j = 0; j < dd; ++j) S[i + (size_t)j * dd] = hK[(size_t)i * qpad + j];
+        for (int j = 0; j < dd; ++j) S[i + (size_t)j * dd] = hS[(size_t)i * ldh + j];
     if (mu) for (int i = 0; i < dd; ++i) mu[i] = hm[i];
     return JCH_OK;
 }

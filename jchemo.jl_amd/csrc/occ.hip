@@ -204,31 +204,25 @@ extern "C" int32_t jch_row_resid_ss(jch_ctx *ctx, int32_t loc, const double *X, 
     for (int64_t l = 0; l < k; ++l)
         for (int64_t j = 0; j < p; ++j) hb[(size_t)l * PB + j] = B[j + l * ldb];
     if (shift) for (int64_t j = 0; j < p; ++j) hb[(size_t)lrows * PB + j] = shift[j];
-    // every reservation first: nothing may fail between the first queued copy of `hb` (pageable) and the synchronisation except inside `run`
     JCH_TRY(jch_reserve(ctx, ctx->gemm_b, sizeof(double) * hb.size()));
     if (loc == JCH_LOC_HOST) {   // jch_transform's staging: X into xq, then Z and the result side by side in gemm_out
         JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)m * p));
         JCH_TRY(jch_reserve(ctx, ctx->gemm_out, sizeof(double) * (size_t)m * (size_t)(k + 1)));
     }
     double *dB = (double *)ctx->gemm_b.ptr;
-    auto run = [&]() -> int32_t {
+    return jch_synced(ctx, true, [&]() -> int32_t {
         JCH_HIP(ctx, hipMemcpyAsync(dB, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, ctx->stream));
         const double *dX = X, *dZ = Z;
         double *dO = out;
         int64_t ldxd = ldx, ldzd = ldz;
         if (loc == JCH_LOC_HOST) {
-            JCH_TRY(jch_copy2d(ctx, (double *)ctx->xq.ptr, m, X, ldx, m, p, hipMemcpyHostToDevice));
-            if (k > 0) JCH_TRY(jch_copy2d(ctx, (double *)ctx->gemm_out.ptr, m, Z, ldz, m, k, hipMemcpyHostToDevice));
-            dX = (const double *)ctx->xq.ptr; dZ = (const double *)ctx->gemm_out.ptr; dO = (double *)ctx->gemm_out.ptr + (size_t)m * k;
-            ldxd = m; ldzd = m;
+            JCH_TRY(jch_stage_in(ctx, true, (double *)ctx->xq.ptr, m, p, &dX, &ldxd));
+            if (k > 0) JCH_TRY(jch_stage_in(ctx, true, (double *)ctx->gemm_out.ptr, m, k, &dZ, &ldzd));
+            else { dZ = (const double *)ctx->gemm_out.ptr; ldzd = m; }
+            dO = (double *)ctx->gemm_out.ptr + (size_t)m * k;
         }
         JCH_TRY(oc_launch(ctx, dX, m, (int)p, ldxd, dZ, (int)k, ldzd, dB, ks, lrows, PB, dO));
         if (loc == JCH_LOC_HOST) JCH_HIP(ctx, hipMemcpyAsync(out, dO, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         return JCH_OK;
-    };
-    const int32_t st = run();
-    const hipError_t es = hipStreamSynchronize(ctx->stream);   // on the failure paths too: `hb` must outlive every copy queued from it
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
-    return JCH_OK;
+    });
 }

@@ -190,9 +190,8 @@ static int32_t rp_check(jch_ctx *ctx, const char *who, int32_t loc, const double
 template <class F>
 static int32_t rp_run(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, double *out, int64_t ldo, int64_t pout, F fn)
 {
-    if (loc == JCH_LOC_DEVICE) {
-        JCH_TRY(fn(X, n, ldx, out, ldo));
-    } else {
+    return jch_synced(ctx, true, [&]() -> int32_t {
+        if (loc == JCH_LOC_DEVICE) return fn(X, n, ldx, out, ldo);
         const int64_t rb = rp_block_rows(n, p);
         JCH_TRY(jch_reserve(ctx, ctx->rp_stage, sizeof(double) * (size_t)rb * (size_t)p));
         double *S = (double *)ctx->rp_stage.ptr;
@@ -202,9 +201,8 @@ static int32_t rp_run(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int
             JCH_TRY(fn(S, rows, rb, S, rb));
             JCH_TRY(jch_copy2d(ctx, out + r0, ldo, S, rb, rows, pout, hipMemcpyDeviceToHost));
         }
-    }
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JCH_OK;
+        return JCH_OK;
+    });
 }
 
 static int32_t rp_coef(jch_ctx *ctx, const double *host, size_t count, const double **dev)

@@ -201,7 +201,6 @@ extern "C" int32_t jch_farthest_pair(jch_ctx *ctx, int32_t loc, const double *X,
     const size_t o_pd = cv.take((size_t)nblocks), o_pr = cv.take((size_t)nblocks), o_pc = cv.take((size_t)nblocks), o_res = cv.take(4);
     const size_t o_cp = cv.take((size_t)ldc * (size_t)pp);
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    // every reservation first: nothing but a launch may fail between the first queued copy and the synchronisation
     JCH_TRY(jch_reserve(ctx, ctx->sp_ws, sizeof(double) * cv.off));
     JCH_TRY(jch_reserve_host(ctx, 64));
     if (loc == JCH_LOC_HOST) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)n * (size_t)p));
@@ -214,13 +213,10 @@ extern "C" int32_t jch_farthest_pair(jch_ctx *ctx, int32_t loc, const double *X,
         JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_sp_pair, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr.mark(ctx->device);
     }
-    auto run = [&]() -> int32_t {
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
         const double *dX = X;
         int64_t ldxd = ldx;
-        if (loc == JCH_LOC_HOST) {
-            JCH_TRY(jch_copy2d(ctx, (double *)ctx->xq.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
-            dX = (const double *)ctx->xq.ptr; ldxd = n;
-        }
+        JCH_TRY(jch_stage_in(ctx, loc == JCH_LOC_HOST, (double *)ctx->xq.ptr, n, p, &dX, &ldxd));
         if (ns) JCH_HIP(ctx, hipMemcpyAsync(dskip, sk.data(), sizeof(int64_t) * (size_t)ns, hipMemcpyHostToDevice, ctx->stream));
         const unsigned nbr = (unsigned)((n + SP_NT - 1) / SP_NT);
         hipLaunchKernelGGL(k_sp_rowflag, dim3(nbr), dim3(SP_NT), 0, ctx->stream, dX, n, p, ldxd, (const int64_t *)dskip, ns, flag);
@@ -234,11 +230,7 @@ extern "C" int32_t jch_farthest_pair(jch_ctx *ctx, int32_t loc, const double *X,
         JCH_HIP(ctx, hipGetLastError());
         JCH_HIP(ctx, hipMemcpyAsync(ctx->hstage, res_d, 32, hipMemcpyDeviceToHost, ctx->stream));
         return JCH_OK;
-    };
-    const int32_t st = run();
-    const hipError_t es = hipStreamSynchronize(ctx->stream);   // on the failure paths too: `sk` and a host X have copies queued
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
+    }));
     const int64_t *hi = (const int64_t *)ctx->hstage + 1;
     if (hi[0] < 0) return jch_fail(ctx, JCH_EINVAL, "jch_farthest_pair: fewer than two unskipped rows without a non-finite entry");
     pair[0] = hi[0]; pair[1] = hi[1];
@@ -425,19 +417,15 @@ extern "C" int32_t jch_maxmin_select(jch_ctx *ctx, int32_t loc, const double *X,
     const size_t o_cur = cv.take(4), o_tgt = cv.take((size_t)(4 * pstride)), o_pm = cv.take((size_t)(3 * nb)), o_pi = cv.take((size_t)(3 * nb));
     const size_t o_sel = cv.take(nk), o_dsel = cv.take(nk), o_mind = cv.take((size_t)n * (size_t)nsets);
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    // every reservation first: nothing but a launch may fail between the first queued copy and the synchronisation
     JCH_TRY(jch_reserve(ctx, ctx->sp_ws, sizeof(double) * cv.off));
     if (loc == JCH_LOC_HOST) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)n * (size_t)p));
     double *ws = (double *)ctx->sp_ws.ptr;
     int64_t *cur = (int64_t *)(ws + o_cur), *part_i = (int64_t *)(ws + o_pi), *dsel_i = (int64_t *)(ws + o_sel);
     double *tgt = ws + o_tgt, *part_m = ws + o_pm, *ddsel = ws + o_dsel, *mind = ws + o_mind;
-    auto run = [&]() -> int32_t {
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
         const double *dX = X;
         int64_t ldxd = ldx;
-        if (loc == JCH_LOC_HOST) {   // staged once for all steps
-            JCH_TRY(jch_copy2d(ctx, (double *)ctx->xq.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
-            dX = (const double *)ctx->xq.ptr; ldxd = n;
-        }
+        JCH_TRY(jch_stage_in(ctx, loc == JCH_LOC_HOST, (double *)ctx->xq.ptr, n, p, &dX, &ldxd));   // staged once for all steps
         JCH_HIP(ctx, hipMemcpyAsync(cur, hinit, sizeof(int64_t) * 2 * (size_t)nsets, hipMemcpyHostToDevice, ctx->stream));
         if (nsets == 1) mm_enqueue<1>(ctx, dX, n, p, ldxd, k, tgt, pstride, cur, mind, part_m, part_i, dsel_i, ddsel);
         else mm_enqueue<2>(ctx, dX, n, p, ldxd, k, tgt, pstride, cur, mind, part_m, part_i, dsel_i, ddsel);
@@ -445,11 +433,7 @@ extern "C" int32_t jch_maxmin_select(jch_ctx *ctx, int32_t loc, const double *X,
         JCH_HIP(ctx, hipMemcpyAsync(sel, dsel_i, sizeof(int64_t) * nk, hipMemcpyDeviceToHost, ctx->stream));
         if (dsel) JCH_HIP(ctx, hipMemcpyAsync(dsel, ddsel, sizeof(double) * nk, hipMemcpyDeviceToHost, ctx->stream));
         return JCH_OK;
-    };
-    const int32_t st = run();
-    const hipError_t es = hipStreamSynchronize(ctx->stream);   // on the failure paths too: host memory has copies queued
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
+    }));
     for (size_t a = 0; a < nk; ++a)
         if (sel[a] < 0) return jch_fail(ctx, JCH_EINVAL, "jch_maxmin_select: fewer than %lld rows per set without a non-finite entry", (long long)k);
     return JCH_OK;

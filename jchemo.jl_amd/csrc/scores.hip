@@ -49,29 +49,31 @@ extern "C" int32_t jch_score_sums(jch_ctx *ctx, int32_t loc, const double *Pred,
         return jch_fail(ctx, JCH_EINVAL, "jch_score_sums: bad arguments (ncol must be a multiple of q)");
     if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "jch_score_sums: bad loc");
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    const double *dP = Pred, *dY = Y, *dM = mask;
-    int64_t ldpd = ldp, ldyd = ldy;
-    if (loc == JCH_LOC_HOST) {
-        JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * ncol + (size_t)m * q + (size_t)m)));
-        double *b = (double *)ctx->xq.ptr;
-        if (ldp == m) JCH_HIP(ctx, hipMemcpyAsync(b, Pred, sizeof(double) * (size_t)m * ncol, hipMemcpyHostToDevice, ctx->stream));
-        else JCH_HIP(ctx, hipMemcpy2DAsync(b, sizeof(double) * m, Pred, sizeof(double) * ldp, sizeof(double) * m, ncol, hipMemcpyHostToDevice, ctx->stream));
-        dP = b; ldpd = m; b += (size_t)m * ncol;
-        if (ldy == m) JCH_HIP(ctx, hipMemcpyAsync(b, Y, sizeof(double) * (size_t)m * q, hipMemcpyHostToDevice, ctx->stream));
-        else JCH_HIP(ctx, hipMemcpy2DAsync(b, sizeof(double) * m, Y, sizeof(double) * ldy, sizeof(double) * m, q, hipMemcpyHostToDevice, ctx->stream));
-        dY = b; ldyd = m; b += (size_t)m * q;
-        if (mask) { JCH_HIP(ctx, hipMemcpyAsync(b, mask, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, ctx->stream)); dM = b; }
-    }
+    const bool host = loc == JCH_LOC_HOST;
+    if (host) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * ncol + (size_t)m * q + (size_t)m)));
     const int nbx = (int)std::max<int64_t>(1, std::min<int64_t>((m + 255) / 256, std::max<int64_t>(1, (int64_t)ctx->cus * 8 / ncol)));
     JCH_TRY(jch_reserve(ctx, ctx->colpart, sizeof(double) * ((size_t)nbx * ncol * 6 + (size_t)ncol * 6) + 4096));
-    double *part = (double *)ctx->colpart.ptr, *out = part + (size_t)nbx * ncol * 6;
-    hipLaunchKernelGGL(k_score_sums, dim3(nbx, (unsigned)ncol), dim3(256), 0, ctx->stream, dP, m, ldpd, dY, (int)q, ldyd, dM, part);
-    hipLaunchKernelGGL(k_score_reduce, dim3((unsigned)((ncol * 6 + 255) / 256)), dim3(256), 0, ctx->stream, part, nbx, (int)ncol, out);
-    JCH_TRY(jch_allreduce_f64(ctx, out, (size_t)ncol * 6));
-    JCH_HIP(ctx, hipGetLastError());
-    JCH_HIP(ctx, hipMemcpyAsync(sums, out, sizeof(double) * (size_t)ncol * 6, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JCH_OK;
+    return jch_synced(ctx, true, [&]() -> int32_t {
+        const double *dP = Pred, *dY = Y, *dM = mask;
+        int64_t ldpd = ldp, ldyd = ldy;
+        double *b = (double *)ctx->xq.ptr;   // (host calls only)
+        if (host) {
+            JCH_TRY(jch_stage_in(ctx, host, b, m, ncol, &dP, &ldpd));
+            JCH_TRY(jch_stage_in(ctx, host, b + (size_t)m * ncol, m, q, &dY, &ldyd));
+        }
+        if (host && mask) {
+            b += (size_t)m * ncol + (size_t)m * q;
+            JCH_HIP(ctx, hipMemcpyAsync(b, mask, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+            dM = b;
+        }
+        double *part = (double *)ctx->colpart.ptr, *out = part + (size_t)nbx * ncol * 6;
+        hipLaunchKernelGGL(k_score_sums, dim3(nbx, (unsigned)ncol), dim3(256), 0, ctx->stream, dP, m, ldpd, dY, (int)q, ldyd, dM, part);
+        hipLaunchKernelGGL(k_score_reduce, dim3((unsigned)((ncol * 6 + 255) / 256)), dim3(256), 0, ctx->stream, part, nbx, (int)ncol, out);
+        JCH_TRY(jch_allreduce_f64(ctx, out, (size_t)ncol * 6));
+        JCH_HIP(ctx, hipGetLastError());
+        JCH_HIP(ctx, hipMemcpyAsync(sums, out, sizeof(double) * (size_t)ncol * 6, hipMemcpyDeviceToHost, ctx->stream));
+        return JCH_OK;
+    });
 }
 
 // ---- the same statistics for EVERY nlv of a range straight from the scores (round 4, second half): the predictions of a fold
@@ -152,22 +154,6 @@ extern "C" int32_t jch_score_sums_lv(jch_ctx *ctx, int32_t loc, const double *T,
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const int le_all = nlv_hi - nlv_lo + 1;
     const int64_t ncol = (int64_t)le_all * q;
-    const double *dT = kfit > 0 ? T : Y, *dY = Y, *dM = mask;
-    int64_t ldtd = kfit > 0 ? ldt : ldy, ldyd = ldy;
-    if (loc == JCH_LOC_HOST) {
-        JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * kfit + (size_t)m * q + (size_t)m)));
-        double *b = (double *)ctx->xq.ptr;
-        if (kfit > 0) {
-            if (ldt == m) JCH_HIP(ctx, hipMemcpyAsync(b, T, sizeof(double) * (size_t)m * kfit, hipMemcpyHostToDevice, ctx->stream));
-            else JCH_HIP(ctx, hipMemcpy2DAsync(b, sizeof(double) * m, T, sizeof(double) * ldt, sizeof(double) * m, kfit, hipMemcpyHostToDevice, ctx->stream));
-        }
-        dT = b; ldtd = m; b += (size_t)m * kfit;
-        if (kfit == 0) dT = b;                             // (no score column is ever used; the kernel's clamped loads stay in range)
-        if (ldy == m) JCH_HIP(ctx, hipMemcpyAsync(b, Y, sizeof(double) * (size_t)m * q, hipMemcpyHostToDevice, ctx->stream));
-        else JCH_HIP(ctx, hipMemcpy2DAsync(b, sizeof(double) * m, Y, sizeof(double) * ldy, sizeof(double) * m, q, hipMemcpyHostToDevice, ctx->stream));
-        dY = b; ldyd = m; b += (size_t)m * q;
-        if (mask) { JCH_HIP(ctx, hipMemcpyAsync(b, mask, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, ctx->stream)); dM = b; }
-    }
     // small constants: Cs[l][k] = C[k][l] yscales[k], ymeans
     std::vector<double> hc((size_t)kfit * q + q + 8, 0.0);
     for (int64_t l = 0; l < kfit; ++l)
@@ -175,15 +161,31 @@ extern "C" int32_t jch_score_sums_lv(jch_ctx *ctx, int32_t loc, const double *T,
     for (int64_t k = 0; k < q; ++k) hc[(size_t)kfit * q + k] = ymeans ? ymeans[k] : 0.0;
     const int nbx = (int)std::max<int64_t>(1, std::min<int64_t>((m + 255) / 256, std::max<int64_t>(1, (int64_t)ctx->cus * 8 / q)));
     JCH_TRY(jch_reserve(ctx, ctx->colpart, sizeof(double) * ((size_t)nbx * ncol * 6 + (size_t)ncol * 6 + hc.size()) + 4096));
-    double *part = (double *)ctx->colpart.ptr, *out = part + (size_t)nbx * ncol * 6, *dC = out + (size_t)ncol * 6;
-    JCH_HIP(ctx, hipMemcpyAsync(dC, hc.data(), sizeof(double) * hc.size(), hipMemcpyHostToDevice, ctx->stream));
-    for (int l0 = 0; l0 < le_all; l0 += SLV_LE)
-        hipLaunchKernelGGL(k_score_sums_lv, dim3(nbx, (unsigned)q), dim3(256), 0, ctx->stream, dT, m, ldtd, (int)kfit, dC, dC + (size_t)kfit * q, dY, (int)q,
-                           ldyd, dM, nlv_lo + l0, std::min(SLV_LE, le_all - l0), (int)ncol, l0 * (int)q, part);
-    hipLaunchKernelGGL(k_score_reduce, dim3((unsigned)((ncol * 6 + 255) / 256)), dim3(256), 0, ctx->stream, part, nbx, (int)ncol, out);
-    JCH_TRY(jch_allreduce_f64(ctx, out, (size_t)ncol * 6));
-    JCH_HIP(ctx, hipGetLastError());
-    JCH_HIP(ctx, hipMemcpyAsync(sums, out, sizeof(double) * (size_t)ncol * 6, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (also keeps `hc` alive until its upload is done)
-    return JCH_OK;
+    const bool host = loc == JCH_LOC_HOST;
+    if (host) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * kfit + (size_t)m * q + (size_t)m)));
+    return jch_synced(ctx, true, [&]() -> int32_t {
+        const double *dT = T, *dY = Y, *dM = mask;
+        int64_t ldtd = ldt, ldyd = ldy;
+        double *b = (double *)ctx->xq.ptr;   // (host calls only)
+        if (host) {
+            if (kfit > 0) JCH_TRY(jch_stage_in(ctx, host, b, m, kfit, &dT, &ldtd));
+            JCH_TRY(jch_stage_in(ctx, host, b + (size_t)m * kfit, m, q, &dY, &ldyd));
+        }
+        if (kfit == 0) { dT = dY; ldtd = ldyd; }           // (no score column is ever used; the kernel's clamped loads stay in range)
+        if (host && mask) {
+            b += (size_t)m * kfit + (size_t)m * q;
+            JCH_HIP(ctx, hipMemcpyAsync(b, mask, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+            dM = b;
+        }
+        double *part = (double *)ctx->colpart.ptr, *out = part + (size_t)nbx * ncol * 6, *dC = out + (size_t)ncol * 6;
+        JCH_HIP(ctx, hipMemcpyAsync(dC, hc.data(), sizeof(double) * hc.size(), hipMemcpyHostToDevice, ctx->stream));
+        for (int l0 = 0; l0 < le_all; l0 += SLV_LE)
+            hipLaunchKernelGGL(k_score_sums_lv, dim3(nbx, (unsigned)q), dim3(256), 0, ctx->stream, dT, m, ldtd, (int)kfit, dC, dC + (size_t)kfit * q, dY,
+                               (int)q, ldyd, dM, nlv_lo + l0, std::min(SLV_LE, le_all - l0), (int)ncol, l0 * (int)q, part);
+        hipLaunchKernelGGL(k_score_reduce, dim3((unsigned)((ncol * 6 + 255) / 256)), dim3(256), 0, ctx->stream, part, nbx, (int)ncol, out);
+        JCH_TRY(jch_allreduce_f64(ctx, out, (size_t)ncol * 6));
+        JCH_HIP(ctx, hipGetLastError());
+        JCH_HIP(ctx, hipMemcpyAsync(sums, out, sizeof(double) * (size_t)ncol * 6, hipMemcpyDeviceToHost, ctx->stream));
+        return JCH_OK;
+    });
 }

@@ -69,22 +69,19 @@ extern "C" int32_t jch_stah(jch_ctx *ctx, int32_t loc, const double *X, int64_t 
         b2[cc] = acc;
     }
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    // every reservation first: nothing but a launch may fail between the first queued copy of `hb` (pageable) and the synchronisation
     JCH_TRY(jch_reserve(ctx, ctx->gemm_b, sizeof(double) * hb.size()));
     JCH_TRY(jch_reserve(ctx, ctx->st_t, sizeof(double) * (size_t)n * (size_t)b));
     JCH_TRY(jch_reserve(ctx, ctx->st_ms, sizeof(double) * (2 * (size_t)a + (loc == JCH_LOC_HOST ? (size_t)n : 0))));
     if (fit) JCH_TRY(jch_colselect_reserve(ctx, b));
     if (loc == JCH_LOC_HOST) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)n * (size_t)p));
     double *dB = (double *)ctx->gemm_b.ptr, *dT = (double *)ctx->st_t.ptr, *dmu = (double *)ctx->st_ms.ptr, *ds = dmu + a;
-    auto run = [&]() -> int32_t {
+    return jch_synced(ctx, true, [&]() -> int32_t {
         JCH_HIP(ctx, hipMemcpyAsync(dB, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, ctx->stream));
         const double *dX = X;
         double *dd = d;
         int64_t ldxd = ldx;
-        if (loc == JCH_LOC_HOST) {   // staged once for all panels
-            JCH_TRY(jch_copy2d(ctx, (double *)ctx->xq.ptr, n, X, ldx, n, p, hipMemcpyHostToDevice));
-            dX = (const double *)ctx->xq.ptr; ldxd = n; dd = ds + a;
-        }
+        JCH_TRY(jch_stage_in(ctx, loc == JCH_LOC_HOST, (double *)ctx->xq.ptr, n, p, &dX, &ldxd));   // staged once for all panels
+        if (loc == JCH_LOC_HOST) dd = ds + a;
         if (!fit) {
             JCH_HIP(ctx, hipMemcpyAsync(dmu, mu, sizeof(double) * (size_t)a, hipMemcpyHostToDevice, ctx->stream));
             JCH_HIP(ctx, hipMemcpyAsync(ds, s, sizeof(double) * (size_t)a, hipMemcpyHostToDevice, ctx->stream));
@@ -105,10 +102,5 @@ extern "C" int32_t jch_stah(jch_ctx *ctx, int32_t loc, const double *X, int64_t 
             JCH_HIP(ctx, hipMemcpyAsync(s, ds, sizeof(double) * (size_t)a, hipMemcpyDeviceToHost, ctx->stream));
         }
         return JCH_OK;
-    };
-    const int32_t st = run();
-    const hipError_t es = hipStreamSynchronize(ctx->stream);   // on the failure paths too: `hb`, mu and s must outlive every copy queued on them
-    if (st != JCH_OK) return st;
-    JCH_HIP(ctx, es);
-    return JCH_OK;
+    });
 }

@@ -1,5 +1,29 @@
-// Harness utilities: device-side synthetic input generator (README.md:79-94 `rand(n,p)` stand-in).
+// What every entry point may use: the grid of an element-wise launch, the strided copy and the operand staging of a host-array call
+// (their frame, jch_synced, is a template in jch_internal.h), and the device-side synthetic input generator (README.md:79-94
+// `rand(n,p)` stand-in).
+#include <algorithm>
+
 #include "jch_internal.h"
+
+unsigned jch_grid1(const jch_ctx *ctx, int64_t work)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, (int64_t)ctx->cus * 16));
+}
+
+int32_t jch_copy2d(jch_ctx *ctx, double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols, hipMemcpyKind kind)
+{
+    if (ldd == rows && lds == rows) JCH_HIP(ctx, hipMemcpyAsync(dst, src, sizeof(double) * (size_t)rows * (size_t)cols, kind, ctx->stream));
+    else JCH_HIP(ctx, hipMemcpy2DAsync(dst, sizeof(double) * ldd, src, sizeof(double) * lds, sizeof(double) * rows, cols, kind, ctx->stream));
+    return JCH_OK;
+}
+
+int32_t jch_stage_in(jch_ctx *ctx, bool host, double *dst, int64_t rows, int64_t cols, const double **src, int64_t *ld)
+{
+    if (!host) return JCH_OK;
+    JCH_TRY(jch_copy2d(ctx, dst, rows, *src, *ld, rows, cols, hipMemcpyHostToDevice));
+    *src = dst; *ld = rows;
+    return JCH_OK;
+}
 
 __device__ __forceinline__ double sm64_u01(uint64_t seed, uint64_t k)
 {

@@ -278,15 +278,16 @@ extern "C" int32_t jch_xtdx(jch_ctx *ctx, int32_t loc, const double *X, int64_t 
     double *ws = (double *)ctx->xt_ws.ptr;
     double *wn = ws + ow, *mu = mu_dev ? mu_dev : ws + omu, *G = G_dev ? G_dev : ws + oG;
     const int64_t ld = G_dev ? ldg : p;
-    xt_in in;
-    JCH_TRY(xt_stage(ctx, loc, X, n, p, ldx, weights, ws + owr, &in));
-    JCH_TRY(jch_launch_weights(ctx, in.dw, n, wn, ws + ohdr));
-    JCH_TRY(jch_covsel_pass(ctx, in.dX, n, p, in.ldxd, nullptr, wn, 1, n, mu));
-    JCH_TRY(jch_launch_xtdx(ctx, in.dX, n, (int)p, in.ldxd, mu, wn, G, ld));
-    if (G_host) JCH_TRY(jch_copy2d(ctx, G_host, p, G, ld, p, p, hipMemcpyDeviceToHost));
-    if (mu_host) JCH_HIP(ctx, hipMemcpyAsync(mu_host, mu, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JCH_OK;
+    return jch_synced(ctx, true, [&]() -> int32_t {
+        xt_in in;
+        JCH_TRY(xt_stage(ctx, loc, X, n, p, ldx, weights, ws + owr, &in));
+        JCH_TRY(jch_launch_weights(ctx, in.dw, n, wn, ws + ohdr));
+        JCH_TRY(jch_covsel_pass(ctx, in.dX, n, p, in.ldxd, nullptr, wn, 1, n, mu));
+        JCH_TRY(jch_launch_xtdx(ctx, in.dX, n, (int)p, in.ldxd, mu, wn, G, ld));
+        if (G_host) JCH_TRY(jch_copy2d(ctx, G_host, p, G, ld, p, p, hipMemcpyDeviceToHost));
+        if (mu_host) JCH_HIP(ctx, hipMemcpyAsync(mu_host, mu, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+        return JCH_OK;
+    });
 }
 
 extern "C" int32_t jch_pca_fit(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *weights, const double *Y, int64_t q,
@@ -313,58 +314,55 @@ extern "C" int32_t jch_pca_fit(jch_ctx *ctx, int32_t loc, const double *X, int64
     JCH_TRY(jch_reserve(ctx, ctx->xt_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->xt_ws.ptr;
     double *G = ws + oG, *wn = ws + ow, *mu = ws + omu, *cvd = ws + ocv, *xsd = ws + oxs, *trd = ws + otr;
-    xt_in in;
-    JCH_TRY(xt_stage(ctx, loc, X, n, p, ldx, weights, ws + owr, &in));
-    // ---- weights -> mu -> G (:83-91 without touching X)
-    JCH_TRY(jch_launch_weights(ctx, in.dw, n, wn, ws + ohdr));
-    JCH_TRY(jch_covsel_pass(ctx, in.dX, n, p, in.ldxd, nullptr, wn, 1, n, mu));
-    JCH_TRY(jch_launch_xtdx(ctx, in.dX, n, pi, in.ldxd, mu, wn, G, p));
-    hipLaunchKernelGGL(k_xt_diag, dim3((pi + XT_NT - 1) / XT_NT), dim3(XT_NT), 0, ctx->stream, G, p, pi, (int)(scal != 0), cvd, xsd);
-    if (scal) hipLaunchKernelGGL(k_xt_rescale, dim3(jch_grid1(ctx, p * p)), dim3(XT_NT), 0, ctx->stream, G, p, pi, xsd);
-    hipLaunchKernelGGL(k_xt_trace, dim3(1), dim3(XT_NT), 0, ctx->stream, G, p, pi, trd);
-    JCH_HIP(ctx, hipGetLastError());
     std::vector<double> xm((size_t)pi), xs((size_t)pi), cvh((size_t)pi);
     double trh = 0.0;
-    JCH_HIP(ctx, hipMemcpyAsync(xm.data(), mu, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipMemcpyAsync(xs.data(), xsd, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipMemcpyAsync(cvh.data(), cvd, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipMemcpyAsync(&trh, trd, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    // ---- the A leading eigenpairs of G: P and sv^2 (:95-98 by the eigen route)
     jch_eig_lead_out eg;
-    JCH_TRY(jch_eig_lead(ctx, G, p, p, nullptr, A, tol, maxit, &eg));
-    std::vector<double> Ph((size_t)pi * A);
-    JCH_HIP(ctx, hipMemcpyAsync(Ph.data(), eg.X, sizeof(double) * Ph.size(), hipMemcpyDeviceToHost, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // ---- T = cscale(X, xmeans, xscales) P (:99 is the same matrix: sqrtD^-1 U S = Xc V)
-    if (T) {
-        double *Td = host ? ws + oT : T;
-        JCH_TRY(jch_transform(ctx, JCH_LOC_DEVICE, in.dX, n, p, in.ldxd, xm.data(), xs.data(), Ph.data(), A, Td, n));
-        if (host) JCH_HIP(ctx, hipMemcpyAsync(T, Td, sizeof(double) * nn * A, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    // ---- pcr (src/pcr.jl:86-93): ymeans and Xs'D Yc, from which beta = diag(1 / sv^2) P' Xs'D Yc is host work (Xs = cscale(X))
-    if (qi > 0) {
-        const double *dY = Y;
-        int64_t ldyd = ldy;
-        if (host) {
-            JCH_TRY(jch_copy2d(ctx, ws + oY, n, Y, ldy, n, q, hipMemcpyHostToDevice));
-            dY = ws + oY; ldyd = n;
-        }
-        std::vector<double> ym((size_t)qi);
-        JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dY, n, q, ldyd, in.dw, ym.data(), nullptr));
-        JCH_HIP(ctx, hipMemcpyAsync(ws + oym, ym.data(), sizeof(double) * (size_t)qi, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_xt_dyc, dim3(jch_grid1(ctx, n * q)), dim3(XT_NT), 0, ctx->stream, dY, n, qi, ldyd, ws + oym, wn, ws + oV);
+    std::vector<double> Ph((size_t)pi * A), ym((size_t)qi), K((size_t)pi * qi);
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        xt_in in;
+        JCH_TRY(xt_stage(ctx, loc, X, n, p, ldx, weights, ws + owr, &in));
+        // ---- weights -> mu -> G (:83-91 without touching X)
+        JCH_TRY(jch_launch_weights(ctx, in.dw, n, wn, ws + ohdr));
+        JCH_TRY(jch_covsel_pass(ctx, in.dX, n, p, in.ldxd, nullptr, wn, 1, n, mu));
+        JCH_TRY(jch_launch_xtdx(ctx, in.dX, n, pi, in.ldxd, mu, wn, G, p));
+        hipLaunchKernelGGL(k_xt_diag, dim3((pi + XT_NT - 1) / XT_NT), dim3(XT_NT), 0, ctx->stream, G, p, pi, (int)(scal != 0), cvd, xsd);
+        if (scal) hipLaunchKernelGGL(k_xt_rescale, dim3(jch_grid1(ctx, p * p)), dim3(XT_NT), 0, ctx->stream, G, p, pi, xsd);
+        hipLaunchKernelGGL(k_xt_trace, dim3(1), dim3(XT_NT), 0, ctx->stream, G, p, pi, trd);
         JCH_HIP(ctx, hipGetLastError());
-        JCH_TRY(jch_covsel_pass(ctx, in.dX, n, p, in.ldxd, mu, ws + oV, q, n, ws + oK));
-        std::vector<double> K((size_t)pi * qi);
-        JCH_HIP(ctx, hipMemcpyAsync(K.data(), ws + oK, sizeof(double) * K.size(), hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(xm.data(), mu, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(xs.data(), xsd, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(cvh.data(), cvd, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(&trh, trd, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        // ---- the A leading eigenpairs of G: P and sv^2 (:95-98 by the eigen route)
+        JCH_TRY(jch_eig_lead(ctx, G, p, p, nullptr, A, tol, maxit, &eg));
+        JCH_HIP(ctx, hipMemcpyAsync(Ph.data(), eg.X, sizeof(double) * Ph.size(), hipMemcpyDeviceToHost, ctx->stream));
         JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ymeans) std::copy(ym.begin(), ym.end(), ymeans);
-        if (xtdy)
-            for (int k = 0; k < qi; ++k)
-                for (int j = 0; j < pi; ++j) xtdy[(size_t)j + (size_t)k * pi] = K[(size_t)j + (size_t)k * pi] / xs[j];
-    }
-    if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        // ---- T = cscale(X, xmeans, xscales) P (:99 is the same matrix: sqrtD^-1 U S = Xc V)
+        if (T) {
+            double *Td = host ? ws + oT : T;
+            JCH_TRY(jch_transform(ctx, JCH_LOC_DEVICE, in.dX, n, p, in.ldxd, xm.data(), xs.data(), Ph.data(), A, Td, n));
+            if (host) JCH_HIP(ctx, hipMemcpyAsync(T, Td, sizeof(double) * nn * A, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        // ---- pcr (src/pcr.jl:86-93): ymeans and Xs'D Yc, from which beta = diag(1 / sv^2) P' Xs'D Yc is host work (Xs = cscale(X))
+        if (qi > 0) {
+            const double *dY = Y;
+            int64_t ldyd = ldy;
+            JCH_TRY(jch_stage_in(ctx, host, ws + oY, n, q, &dY, &ldyd));
+            JCH_TRY(jch_col_stats(ctx, JCH_LOC_DEVICE, dY, n, q, ldyd, in.dw, ym.data(), nullptr));
+            JCH_HIP(ctx, hipMemcpyAsync(ws + oym, ym.data(), sizeof(double) * (size_t)qi, hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_xt_dyc, dim3(jch_grid1(ctx, n * q)), dim3(XT_NT), 0, ctx->stream, dY, n, qi, ldyd, ws + oym, wn, ws + oV);
+            JCH_HIP(ctx, hipGetLastError());
+            JCH_TRY(jch_covsel_pass(ctx, in.dX, n, p, in.ldxd, mu, ws + oV, q, n, ws + oK));
+            JCH_HIP(ctx, hipMemcpyAsync(K.data(), ws + oK, sizeof(double) * K.size(), hipMemcpyDeviceToHost, ctx->stream));
+            JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (ymeans) std::copy(ym.begin(), ym.end(), ymeans);
+            if (xtdy)
+                for (int k = 0; k < qi; ++k)
+                    for (int j = 0; j < pi; ++j) xtdy[(size_t)j + (size_t)k * pi] = K[(size_t)j + (size_t)k * pi] / xs[j];
+        }
+        if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+        return JCH_OK;
+    }));
     for (int e = 0; e < A; ++e) {
         const double ev = std::max(eg.theta[e], 0.0);   // `sv[sv .< 0] .= 0` (:98)
         if (eig) eig[e] = ev;

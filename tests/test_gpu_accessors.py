@@ -489,3 +489,4 @@ def test_zz_report_the_worst_ratios():
     for level, width in sorted(FOLD):
         print(f"  level {level:g}, {width}: worst err / (gamma(p + 3) |X - shift| |Bs|) = {FOLD[(level, width)]:.3f}")
     assert all(v <= 1.0 for v in WORST.values())
+

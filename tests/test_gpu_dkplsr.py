@@ -373,3 +373,11 @@ def test_full_size_fit(ctx):
     errs["C"] = O.rel_fro(ref.C, fm.fm.C * s)
     print("full size TT[end]/TT[1] = %.2e" % (ref.TT[-1] / ref.TT[0]), errs)
     assert max(errs.values()) < TOL, errs
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["dkplsr"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["dkplsr"][entry])

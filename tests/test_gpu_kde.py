@@ -289,3 +289,11 @@ def test_host_arrays_and_device_tensors_agree(J, ctx):
     assert oh.shape == (70, 2, 3) and np.array_equal(oh, _host(od))
     ref, bound = ld_kde_dens(inp["Z"], inp["Xq"], inp["cs"], inp["u"], inp["v2"], inp["coef"], inp["dims"])
     assert ratio(oh, ref, bound) <= 1.0
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["kde"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["kde"][entry])

@@ -491,3 +491,11 @@ def test_occlknndis(typc, reading, J, ctx):
     gd = J.predict(od, _dev(Xq), ctx=ctx)
     assert isinstance(gd.d["d"], torch.Tensor)
     assert O.rel_fro(_host(got.d["d"]), _host(gd.d["d"])) < 1e-12 and np.array_equal(_host(gd.pred), got.pred)
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["knn"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["knn"][entry])

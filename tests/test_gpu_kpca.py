@@ -237,3 +237,11 @@ def test_full_size_against_eigsh(J):
     vals, _ = eigsh(Kd, k=nlv, which="LA", tol=1e-13)
     vals = np.sort(vals)[::-1]
     assert np.max(np.abs(fm.eig - vals)) <= 1e-10 * fm.eig[0]
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["kpca"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["kpca"][entry])

@@ -294,3 +294,11 @@ def test_full_size_fit(ctx, q):
 def test_report_achieved():
     if ACHIEVED:
         print("\nkplsr: worst rel. Frobenius error per case:", {k: f"{v:.1e}" for k, v in sorted(ACHIEVED.items())})
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["kplsr"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["kplsr"][entry])

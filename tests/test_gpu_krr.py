@@ -312,3 +312,11 @@ def test_full_size_against_scipy_cholesky(J):
     e_A, e_p, e_df = _rel(A, Aref), _rel(pred - ref["ymeans"], pref), abs(df - dref)
     print(f"A {e_A:.3e} pred {e_p:.3e} (50 eps cond = {50 * EPS * cond:.3e}); df = {dref:.6f}, gpu off by {e_df:.3e} (10 n eps cond = {10 * n * EPS * cond:.3e})")
     assert e_A <= 50 * EPS * cond and e_p <= 50 * EPS * cond and e_df <= 10 * n * EPS * cond
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["krr"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["krr"][entry])

@@ -310,3 +310,11 @@ def test_xfit_and_xresid_take_a_pca_and_a_pcr(J, fits):
                 assert np.max(np.abs(got - ref)) <= 1e-9 * np.max(np.abs(ref)), (type(fm).__name__, nlv, fn.__name__)
     gd = J.xresid(pca, _cm(J, Xnew), nlv=3, ctx=ctx)
     assert gd.is_cuda and np.array_equal(_host(gd), J.xresid(pca, Xnew, nlv=3, ctx=ctx))
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["occ"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["occ"][entry])

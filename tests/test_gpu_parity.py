@@ -1701,3 +1701,11 @@ def test_one_pass_nipals_is_the_default_path_to_rounding(shape, alg, J, ctx):
     assert np.abs(G - np.diag(np.diag(G))).max() < 1e-9 * np.abs(np.diag(G)).max()
     with pytest.raises(J.JchError):                                  # outside the envelope of the postponed write-back: refused, loudly
         fn(X[:, :20], CO.fill_uniform(507, n, 17), nlv=2, ctx=ctx, one_pass=True)   # q = 17
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["lwplsr"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["lwplsr"][entry])

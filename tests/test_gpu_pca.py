@@ -377,3 +377,11 @@ def test_errors(J):
     finally:
         c.close()
         lib.jch_loopback_group_destroy(grp)
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["pca"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["pca"][entry])

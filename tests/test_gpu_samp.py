@@ -351,3 +351,11 @@ def test_one_larger_run_on_a_device_x(J, ctx):
     rd = J.sampdp(Xd, k, ctx=ctx)
     assert np.array_equal(rd.train, want2[:, 0]) and np.array_equal(rd.test, want2[:, 1])
     _check_partition(n, rd.train, rd.test, rd.remain)
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["samp"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["samp"][entry])

@@ -261,3 +261,11 @@ def test_seed_gives_the_same_directions_twice(J, ctx, data):
     assert np.array_equal(r1.d, r2.d) and np.array_equal(r1.mu, r2.mu) and np.array_equal(r1.s, r2.s)
     o = J.occstah(X, a=9, seed=3, ctx=ctx)
     assert np.array_equal(o.res_stah.P, r1.P) and np.array_equal(o.d["d"], r1.d)
+
+
+# ---------------------------------------------------------------------------------- the three routes of the C entries (tests/host_routes.py)
+@pytest.mark.parametrize("entry", sorted(__import__("host_routes").ROUTES["stah"]))
+def test_host_arrays_padded_and_unpadded_give_the_bits_of_the_device_route(entry):
+    """Device buffers, host arrays with ld == rows and with ld = rows + 3 between NaN guards: equal bytes, NaN padding kept, inputs unchanged."""
+    import host_routes as HR
+    HR.three_routes(HR.ROUTES["stah"][entry])
