@@ -651,6 +651,31 @@ JCH_API int32_t jch_knn_vote(jch_ctx *ctx, int32_t loc, const int32_t *cls, int6
                              int32_t k, int32_t *pred, double *score);
 JCH_API int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double *v, int64_t n, const int32_t *ind, int64_t m, int32_t k, double *out);
 
+/* ---- the local fit of the locally weighted MLR models (src/lwmlr.jl, src/lwmlr_s.jl, src/lwmlrda.jl, src/lwmlrda_s.jl through src/locw.jl and
+ * src/mlr.jl:69-86) ----------------------------------------------------------------------------------------------------------------
+ * jch_knn_wls -- for each of the m queries a weighted least-squares regression of its k neighbours' responses on their d coordinates, and the
+ *   prediction of the query's own row.  X n x d (ldx >= n), Y n x q (ldy >= n), Xq m x d (ldq >= m), column-major; ind (int32, 0-based) and w [m][k]
+ *   row-major, as jch_knn_search writes them; pred m x q column-major (ld m); info [m] int32, may be NULL.  All arrays [loc].  Any n, m, d, q, k >= 1
+ *   (d, q <= 2^20).  Per query i, with the rows r_j = ind[i][j]:
+ *       w~_j = w_ij / sum_j w_ij (`mweight`);  xbar = sum_j w~_j X[r_j, :], ybar = sum_j w~_j Y[r_j, :];
+ *       A = diag(sqrt(w~)) (X[r, :] - 1 xbar'), B = diag(sqrt(w~)) (Y[r, :] - 1 ybar');
+ *       beta = argmin |A beta - B| by Householder QR of A (no pivoting, no normal equations: the reference's `mlr` is the QR one);
+ *       pred[i, :] = ybar + (Xq[i, :] - xbar)' beta -- the reference's `int + x B` in centred form;  info[i] = 0.
+ *   Special cases:
+ *   - q == 1 and the k gathered responses all == (src/locw.jl:33-34): pred[i] is that value exactly and info[i] = 2, whatever k and d are.  For
+ *     q > 1 there is no shortcut.
+ *   - rank deficiency -- k <= d (a centred k-row slab has rank <= k - 1), or some |r_jj| <= min(k, d) 2^-52 max_i |r_ii|: the whole row pred[i, :]
+ *     is NaN and info[i] = 1.  A DEPARTURE from the reference, whose `\` returns LAPACK's minimum-norm solution on such a slab.
+ *   - a NaN in a neighbourhood or in a query stays in that query's row (info[i] = 0: it is no rank deficiency); a row index outside [0, n) gathers
+ *     NaN, so the whole row pred[i, :] is NaN, and is never read out of bounds.  The weights are expected > 0 (jch_knn_search clamps them to tol).
+ *   Fixed summation order, no atomics: the same call gives the same bits.  One 256-thread workgroup per query, one launch; the k x (d + q) slab
+ *   lives in LDS while 8 ((d + q) (k | 1) + 2 k + 3 d + q + ceil(k / 2)) bytes <= 150 KiB, beyond that in the ctx workspace (the same device code,
+ *   slower, never absent).  The entry first writes a row-major copy [X | Y] (n (d + q) doubles) into the ctx workspace.  It reserves the kNN
+ *   workspace only: the X copy a fit left for JCH_REUSE_XCOPY survives.  With loc JCH_LOC_DEVICE the call only enqueues on the ctx stream;
+ *   otherwise it returns synchronised.  One rank only. */
+JCH_API int32_t jch_knn_wls(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t d, int64_t ldx, const double *Y, int64_t q, int64_t ldy,
+                            const double *Xq, int64_t m, int64_t ldq, const int32_t *ind, const double *w, int32_t k, double *pred, int32_t *info);
+
 /* ---- Gaussian kernel density estimates: what the reference's `dmkern`, `kdeda` and `plskdeda` evaluate (src/dmkern.jl:151-163,
  * src/kdeda.jl:81-97, src/plskdeda.jl:52-64 with the prediction of src/plslda.jl:107-130) -- DESIGN.md §21.
  * jch_kde_dens -- for the m queries Xq (m x d) against the n training rows Z (n x d) GROUPED BY CLASS (class c owns the rows

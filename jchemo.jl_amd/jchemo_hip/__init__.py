@@ -13,4 +13,6 @@ from .stah import Occstah, Stah, col_median_mad, colmad, occstah, stah  # noqa: 
 from .samp import Samp, Sampcla, Sampdp, farthest_pair, maxmin_select, sampcla, sampdp, sampks, sampsys  # noqa: F401
 from .knn import (KnnPred, Knnda, Knnr, Occknndis, Occlknndis, getknn, knn_gather_median, knn_prepare, knn_release, knn_search, knn_vote, knn_wmean,  # noqa: F401
                   knnda, knnda_predict, knnr, knnr_predict, occknn_predict, occknndis, occlknndis)
+from .lwmlr import (Lwmlr, LwmlrS, Lwmlrda, LwmlrdaS, knn_wls, knn_wls_lds_bytes, lwmlr, lwmlr_predict, lwmlr_s, lwmlr_s_predict, lwmlrda,  # noqa: F401
+                    lwmlrda_predict, lwmlrda_s, lwmlrda_s_predict)
 from .kde import Dmkern, Kernda, dmkern, dmkern_predict, kde_dens, kdeda, kdeda_predict, plskdeda, plskdeda_predict  # noqa: F401

@@ -36,7 +36,7 @@ SYMBOLS = (
     "jch_xtdx", "jch_pca_fit", "jch_row_resid_ss", "jch_col_median_mad", "jch_stah",
     "jch_farthest_pair", "jch_maxmin_select",
     "jch_knn_prepare", "jch_knn_release", "jch_knn_search", "jch_knn_wmean", "jch_knn_vote", "jch_knn_gather_median", "jch_ctx_synchronize",
-    "jch_kde_dens",
+    "jch_kde_dens", "jch_knn_wls",
 )
 
 
@@ -146,6 +146,7 @@ def load():
     L.jch_knn_wmean.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i32, dp]
     L.jch_knn_vote.argtypes = [vp, i32, dp, i64, i32, dp, dp, i64, i32, dp, dp]
     L.jch_knn_gather_median.argtypes = [vp, i32, dp, i64, dp, i64, i32, dp]
+    L.jch_knn_wls.argtypes = [vp, i32, dp, i64, i64, i64, dp, i64, i64, dp, i64, i64, dp, dp, i32, dp, dp]
     L.jch_kde_dens.argtypes = [vp, i32, dp, i64, i64, i64, dp, i64, i64, dp, i32, dp, dp, dp, dp, i32, dp, i64]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]
     L.jch_ctx_set_profiling.argtypes = [vp, i32]

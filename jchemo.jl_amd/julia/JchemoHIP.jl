@@ -41,7 +41,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Occstah, occstah, stah, colmad, col_median_mad,
        sampks, sampdp, sampsys, sampcla, farthest_pair, maxmin_select,
        Knnr, Knnda, Occknndis, Occlknndis, getknn, knnr, knnda, occknndis, occlknndis, knn_search, knn_wmean, knn_vote, knn_gather_median,
-       Dmkern, Kernda, dmkern, kdeda, plskdeda, kde_dens
+       Dmkern, Kernda, dmkern, kdeda, plskdeda, kde_dens,
+       Lwmlr, LwmlrS, Lwmlrda, LwmlrdaS, lwmlr, lwmlr_s, lwmlrda, lwmlrda_s, knn_wls
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -2094,6 +2095,144 @@ function predict(object::Knnda, X; ctx = default_ctx())
     cls = [searchsortedfirst(object.lev, v) for v in yv]
     code = knn_vote(cls, length(object.lev), res.ind, res.w; ctx = ctx).pred
     merge((pred = reshape(object.lev[code], :, 1),), _knn_lists(res))
+end
+
+# ---- locally weighted MLR and MLR-DA (src/lwmlr.jl, src/lwmlr_s.jl, src/lwmlrda.jl, src/lwmlrda_s.jl through src/locw.jl, src/mlr.jl:69-86 and
+# src/mlrda.jl; DESIGN.md 23): one search, then one jch_knn_wls.  NOT EXECUTED in the build image (no Julia toolchain).
+"""`knn_wls(X, Y, Xq, ind, w)` — jch_knn_wls on host arrays: (pred, info).  Per query i the weighted least-squares fit (Householder QR) of
+Y[ind[:, i], :] on X[ind[:, i], :] with the weights w[:, i] / sum(w[:, i]), evaluated at Xq[i, :]; ind, w: k x m, rows 1-based.  info: 0 fitted,
+1 rank-deficient (the row of pred is NaN; the reference returns LAPACK's minimum-norm solution there), 2 the constant response of src/locw.jl:33-34."""
+function knn_wls(X, Y, Xq, ind, w; ctx = default_ctx())
+    Xm = Matrix{Float64}(Array(_in(X))); Ym = Matrix{Float64}(Array(_in(Y))); Qm = Matrix{Float64}(Array(_in(Xq)))
+    n, d = size(Xm); q = size(Ym, 2); k, m = size(ind)
+    (size(Ym, 1) == n && size(Qm, 2) == d && size(Qm, 1) == m && size(w) == size(ind)) || throw(DimensionMismatch("knn_wls: X, Y, Xq, ind and w do not fit"))
+    i0 = Matrix{Int32}(ind .- 1); wm = Matrix{Float64}(w); pred = zeros(m, q); info = zeros(Int32, m)
+    GC.@preserve Xm Ym Qm i0 wm pred info begin
+        check(ctx, ccall((:jch_knn_wls, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Int32},
+                          Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int32}),
+                         ctx.h, Int32(0), pointer(Xm), n, d, n, pointer(Ym), q, n, pointer(Qm), m, m, pointer(i0), pointer(wm), Int32(k), pointer(pred),
+                         pointer(info)))
+    end
+    (pred = pred, info = Int.(info))
+end
+
+struct Lwmlr                      # src/lwmlr.jl:1-9
+    X; Y; metric::String; h::Real; k::Int; tol::Real; verbose::Bool
+end
+struct LwmlrS                     # src/lwmlr_s.jl:1-10
+    T; Y; fm; metric::String; h::Real; k::Int; tol::Real; verbose::Bool
+end
+struct Lwmlrda                    # src/lwmlrda.jl:1-9
+    X; y; metric::String; h::Real; k::Int; tol::Real; verbose::Bool
+end
+struct LwmlrdaS                   # src/lwmlrda_s.jl:1-10
+    T; y; fm; metric::String; h::Real; k::Int; tol::Real; verbose::Bool
+end
+function _lw_check(metric, h, k)
+    metric in ("eucl", "mahal") || throw(ArgumentError("metric must be \"eucl\" or \"mahal\""))
+    (k isa Integer && k >= 1) || throw(ArgumentError("k = $k must be an integer >= 1"))
+    h > 0 || throw(ArgumentError("h = $h must be > 0"))
+    nothing
+end
+"`lwmlr(X, Y; metric = \"eucl\", h, k, tol = 1e-4, verbose = false)` — src/lwmlr.jl:64-70."
+function lwmlr(X, Y; metric = "eucl", h, k, tol = 1e-4, verbose = false, ctx = default_ctx())
+    _lw_check(metric, h, k)
+    Lwmlr(_in(X), _in(Y), metric, h, k, tol, verbose)
+end
+"`lwmlrda(X, y; metric = \"eucl\", h, k, tol = 1e-4, verbose = false)` — src/lwmlrda.jl:58-64."
+function lwmlrda(X, y; metric = "eucl", h, k, tol = 1e-4, verbose = false, ctx = default_ctx())
+    _lw_check(metric, h, k)
+    Lwmlrda(_in(X), ensure_mat(y), metric, h, k, tol, verbose)
+end
+_lw_transform(fm, X, ctx) = transform(fm, X; ctx = ctx)      # (Pca, Plsr, Plsrda through its inner fit, Dkplsr: the methods above)
+function _lw_reduce(X, Y, yv, s, nlv, reduc, gamma, scal, ctx)      # src/lwmlr_s.jl:84-95, src/lwmlrda_s.jl:90-103
+    reduc in ("pca", "pls", "dkpls") || throw(ArgumentError("reduc must be \"pca\", \"pls\" or \"dkpls\""))
+    zX = s === nothing ? X : _colocate_mat(Array(X)[s, :], X)
+    zY = Y === nothing ? nothing : (s === nothing ? Y : _colocate_mat(Array(Y)[s, :], X))
+    fm = if reduc == "pca"
+        pcasvd(zX; nlv = nlv, scal = scal, ctx = ctx)
+    elseif reduc == "pls"
+        yv === nothing ? plskern(zX, zY; nlv = nlv, scal = scal, ctx = ctx) : plsrda(zX, s === nothing ? yv : yv[s]; nlv = nlv, scal = scal, ctx = ctx)
+    else
+        dkplsr(zX, zY; nlv = nlv, kern = "krbf", gamma = gamma, scal = scal, ctx = ctx)
+    end
+    fm, _lw_transform(fm, X, ctx)
+end
+"""`lwmlr_s(X, Y; nlv, reduc = "pls", metric = "eucl", h, k, gamma = 1, psamp = 1, samp = "sys", tol = 1e-4, scal = false, verbose = false)` —
+src/lwmlr_s.jl:73-98.  psamp = 1 takes every row; samp = "random" draws from `MersenneTwister(seed)`."""
+function lwmlr_s(X, Y; nlv, reduc = "pls", metric = "eucl", h, k, gamma = 1, psamp = 1, samp = "sys", tol = 1e-4, scal = false, verbose = false,
+                 seed = nothing, ctx = default_ctx())
+    _lw_check(metric, h, k)
+    samp in ("sys", "random") || throw(ArgumentError("samp must be \"sys\" or \"random\""))
+    X = _in(X); Y = _in(Y); n = size(X, 1)
+    ms = Int64(round(psamp * n))
+    s = ms >= n ? nothing : (samp == "sys" ? sampsys(vec(sum(Array(Y); dims = 2)); k = ms).train : randperm(MersenneTwister(seed), n)[1:ms])
+    fm, T = _lw_reduce(X, Y, nothing, s, nlv, reduc, gamma, scal, ctx)
+    LwmlrS(T, Y, fm, metric, h, k, tol, verbose)
+end
+"""`lwmlrda_s(X, y; nlv, reduc = "pls", metric = "eucl", h, k, gamma = 1, psamp = 1, samp = "cla", tol = 1e-4, scal = false, verbose = false)` —
+src/lwmlrda_s.jl:77-106.  reduc = "dkpls" is `dkplsr` on `dummy(y).Y`, which is what the reference's `dkplsrda` fits."""
+function lwmlrda_s(X, y; nlv, reduc = "pls", metric = "eucl", h, k, gamma = 1, psamp = 1, samp = "cla", tol = 1e-4, scal = false, verbose = false,
+                   seed = nothing, ctx = default_ctx())
+    _lw_check(metric, h, k)
+    samp in ("cla", "random") || throw(ArgumentError("samp must be \"cla\" or \"random\""))
+    X = _in(X); yv = vec(Array(y)); n = size(X, 1)
+    ms = Int64(round(psamp * n))
+    nlev = length(unique(yv))
+    s = ms >= n ? nothing : (samp == "cla" ? sampcla(yv; k = max(Int64(round(ms / nlev)), 1), seed = seed).train : randperm(MersenneTwister(seed), n)[1:ms])
+    Yd = reduc == "dkpls" ? _colocate_mat(dummy(yv).Y, X) : nothing
+    fm, T = _lw_reduce(X, Yd, yv, s, nlv, reduc, gamma, scal, ctx)
+    LwmlrdaS(T, ensure_mat(y), fm, metric, h, k, tol, verbose)
+end
+function _lw_search(object, coords, Q, ctx)       # getknn(object.X, X; k, metric), then wdist and the clamp (src/lwmlr.jl:82-90)
+    Zt, qmap, _ = _knn_train_space((fm = nothing, scal = false, metric = object.metric), coords, ctx)
+    kh = knn_prepare(Zt; ctx = ctx)
+    res = knn_search(kh, qmap(Q), object.k; h = object.h, tol = object.tol)
+    knn_release!(kh)
+    res
+end
+function _lw_warn(info, who)
+    nbad = count(==(1), info)
+    nbad > 0 && @warn "$who: $nbad of $(length(info)) neighbourhoods are rank-deficient; their predictions are NaN"
+    info .== 1
+end
+function _lw_predict_reg(object, coords, Q, ctx, who)
+    res = _lw_search(object, coords, Q, ctx)
+    out = knn_wls(coords, object.Y, Q, res.ind, res.w; ctx = ctx)
+    _lw_warn(out.info, who)
+    object.verbose && println(join(1:size(Q, 1), " "))
+    merge((pred = out.pred,), _knn_lists(res))
+end
+function _lw_predict_da(object, coords, Q, ctx, who)   # the global dummy table, then the row argmax: equal to `mlrda` on the local levels (DESIGN.md 23)
+    res = _lw_search(object, coords, Q, ctx)
+    yv = vec(Array(object.y)); dm = dummy(yv)
+    out = knn_wls(coords, dm.Y, Q, res.ind, res.w; ctx = ctx)
+    bad = _lw_warn(out.info, who)
+    code = [argmax(replace(out.pred[i, :], NaN => -Inf)) for i in 1:size(out.pred, 1)]
+    if any(bad)                                    # no fit there: the weighted vote of knnda
+        cls = [searchsortedfirst(dm.lev, v) for v in yv]
+        vote = knn_vote(cls, length(dm.lev), res.ind, res.w; ctx = ctx).pred
+        code = [bad[i] ? vote[i] : code[i] for i in eachindex(code)]
+    end
+    object.verbose && println(join(1:size(Q, 1), " "))
+    merge((pred = reshape(dm.lev[code], :, 1),), _knn_lists(res))
+end
+"`predict(object::Lwmlr, X)` — src/lwmlr.jl:78-97."
+function predict(object::Lwmlr, X; ctx = default_ctx())
+    _lw_predict_reg(object, object.X, _in(X), ctx, "predict(::Lwmlr)")
+end
+"`predict(object::LwmlrS, X)` — src/lwmlr_s.jl:106-125."
+function predict(object::LwmlrS, X; ctx = default_ctx())
+    _lw_predict_reg(object, object.T, _lw_transform(object.fm, _in(X), ctx), ctx, "predict(::LwmlrS)")
+end
+"`predict(object::Lwmlrda, X)` — src/lwmlrda.jl:72-91."
+function predict(object::Lwmlrda, X; ctx = default_ctx())
+    _lw_predict_da(object, object.X, _in(X), ctx, "predict(::Lwmlrda)")
+end
+"`predict(object::LwmlrdaS, X)` — src/lwmlrda_s.jl:114-133."
+function predict(object::LwmlrdaS, X; ctx = default_ctx())
+    _lw_predict_da(object, object.T, _lw_transform(object.fm, _in(X), ctx), ctx, "predict(::LwmlrdaS)")
 end
 
 struct Occknndis                  # src/occknndis.jl:1-9 (e_cdf: the sorted training d), then the search handle
