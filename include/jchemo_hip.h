@@ -695,6 +695,37 @@ JCH_API int32_t jch_kde_dens(jch_ctx *ctx, int32_t loc, const double *Z, int64_t
                              const int64_t *cls_start, int32_t ncls, const double *u, const double *v2, const double *coef, const int32_t *dims,
                              int32_t nmod, double *out, int64_t ldo);
 
+/* ---- Gaussian discrimination on raw X: what the reference's `matW`, `dmnorm`, `lda`, `qda` and `mahsqchol` compute (src/matW.jl,
+ * src/dmnorm.jl:107-143, src/lda.jl:56-77, src/qda.jl:55-79, src/distances.jl:104-126) -- DESIGN.md §24.  All matrices column-major; [loc]: where
+ * `loc` says.  Each of the three entries serves one rank only, ends synchronised with the ctx stream, uses the ctx's own workspace (the X copy a
+ * fit left for JCH_REUSE_XCOPY is not touched) and returns JCH_EINVAL with a message before any device work for a NULL pointer, a leading
+ * dimension smaller than the row count, an empty class, or a cls_start that does not run from 0 to n.  Every output element is a fixed-order sum
+ * with no floating-point atomics: the same call gives the same bits, and so do a host and a device input, and an aligned and an unaligned one.
+ * jch_class_cov -- class means and within-class covariances of the n x p matrix Z [loc] GROUPED BY CLASS exactly as in jch_kde_dens (cls_start,
+ *   ncls + 1 entries, HOST).  ct (ncls x p, ld ncls, HOST, may be NULL): the class means.  Wi ([loc], p x p x ncls, ld p, stride p * p, may be
+ *   NULL): cov(Z_c; corrected = false) of every class, from one read-only pass over the rows of the class with the centring in registers; for a
+ *   class of ONE row the uncorrected covariance of all n rows (src/matW.jl:54-65; one more pass over Z, made only in that case).  W ([loc], p x p,
+ *   ld p, may be NULL) = sum_c (n_c / n) Wi[c], added in class order as src/matW.jl:69-73 does.  With Wi NULL one p x p workspace is reused per
+ *   class.  Both triangles of every output are bitwise symmetric.  p <= 32768, ncls <= 65535.
+ * jch_gauss_factor -- for f < nfac: S_f = S + f * sstride ([loc], p x p, ld lds; only its lower triangle is read, it is copied to the workspace and
+ *   never written) = L L' by the blocked Cholesky of jch_chol_factor; Uinv_f = Uinv + f * ustride ([loc], ld ldu) = L^-T, upper triangular with
+ *   exact zeros strictly below the diagonal (the reference's `LinearAlgebra.inv!(cholesky!(Hermitian(S)).U)`, src/dmnorm.jl:120-123); diagU
+ *   (p x nfac, HOST) = diag(L): det(S_f) = prod(diagU[:, f])^2; info[f] (HOST) as jch_chol_factor's: 0, or the 1-based column of the first pivot
+ *   that is not > 0 -- then Uinv_f and diagU[:, f] are unspecified; it is a result, not an error, and the other factors are not affected.  The call
+ *   invalidates the factor a jch_chol_solve of this ctx would be keyed to.  p <= 32768, nfac <= 65535.
+ * jch_mahsq_chol -- out[i, c] = sum_j z_j^2,  z_j = sum_{k <= j} (Xq[i, k] - Mu[c, k]) * Uinv_f[k, j],  f = (nfac == 1 ? 0 : c): the squared
+ *   Mahalanobis distances of the m rows of Xq ([loc], m x p, ld ldq) to the ncen centres Mu (ncen x p, ld ncen, HOST) under one shared factor
+ *   (nfac == 1) or one per centre (nfac == ncen); Uinv as jch_gauss_factor writes it ([loc]); out m x ncen ([loc], ldo >= m).  On the f64 matrix
+ *   cores, without an m x p intermediate.  The difference is taken before the product, never x U - mu U.  The strictly lower triangle of Uinv_f is
+ *   never read.  A NaN at Xq[i, k] reaches row i of out only; rows >= m of Xq and of out are never read or written.  ncen is meant to be small
+ *   (classes, not observations: every centre reads the query rows again): ncen <= 65535, p <= 32768. */
+JCH_API int32_t jch_class_cov(jch_ctx *ctx, int32_t loc, const double *Z, int64_t n, int64_t p, int64_t ldz, const int64_t *cls_start, int32_t ncls,
+                              double *Wi, double *W, double *ct);
+JCH_API int32_t jch_gauss_factor(jch_ctx *ctx, int32_t loc, const double *S, int64_t p, int64_t lds, int64_t sstride, int32_t nfac, double *Uinv,
+                                 int64_t ldu, int64_t ustride, double *diagU, int32_t *info);
+JCH_API int32_t jch_mahsq_chol(jch_ctx *ctx, int32_t loc, const double *Xq, int64_t m, int64_t p, int64_t ldq, const double *Mu, int32_t ncen,
+                               const double *Uinv, int64_t ldu, int64_t ustride, int32_t nfac, double *out, int64_t ldo);
+
 typedef struct jch_profile {
     double fit_ms;        /* device time of the last fit, first kernel -> last kernel (HIP events)   */
     double prologue_ms;   /* weights + means (+ var) + centre/transpose/XtY                           */

@@ -19,8 +19,9 @@
 // read once per direction and per 8 columns of B.
 // |L^-1|_F^2: W = L^-T (upper triangle of an n x n workspace) from X L' = I by the same forward substitution on block rows of the
 // identity: W[:, k] = W[:, k] inv(L_kk)' (k_chol_tile<0>), W[:, i] -= W[:, k] L_ik' for i > k (k_chol_tile<2>); the rows below block k
-// are known zeros and are never touched, so the cost is n^3/3 flop in products of inner dimension NB.  Only the sum of squares
-// leaves the device (block partials, then one workgroup, fixed order).
+// are known zeros and are never touched, so the cost is n^3/3 flop in products of inner dimension NB.  jch_launch_chol_inv_t writes W
+// into any n x n buffer (ld ldw): ctx->chol_w here, the caller's Uinv for jch_gauss_factor (gda.hip).  Of jch_chol_inv_fro2 only the sum
+// of squares leaves the device (block partials, then one workgroup, fixed order).
 #include <math.h>
 #include <stdlib.h>
 
@@ -231,10 +232,10 @@ __global__ __launch_bounds__(256) void k_chol_bwd(const double *__restrict__ Lp,
 }
 
 // ---- |L^-1|_F^2
-__global__ __launch_bounds__(256) void k_chol_eye(double *W, int64_t n)
+__global__ __launch_bounds__(256) void k_chol_eye(double *W, int64_t n, int64_t ldw)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) W[(size_t)i * (size_t)(n + 1)] = 1.0;
+    if (i < n) W[(size_t)i * (size_t)(ldw + 1)] = 1.0;
 }
 __global__ __launch_bounds__(256) void k_chol_sumsq(const double *__restrict__ W, int64_t tot, double *__restrict__ part, const int *__restrict__ info)
 {
@@ -348,6 +349,30 @@ int32_t jch_launch_chol_solve(jch_ctx *ctx, const double *L, int64_t n, int64_t 
     return JCH_OK;
 }
 
+int32_t jch_launch_chol_inv_t(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *W, int64_t ldw, const int *info)
+{
+    if (ctx->chol_L != L || ctx->chol_n != n || ctx->chol_ld != ldl)
+        return jch_fail(ctx, JCH_EINVAL, "the inverse factor: L is not the factor the last jch_chol_factor of this ctx produced");
+    const size_t nn = (size_t)n, lw = (size_t)ldw;
+    JCH_TRY(ch_attrs(ctx));
+    const double *inv = (const double *)ctx->chol_inv.ptr;
+    if (lw == nn) JCH_HIP(ctx, hipMemsetAsync(W, 0, sizeof(double) * nn * nn, ctx->stream));
+    else JCH_HIP(ctx, hipMemset2DAsync(W, sizeof(double) * lw, 0, sizeof(double) * nn, nn, ctx->stream));
+    hipLaunchKernelGGL(k_chol_eye, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, W, n, ldw);
+    JCH_HIP(ctx, hipGetLastError());
+    const int64_t nblk = (n + CH_NB - 1) / CH_NB;
+    for (int64_t k = 0; k < nblk; ++k) {
+        const int64_t k0 = k * CH_NB, below = n - k0 - CH_NB;
+        const int kb = (int)std::min<int64_t>(CH_NB, n - k0);
+        double *Wk = W + (size_t)k0 * lw;   // block column k of W: rows [0, k0 + kb) are live
+        JCH_TRY(launch_tile<0>(ctx, Wk, ldw, k0 + kb, inv + (size_t)k * CH_NB * CH_NB, CH_NB, kb, kb, Wk, ldw, info));
+        if (below > 0)
+            JCH_TRY(launch_tile<2>(ctx, Wk, ldw, k0 + CH_NB, L + (size_t)(k0 + CH_NB) + (size_t)k0 * (size_t)ldl, ldl, below, CH_NB,
+                                   W + (size_t)(k0 + CH_NB) * lw, ldw, info));
+    }
+    return JCH_OK;
+}
+
 int32_t jch_launch_chol_inv_fro2(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *out, const int *info)
 {
     if (ctx->chol_L != L || ctx->chol_n != n || ctx->chol_ld != ldl)
@@ -357,22 +382,8 @@ int32_t jch_launch_chol_inv_fro2(jch_ctx *ctx, const double *L, int64_t n, int64
         return jch_fail(ctx, JCH_ENOMEM, "jch_chol_inv_fro2: no room for the n x n workspace of inv(L) (%.1f GiB) that df needs; ask without df",
                         (double)(sizeof(double) * nn * nn) / (1024.0 * 1024.0 * 1024.0));
     JCH_TRY(jch_reserve(ctx, ctx->chol_s, 256 + sizeof(double) * (CH_SUMSQ_WG + 8)));
-    JCH_TRY(ch_attrs(ctx));
     double *W = (double *)ctx->chol_w.ptr, *part = (double *)((char *)ctx->chol_s.ptr + 256);
-    const double *inv = (const double *)ctx->chol_inv.ptr;
-    JCH_HIP(ctx, hipMemsetAsync(W, 0, sizeof(double) * nn * nn, ctx->stream));
-    hipLaunchKernelGGL(k_chol_eye, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, W, n);
-    JCH_HIP(ctx, hipGetLastError());
-    const int64_t nblk = (n + CH_NB - 1) / CH_NB;
-    for (int64_t k = 0; k < nblk; ++k) {
-        const int64_t k0 = k * CH_NB, below = n - k0 - CH_NB;
-        const int kb = (int)std::min<int64_t>(CH_NB, n - k0);
-        double *Wk = W + (size_t)k0 * nn;   // block column k of W: rows [0, k0 + kb) are live
-        JCH_TRY(launch_tile<0>(ctx, Wk, n, k0 + kb, inv + (size_t)k * CH_NB * CH_NB, CH_NB, kb, kb, Wk, n, info));
-        if (below > 0)
-            JCH_TRY(launch_tile<2>(ctx, Wk, n, k0 + CH_NB, L + (size_t)(k0 + CH_NB) + (size_t)k0 * (size_t)ldl, ldl, below, CH_NB,
-                                   W + (size_t)(k0 + CH_NB) * nn, n, info));
-    }
+    JCH_TRY(jch_launch_chol_inv_t(ctx, L, n, ldl, W, n, info));
     const int64_t tot = n * n;
     const int np = (int)std::max<int64_t>(1, std::min<int64_t>(CH_SUMSQ_WG, (tot + 255) / 256));
     hipLaunchKernelGGL(k_chol_sumsq, dim3((unsigned)np), dim3(256), 0, ctx->stream, W, tot, part, info);

@@ -99,6 +99,7 @@ struct jch_ctx {
     jch_buf sp_ws;   // samp.hip: row flags, per-workgroup triples and the result of a farthest-pair search; running minima, partials and targets of a max-min selection
     jch_buf kn_ws;   // knn.hip: the search's lists ahead of the drop of `self`, the results of a host call, the sort buffers and class accumulators of shapes beyond the LDS
     jch_buf kd_ws;   // kde.hip: the bandwidth factors, class offsets and model dimensions of a call, the per-split partial sums, the staging of a host call
+    jch_buf gd_ws;   // gda.hip: per entry, the vectors, one or two p x p matrices, the padded transposed factors and the staging of a host call
     const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
     int64_t chol_n = 0, chol_ld = 0;
     // profiling
@@ -368,9 +369,12 @@ int32_t jch_kblocks_run(jch_ctx *ctx, int32_t loc, int32_t kind, double gamma, d
                         int64_t ldo, const jch_kblock_step &step);
 // chol.hip: blocked Cholesky of the lower triangle of A (n x n, ld lda, in place), everything on ctx->stream, no host sync.  info_dev: a device
 // int that ends up 0 or the 1-based index of the first pivot that is not > 0.  The solves and jch_launch_chol_inv_fro2 need the factor the
-// last jch_launch_chol_factor produced (its inv(L_kk) blocks live in ctx->chol_inv).
+// last jch_launch_chol_factor produced (its inv(L_kk) blocks live in ctx->chol_inv).  jch_launch_chol_inv_t writes W = L^-T (upper triangle,
+// exact zeros below the diagonal) into the caller's n x n device buffer (ld ldw >= n; rows >= n of a column are not touched);
+// jch_launch_chol_inv_fro2 is that into ctx->chol_w followed by the sum of squares.
 int32_t jch_launch_chol_factor(jch_ctx *ctx, double *A, int64_t n, int64_t lda, int *info_dev);
 int32_t jch_launch_chol_solve(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *B, int64_t q, int64_t ldb, const int *info_dev);
+int32_t jch_launch_chol_inv_t(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *W, int64_t ldw, const int *info_dev);
 int32_t jch_launch_chol_inv_fro2(jch_ctx *ctx, const double *L, int64_t n, int64_t ldl, double *out_dev, const int *info_dev);
 int32_t jch_chol_info_word(jch_ctx *ctx, int **info_dev);   // the ctx's own device info word
 // util.hip

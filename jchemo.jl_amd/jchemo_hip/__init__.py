@@ -16,3 +16,5 @@ from .knn import (KnnPred, Knnda, Knnr, Occknndis, Occlknndis, getknn, knn_gathe
 from .lwmlr import (Lwmlr, LwmlrS, Lwmlrda, LwmlrdaS, knn_wls, knn_wls_lds_bytes, lwmlr, lwmlr_predict, lwmlr_s, lwmlr_s_predict, lwmlrda,  # noqa: F401
                     lwmlrda_predict, lwmlrda_s, lwmlrda_s_predict)
 from .kde import Dmkern, Kernda, dmkern, dmkern_predict, kde_dens, kdeda, kdeda_predict, plskdeda, plskdeda_predict  # noqa: F401
+from .gda import (Dmnorm, Lda, Qda, class_cov, dmnorm, dmnorm_predict, gauss_factor, lda, lda_predict, mahsq_chol, mahsqchol, matB, matW,  # noqa: F401
+                  qda, qda_predict)

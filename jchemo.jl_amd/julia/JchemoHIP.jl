@@ -42,7 +42,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        sampks, sampdp, sampsys, sampcla, farthest_pair, maxmin_select,
        Knnr, Knnda, Occknndis, Occlknndis, getknn, knnr, knnda, occknndis, occlknndis, knn_search, knn_wmean, knn_vote, knn_gather_median,
        Dmkern, Kernda, dmkern, kdeda, plskdeda, kde_dens,
-       Lwmlr, LwmlrS, Lwmlrda, LwmlrdaS, lwmlr, lwmlr_s, lwmlrda, lwmlrda_s, knn_wls
+       Lwmlr, LwmlrS, Lwmlrda, LwmlrdaS, lwmlr, lwmlr_s, lwmlrda, lwmlrda_s, knn_wls,
+       Dmnorm, Lda, Qda, dmnorm, lda, qda, matW, matB, mahsqchol, class_cov, gauss_factor, mahsq_chol
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -2475,6 +2476,190 @@ function __init__()
     m = get(Base.loaded_modules, _JCHEMO_ID, nothing)     # `using Jchemo` came first: hook up now; otherwise on first use
     m === nothing || attach!(m)
     nothing
+end
+
+# ---- Gaussian discrimination on raw X (src/dmnorm.jl, src/lda.jl, src/qda.jl, src/matW.jl, `mahsqchol` of src/distances.jl) over jch_class_cov,
+# jch_gauss_factor and jch_mahsq_chol; DESIGN.md §24.  The densities are the reference's plain products: beyond roughly p = 130 they leave the
+# Float64 range for all but well-conditioned data (densities of 0, a NaN posterior, the first level), as in the reference; the distances do not.
+struct Dmnorm                     # src/dmnorm.jl:1-5
+    mu; Uinv; detS
+end
+struct Lda                        # src/lda.jl:1-8; the nlev Dmnorm records share ONE Uinv
+    fm; W; ct; wprior; lev; ni
+end
+struct Qda                        # src/qda.jl:1-8, then the p x p x nlev stack the records' Uinv are slices of
+    fm; Wi; ct; wprior; lev; ni; Uinv
+end
+
+"""`class_cov(Z, cls_start; want_Wi = true, want_W = true)` — jch_class_cov on rows grouped by class (0-based offsets, ncls + 1 of them):
+(Wi, W, ct).  Wi (p x p x ncls) and W (p x p) live where Z does (`nothing` when not wanted), ct (ncls x p) is a host matrix.  Wi[:, :, c] is the
+uncorrected covariance of class c — of ALL rows for a class of one row (src/matW.jl:54-65) — and W = sum_c n_c / n Wi[:, :, c]."""
+function class_cov(Z, cls_start; want_Wi = true, want_W = true, ctx = default_ctx())
+    Z = _in(Z); n, p = size(Z)
+    cs = Vector{Int64}(vec(cls_start)); ncls = length(cs) - 1
+    Wi = want_Wi ? _similar(Z, p, p, ncls) : nothing
+    W = want_W ? _similar(Z, p, p) : nothing
+    ct = Matrix{Float64}(undef, ncls, p)
+    GC.@preserve Z cs Wi W ct begin
+        check(ctx, ccall((:jch_class_cov, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.h, _loc(Z), pointer(Z), n, p, stride(Z, 2), pointer(cs), Int32(ncls), Wi === nothing ? Ptr{Float64}(C_NULL) : pointer(Wi),
+                         W === nothing ? Ptr{Float64}(C_NULL) : pointer(W), pointer(ct)))
+    end
+    (Wi = Wi, W = W, ct = ct)
+end
+
+"""`gauss_factor(S)` — jch_gauss_factor: S p x p or p x p x nfac, symmetric (one triangle is read) -> (Uinv, diagU, info).  Uinv has S's shape and
+lives where S does: Uinv[:, :, f] = L_f^-T, upper triangular with exact zeros below the diagonal; diagU (p x nfac) and info (nfac) are host arrays;
+info[f] != 0 (the column of the first pivot that is not > 0) marks a factor that failed."""
+function gauss_factor(S; ctx = default_ctx())
+    S3 = ndims(S) == 3 ? _f64(S) : reshape(_in(S), size(S, 1), size(S, 1), 1)
+    p = size(S3, 1); nfac = size(S3, 3)
+    size(S3, 2) == p || throw(DimensionMismatch("S must be p x p or p x p x nfac"))
+    Uinv = _similar(S3, p, p, nfac); diagU = Matrix{Float64}(undef, p, nfac); info = zeros(Int32, nfac)
+    GC.@preserve S3 Uinv diagU info begin
+        check(ctx, ccall((:jch_gauss_factor, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Int32, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Int32}),
+                         ctx.h, _loc(S3), pointer(S3), p, stride(S3, 2), p * stride(S3, 2), Int32(nfac), pointer(Uinv), p, p * p, pointer(diagU), pointer(info)))
+    end
+    (Uinv = ndims(S) == 3 ? Uinv : reshape(Uinv, p, p), diagU = diagU, info = info)
+end
+
+"""`mahsq_chol(Xq, Mu, Uinv)` — jch_mahsq_chol: out[i, c] = |(Xq[i, :] - Mu[c, :]) Uinv_f|^2, f = 1 for one factor (Uinv p x p) or c for one per
+centre (p x p x ncen); Mu (ncen x p) is taken to the host; out (m x ncen) lives where Xq does.  The difference is taken before the product."""
+function mahsq_chol(Xq, Mu, Uinv; ctx = default_ctx())
+    Xq = _in(Xq); m, p = size(Xq)
+    Mh = Matrix{Float64}(Array(ensure_mat(Mu))); ncen = size(Mh, 1)
+    size(Mh, 2) == p || throw(DimensionMismatch("Xq has $p columns, Mu has $(size(Mh, 2))"))
+    U3 = ndims(Uinv) == 3 ? _f64(Uinv) : reshape(_in(Uinv), size(Uinv, 1), size(Uinv, 1), 1)
+    nfac = size(U3, 3)
+    (size(U3, 1) == p && size(U3, 2) == p) || throw(DimensionMismatch("Uinv is $(size(Uinv)), the data has $p columns"))
+    (nfac == 1 || nfac == ncen) || throw(ArgumentError("$nfac factors for $ncen centres (one, or one per centre)"))
+    out = _similar(Xq, m, ncen)
+    GC.@preserve Xq Mh U3 out begin
+        check(ctx, ccall((:jch_mahsq_chol, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int32, Ptr{Float64}, Int64, Int64, Int32, Ptr{Float64}, Int64),
+                         ctx.h, _loc(Xq), pointer(Xq), m, p, stride(Xq, 2), pointer(Mh), Int32(ncen), pointer(U3), stride(U3, 2), p * stride(U3, 2), Int32(nfac),
+                         pointer(out), max(m, 1)))
+    end
+    out
+end
+
+struct PosDefFailure <: Exception
+    what::String
+    info::Int
+end
+Base.showerror(io::IO, e::PosDefFailure) = print(io, "PosDefException: ", e.what, ": matrix is not positive definite; Cholesky factorization failed at column ", e.info)
+_gda_posdef(info, what) = info == 0 ? nothing : throw(PosDefFailure(what, Int(info)))
+function _gda_dets(diag)                      # det(U)^2 with det(U) the product of the diagonal in order; 0 -> 1e-20 (src/dmnorm.jl:121-122)
+    d = 1.0
+    for v in diag
+        d *= v
+    end
+    d^2 == 0 ? 1e-20 : d^2
+end
+_gda_coef(p, detS) = (2 * pi)^(-p / 2) * (1 / sqrt(detS))
+
+"`dmnorm(X = nothing; mu = nothing, S = nothing)` — src/dmnorm.jl:107-128; mean and `cov(X)` from one jch_class_cov call, the factor from jch_gauss_factor."
+function dmnorm(X = nothing; mu = nothing, S = nothing, ctx = default_ctx())
+    (X === nothing && (mu === nothing || S === nothing)) && throw(ArgumentError("dmnorm: give X, or both mu and S"))
+    if X !== nothing && (mu === nothing || S === nothing)
+        X = _in(X); n = size(X, 1)
+        res = class_cov(X, [0, n]; want_Wi = S === nothing, want_W = false, ctx = ctx)
+        mu === nothing && (mu = res.ct[1, :])
+        S === nothing && (S = res.Wi[:, :, 1] .* (n / (n - 1)))
+    end
+    muv = Vector{Float64}(vec(Array(mu))); S = ensure_mat(S)
+    (size(S, 1) == size(S, 2) == length(muv)) || throw(DimensionMismatch("mu has $(length(muv)) entries, S is $(size(S))"))
+    f = gauss_factor(S; ctx = ctx)
+    _gda_posdef(f.info[1], "dmnorm")
+    Dmnorm(muv, f.Uinv, _gda_dets(f.diagU[:, 1]))
+end
+"`predict(object::Dmnorm, X)` — src/dmnorm.jl:136-143: one jch_mahsq_chol call."
+function predict(object::Dmnorm, X; ctx = default_ctx())
+    X = _in(X); p = size(X, 2)
+    p == length(object.mu) || throw(DimensionMismatch("X has $p columns, the model has $(length(object.mu))"))
+    d = mahsq_chol(X, reshape(object.mu, 1, :), object.Uinv; ctx = ctx)
+    (pred = _gda_coef(p, object.detS) .* exp.(-.5 .* d),)
+end
+
+function _gda_prepare(X, y, prior)
+    yv = vec(Array(y)); n = size(X, 1)
+    length(yv) == n || throw(DimensionMismatch("X has $n rows, y has $(length(yv))"))
+    lev = sort(unique(yv)); ni = [count(==(l), yv) for l in lev]
+    wprior = _kde_prior(prior, ni)
+    order = sortperm([searchsortedfirst(lev, v) for v in yv]; alg = MergeSort)
+    (lev, ni, wprior, order, vcat(0, cumsum(ni)))
+end
+
+"`lda(X, y; prior = \"unif\")` — src/lda.jl:56-77: W of `matW` times n / (n - nlev), ONE factor, nlev Dmnorm records that share its Uinv."
+function lda(X, y; prior = "unif", ctx = default_ctx())
+    X = _in(X); n = size(X, 1)
+    lev, ni, wprior, order, cs = _gda_prepare(X, y, prior)
+    nlev = length(lev)
+    res = class_cov(X[order, :], cs; want_Wi = false, ctx = ctx)
+    W = res.W .* (n / (n - nlev))
+    f = gauss_factor(W; ctx = ctx)
+    _gda_posdef(f.info[1], "lda: the pooled W of $n rows in $nlev classes")
+    detS = _gda_dets(f.diagU[:, 1])
+    Lda([Dmnorm(res.ct[i, :], f.Uinv, detS) for i in 1:nlev], W, res.ct, wprior, lev, ni)
+end
+
+"`qda(X, y; prior = \"unif\")` — src/qda.jl:55-79: S_i = Wi[i] n_i / (n_i - 1) (Wi[i] itself for a class of one row), nlev factors in one call."
+function qda(X, y; prior = "unif", ctx = default_ctx())
+    X = _in(X)
+    lev, ni, wprior, order, cs = _gda_prepare(X, y, prior)
+    nlev = length(lev); p = size(X, 2)
+    res = class_cov(X[order, :], cs; want_W = false, ctx = ctx)
+    S = res.Wi .* _colocate_mat(reshape([k == 1 ? 1.0 : k / (k - 1) for k in ni], 1, 1, nlev), res.Wi)
+    f = gauss_factor(S; ctx = ctx)
+    for i in 1:nlev
+        _gda_posdef(f.info[i], "qda: class $(lev[i]) ($(ni[i]) rows)")
+    end
+    Qda([Dmnorm(res.ct[i, :], f.Uinv[:, :, i], _gda_dets(f.diagU[:, i])) for i in 1:nlev], res.Wi, res.ct, wprior, lev, ni, f.Uinv)
+end
+
+function _gda_predict(fm, U, wprior, lev, X, ctx)
+    X = _in(X); p = size(X, 2)
+    p == length(fm[1].mu) || throw(DimensionMismatch("X has $p columns, the model has $(length(fm[1].mu))"))
+    d = mahsq_chol(X, permutedims(hcat([f.mu for f in fm]...)), U; ctx = ctx)
+    dens = d isa Array ? exp.(-.5 .* d) .* permutedims([_gda_coef(p, f.detS) for f in fm]) :
+           exp.(-.5 .* d) .* _colocate_mat(reshape([_gda_coef(p, f.detS) for f in fm], 1, :), d)
+    pred, posterior = _kde_posterior(wprior, dens, lev)
+    (pred = pred, dens = dens, posterior = posterior)
+end
+"`predict(object::Lda, X)` — src/lda.jl:85-101: one jch_mahsq_chol call for all classes, with nfac = 1."
+predict(object::Lda, X; ctx = default_ctx()) = _gda_predict(object.fm, object.fm[1].Uinv, object.wprior, object.lev, X, ctx)
+"`predict(object::Qda, X)` — src/qda.jl:87-104: one jch_mahsq_chol call, one factor per class."
+predict(object::Qda, X; ctx = default_ctx()) = _gda_predict(object.fm, object.Uinv, object.wprior, object.lev, X, ctx)
+
+"`matW(X, y)` — src/matW.jl:44-75: (W, Wi, lev, ni); Wi p x p x nlev."
+function matW(X, y; ctx = default_ctx())
+    X = _in(X)
+    lev, ni, _, order, cs = _gda_prepare(X, y, "unif")
+    res = class_cov(X[order, :], cs; ctx = ctx)
+    (W = res.W, Wi = res.Wi, lev = lev, ni = ni)
+end
+"`matB(X, y)` — src/matW.jl:23-29: (B, ct, lev, ni); the centres come from the device, B = covm(ct, mweight(ni)) is host work."
+function matB(X, y; ctx = default_ctx())
+    X = _in(X)
+    lev, ni, _, order, cs = _gda_prepare(X, y, "unif")
+    ct = class_cov(X[order, :], cs; want_Wi = false, want_W = false, ctx = ctx).ct
+    w = ni ./ sum(ni)
+    z = sqrt.(w) .* (ct .- permutedims(w) * ct)
+    (B = transpose(z) * z, ct = ct, lev = lev, ni = ni)
+end
+"""`mahsqchol(X, Y[, Uinv])` — src/distances.jl:104-126, Y playing the centres (few rows): n x k where X lives.  Without Uinv: from the uncorrected
+covariance of X, factored on the device.  x - y is taken before the product with Uinv."""
+function mahsqchol(X, Y, Uinv = nothing; ctx = default_ctx())
+    X = _in(X); Y = ensure_mat(Y)
+    size(X, 2) == size(Y, 2) || throw(DimensionMismatch("X has $(size(X, 2)) columns, Y has $(size(Y, 2))"))
+    if Uinv === nothing
+        f = gauss_factor(class_cov(X, [0, size(X, 1)]; want_W = false, ctx = ctx).Wi[:, :, 1]; ctx = ctx)
+        _gda_posdef(f.info[1], "mahsqchol")
+        Uinv = f.Uinv
+    end
+    mahsq_chol(X, Y, ensure_mat(Uinv); ctx = ctx)
 end
 
 end # module
