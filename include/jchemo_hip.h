@@ -676,6 +676,45 @@ JCH_API int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double *v
 JCH_API int32_t jch_knn_wls(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t d, int64_t ldx, const double *Y, int64_t q, int64_t ldy,
                             const double *Xq, int64_t m, int64_t ldq, const int32_t *ind, const double *w, int32_t k, double *pred, int32_t *info);
 
+/* ---- local PLS discrimination (src/lwplsrda.jl, src/lwplslda.jl, src/lwplsqda.jl through src/locwlv.jl) ---------------------------------
+ * jch_knn_gda -- for each of the m queries the Gaussian discriminants (kind 1: `lda`, src/lda.jl:56-77; kind 2: `qda`, src/qda.jl:55-79) of its k
+ *   neighbours' scores, for ALL the nested score spaces T[:, 1:a], a = nlv_lo .. nlv_hi, from one Cholesky factorisation and one forward substitution
+ *   per covariance: the factor of a leading block is the leading block of the factor, so the squared Mahalanobis distance on the first a columns is a
+ *   prefix sum of z_j^2, z = L^-1 (tq - mu), and det S_a a prefix product of L_jj^2 (the reference refits per a, src/plslda.jl:84-86).
+ *   T [m][k][a_hi] (the score of neighbour e of query i on column j at (i k + e) a_hi + j), tq [m][a_hi] the queries' own scores, cls_nb [m][k] int32
+ *   the neighbours' class codes in 0 .. nlev - 1, post [m][le][nlev], code and info [m][le] int32, le = nlv_hi - nlv_lo + 1; all [loc].
+ *   1 <= nlv_lo <= nlv_hi <= a_hi; prior 0 = "unif", 1 = "prop".  Per query:
+ *     the local levels are the codes present, with counts ni; wprior = 1 / nlev_loc or ni / k; class means of the scores, unweighted;
+ *     Wi = the uncorrected covariance of the class's rows, for a class of ONE row that of all k rows (src/matW.jl:55-65);
+ *     lda: S = (sum_i ni / k Wi) k / (k - nlev_loc), shared; qda: S_i = Wi ni / (ni - 1), Wi itself when ni = 1;
+ *     dens_a = (2 pi)^(-a / 2) detS_a^(-1/2) exp(-d2_a / 2) (a detS of 0 is replaced by 1e-20, src/dmnorm.jl:122); post = wprior .* dens, normalised;
+ *     an absent class has posterior 0; code = the first maximum over the local levels (a NaN counts as the largest value: Julia's argmax).
+ *   info: 0 = fitted (all densities 0: a NaN posterior and the first local level); 1 = one local level: code is that class, post one-hot;
+ *     2 = pivot j of a covariance was <= (k + 4 j) 2^-52 S_jj (the error the covariance sum and the factorisation leave on the diagonal): the
+ *     models a >= j of that query get post NaN and code -1, the models a < j are valid; 3 = non-finite: a non-finite density (a NaN in the
+ *     query's scores) or a NaN pivot (a NaN among the neighbours' scores in the first a columns): post NaN, code the first local level; also for
+ *     a code outside 0 .. nlev - 1 in the list (code -1).
+ *   Differences t - mu are taken before any product; fixed summation order, no atomics: the same call gives the same bits; a NaN stays in its
+ *   query.  One 256-thread workgroup per query; scores, covariance and factor live in LDS while they fit in 150 KiB, beyond that in the kNN
+ *   workspace (the same device code).  Any k, nlev, a_hi <= 4096.  loc JCH_LOC_DEVICE only enqueues on the ctx stream; otherwise synchronised.
+ * jch_lwplsda_predict_prepared -- jch_lwplsr_predict_prepared on a handle whose Ytrain is the n x nlev dummy table of the class codes cls_train
+ *   ([n] int32 in 0 .. nlev - 1, [loc] like Zq and Xq): search, `wdist` weights, one weighted `plskern` per query on the dummy columns, then
+ *   kind 0 (`plsrda`, src/plsrda.jl:106-114): post = the dummy predictions, code = their first maximum over the LOCAL levels;
+ *   kind 1 / 2 (`plslda` / `plsqda`): jch_knn_gda on the local scores, which the local-fit kernel hands out (nlv_lo = 0: JCH_EINVAL).
+ *   A class absent from a neighbourhood is a zero response column, also under scal (the reference builds `dummy` on the local levels: the same
+ *   fit).  info as above, per (query, nlv); 1 = unanimous neighbourhood (src/locwlv.jl:25-28; not fitted, scores 0); with info 2 code is the
+ *   weighted vote of jch_knn_vote.  Requested nlv beyond the local model's clamp.  Results on the HOST: code, info [m][le], post [m][le][nlev],
+ *   tloc_out [m][k][nlv_hi] and tq_out [m][nlv_hi] (local scores, may be NULL), ind_out, dist_out, w_out [m][k] (may be NULL).
+ *   Outside the envelope of the p-space local-fit kernel (p <= 2048, nlev <= 16, nlv_hi <= 48, its LDS) the fits run one query at a time
+ *   (jch_plskern_fit on the local levels' dummy columns, jch_predict, one jch_transform row): slower, never absent. */
+JCH_API int32_t jch_knn_gda(jch_ctx *ctx, int32_t loc, const double *T, int64_t m, int32_t k, int32_t a_hi, const double *tq, const int32_t *cls_nb,
+                            int32_t nlev, int32_t kind, int32_t prior, int32_t nlv_lo, int32_t nlv_hi, double *post, int32_t *code, int32_t *info);
+JCH_API int32_t jch_lwplsda_predict_prepared(jch_ctx *ctx, const jch_lwplsr_model *model, const int32_t *cls_train, int32_t nlev, int32_t kind,
+                                             int32_t prior, int32_t loc, const double *Zq, int64_t ldzq, const double *Xq, int64_t m, int64_t ldxq,
+                                             int32_t k, double h, double tol, int32_t scal, int32_t nlv_lo, int32_t nlv_hi, int32_t *code,
+                                             double *post, int32_t *info, double *tloc_out, double *tq_out, int32_t *ind_out, double *dist_out,
+                                             double *w_out);
+
 /* ---- Gaussian kernel density estimates: what the reference's `dmkern`, `kdeda` and `plskdeda` evaluate (src/dmkern.jl:151-163,
  * src/kdeda.jl:81-97, src/plskdeda.jl:52-64 with the prediction of src/plslda.jl:107-130) -- DESIGN.md §21.
  * jch_kde_dens -- for the m queries Xq (m x d) against the n training rows Z (n x d) GROUPED BY CLASS (class c owns the rows

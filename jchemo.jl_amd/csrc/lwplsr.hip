@@ -379,6 +379,18 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
         double s = 0.0;
         for (int e = tid; e < k; e += 256) { idx[e] = g.ind[(size_t)qi * k + e]; s += g.w[(size_t)qi * k + e]; }
         const double sw = jch_block_sum<256>(s, sc);
+        if (g.da) {   // (block-uniform) discrimination: a neighbourhood of one class is not fitted (src/locwlv.jl:25-28 on the label column)
+            const int c0 = g.cls[idx[0]];
+            int differs = 0;
+            for (int e = tid; e < k; e += 256) differs |= (g.cls[idx[e]] != c0) ? 1 : 0;
+            const int wave_differs = __any(differs) ? 1 : 0;
+            if (lane == 0) sc[16 + wv] = (double)wave_differs;
+            __syncthreads();
+            const bool una = ((sc[16] + sc[17]) + sc[18]) + sc[19] == 0.0;
+            __syncthreads();
+            if (tid == 0) g.info[qi] = una ? 1 : 0;
+            if (una) continue;
+        }
         double sy[Q];
 #pragma unroll
         for (int y = 0; y < Q; ++y) sy[y] = 0.0;
@@ -486,7 +498,8 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
 #pragma unroll
             for (int y = 0; y < Q; ++y) {
                 const double z = yc[(size_t)e * Q + y] - ymean[y];
-                yc[(size_t)e * Q + y] = y < q ? (g.scal ? z / ysd[y] : z) : 0.0;
+                // (discrimination: a class absent from the neighbourhood has sd 0 — its column stays the zero column it is, also under scal)
+                yc[(size_t)e * Q + y] = y < q ? (g.scal ? ((g.da && ysd[y] == 0.0) ? 0.0 : z / ysd[y]) : z) : 0.0;
             }
         // ---- gather + centre/scale into the slab; centred query; K = X' D Y (for Q * KC <= 16 accumulated in the same pass)
         __syncthreads();
@@ -684,6 +697,7 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
                     const double t = tv[rr];
                     const double dt = e < k ? dl[e] * t : 0.0;
                     tt += dt * t;
+                    if (g.tloc && lane == 0 && e < k) g.tloc[((size_t)qi * k + e) * g.nlv_hi + a] = t;   // the neighbour's local score (one lane per row)
 #pragma unroll
                     for (int c = 0; c < KC; ++c) { zp[c].x += dt * x[rr][c].x; zp[c].y += dt * x[rr][c].y; }
                 }
@@ -705,6 +719,7 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
             }
             locw_block_sums<Q + 1>(cs, red);
             const double tq = cs[Q];
+            if (g.tqv && tid == 0) g.tqv[(size_t)qi * g.nlv_hi + a] = tq;
             for (int j = tid; j < ldr; j += 256) {
                 const double z = ((zred[j] + zred[KC * 128 + j]) + zred[2 * KC * 128 + j]) + zred[3 * KC * 128 + j];
 #pragma unroll
@@ -725,14 +740,28 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
             const int kk = nlvloc + 1 + e / q, y = e % q;
             if (kk >= g.nlv_lo) g.pred[((size_t)qi * le + (kk - g.nlv_lo)) * q + y] = prun[y];
         }
+        // score columns the local model does not have: zeros
+        if (g.tloc)
+            for (int e = tid; e < k * (g.nlv_hi - nlvloc); e += 256) {
+                const int r = e / (g.nlv_hi - nlvloc), a = nlvloc + e % (g.nlv_hi - nlvloc);
+                g.tloc[((size_t)qi * k + r) * g.nlv_hi + a] = 0.0;
+            }
+        if (g.tqv)
+            for (int a = nlvloc + tid; a < g.nlv_hi; a += 256) g.tqv[(size_t)qi * g.nlv_hi + a] = 0.0;
     }
+}
+
+// bytes of dynamic LDS of k_locw_plskern<KC, Q> (its carve-up at the top of the kernel): the one copy of the formula
+static size_t locw_pspace_lds(size_t k, size_t ldr, size_t KC, size_t Q)
+{
+    return sizeof(double) * ((1 + Q) * k + (5 + Q) * ldr + 4 * KC * 128 + 128 + 4 * Q + 16 + 5 * Q * (Q + 2) + 2 * (Q + 2) + 8 + 4 * (Q * (Q + 1) / 2 + Q + 1)) +
+           sizeof(int) * k + 64;
 }
 
 template <int KC, int Q>
 static int32_t launch_locw_q(jch_ctx *ctx, locw_args &g)
 {
-    const size_t lds = sizeof(double) * ((1 + (size_t)Q) * g.k + (5 + (size_t)Q) * g.ldr + 4 * KC * 128 + 128 + 4 * Q + 16 + 5 * Q * (Q + 2) +
-                                         2 * (Q + 2) + 8 + 4 * (Q * (Q + 1) / 2 + Q + 1)) + sizeof(int) * (size_t)g.k + 64;
+    const size_t lds = locw_pspace_lds(g.k, g.ldr, KC, Q);
     static jch_per_device_once attr;
     if (!attr.done(ctx->device)) {
         JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_locw_plskern<KC, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -761,16 +790,30 @@ static int32_t launch_locw(jch_ctx *ctx, locw_args &g)
     return launch_locw_q<KC, 16>(ctx, g);
 }
 
+// the shape fits the p-space kernel, the one that can hand out its local scores (the conditions of launch_locw_q, the k-space route apart)
+bool jch_locw_pspace_fits(const locw_args &g)
+{
+    if (g.q > 16 || g.nlv_hi > 48 || g.ldr > JCH_SWEEP_MAXP) return false;
+    const size_t KC = g.ldr <= 128 ? 1 : g.ldr <= 256 ? 2 : g.ldr <= 512 ? 4 : g.ldr <= 1024 ? 8 : 16;
+    const size_t Q = g.q <= 1 ? 1 : g.q <= 2 ? 2 : g.q <= 4 ? 4 : g.q <= 8 ? 8 : 16;
+    return locw_pspace_lds(g.k, g.ldr, KC, Q) <= 150 * 1024;
+}
+
 // the shape fits one of the batched local-fit kernels (the conditions of launch_locw_q / jch_locw_kspace_feasible)
 static bool locw_batched_fits(const locw_args &g)
 {
     if (g.q > 16 || g.nlv_hi > 48 || g.ldr > JCH_SWEEP_MAXP) return false;
-    if (jch_locw_kspace_feasible(g)) return true;
-    const int KC = g.ldr <= 128 ? 1 : g.ldr <= 256 ? 2 : g.ldr <= 512 ? 4 : g.ldr <= 1024 ? 8 : 16;
-    const size_t Q = g.q <= 1 ? 1 : g.q <= 2 ? 2 : g.q <= 4 ? 4 : g.q <= 8 ? 8 : 16;
-    const size_t lds = sizeof(double) * ((1 + Q) * g.k + (5 + Q) * g.ldr + 4 * KC * 128 + 128 + 4 * Q + 16 + 5 * Q * (Q + 2) +
-                                         2 * (Q + 2) + 8 + 4 * (Q * (Q + 1) / 2 + Q + 1)) + sizeof(int) * (size_t)g.k + 64;
-    return lds <= 150 * 1024;
+    return jch_locw_kspace_feasible(g) || jch_locw_pspace_fits(g);
+}
+
+// the p-space kernel for this row width (the caller has checked jch_locw_pspace_fits: no k-space fallback is taken)
+int32_t jch_launch_locw_pspace(jch_ctx *ctx, locw_args &g)
+{
+    if (g.ldr <= 128) return launch_locw<1>(ctx, g);
+    if (g.ldr <= 256) return launch_locw<2>(ctx, g);
+    if (g.ldr <= 512) return launch_locw<4>(ctx, g);
+    if (g.ldr <= 1024) return launch_locw<8>(ctx, g);
+    return launch_locw<16>(ctx, g);
 }
 
 // ---------------------------------------------------------------- C ABI
@@ -778,23 +821,7 @@ static bool locw_batched_fits(const locw_args &g)
 // kernels want it — the row-major copy of Xtrain for the 4 KB-contiguous neighbour gathers, device copies of Ytrain and of
 // the (whitened) training scores.  Built once by jch_lwplsr_prepare and reused by every jch_lwplsr_predict_prepared call;
 // the one-shot jch_lwplsr_predict builds the same thing in the ctx workspace on every call.
-struct jch_lwplsr_model {
-    int device = 0;
-    int64_t n = 0, p = 0, q = 0, dd = 0;
-    int ldr = 0;
-    double *Xrm = nullptr;   // [n][ldr]
-    double *Y = nullptr;     // n x q, column-major, ld n
-    double *Zt = nullptr;    // n x dd, column-major, ld n
-    // optional: the map that takes a query block to the neighbour-search space, as a chain of affine maps (the reference's
-    // transform(fm, X) followed by the whitening of getknn: two stages) kept on the device — jch_lwplsr_add_query_map
-    struct qmap { int p_in = 0, k_out = 0, kpad = 0; double *dB = nullptr; };   // dB: [p_in][kpad] folded B, then kpad folded biases
-    std::vector<qmap> qmaps;
-    // the operand-ordered f32 copy of the scores for the screened kNN (lwplsr_screen.hip); absent when the score space is too wide
-    bool has_screen = false;
-    mutable bool screen_off = false;   // set when a call had a quarter of its queries redone by the exact scan
-    knn_screen screen;
-    void *screen_mem = nullptr;
-};
+// (struct jch_lwplsr_model: lwplsr_dev.h — shared with lwplsda.hip)
 
 void jch_lw_to_rowmajor(jch_ctx *ctx, const double *dX, int64_t ldxd, int64_t n, int p, double *Xrm, int ldr)
 {

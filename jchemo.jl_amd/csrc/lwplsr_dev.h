@@ -1,6 +1,8 @@
 // Arguments shared by the batched local-fit kernels of the kNN-LWPLSR prediction path (lwplsr.hip: k_locw_plskern, the
 // p-space kernel; lwplsr_kspace.hip: k_locw_kspace, the Gram / k-space kernel) — src/locwlv.jl:9-48.
 #pragma once
+#include <vector>
+
 #include "jch_internal.h"
 
 struct locw_args {
@@ -14,6 +16,13 @@ struct locw_args {
     int dbg;                                // measurement switches (JCH_LOCW_DBG; results then wrong by design): 1 = every query gathers rows 0 .. k-1
     int *flags;                             // [m] or null.  k-space kernel: flags[i] = 1 when query i lies too far from its neighbours for the
                                             // Gram matrix about the query row (pivot check, lwplsr_kspace.hip): the caller refits those queries
+    // p-space kernel only, all optional (null / 0: nothing changes) — the local scores for the discriminants of lwplsda.hip
+    double *tloc = nullptr;                 // [m][k][nlv_hi]: the score of neighbour e on LV a at ((i k + e) nlv_hi + a); columns beyond the local model's LVs are 0
+    double *tqv = nullptr;                  // [m][nlv_hi]: the query's own scores
+    const int *cls = nullptr;               // [n] training class codes, read with da
+    int da = 0;                             // discrimination: Y is a dummy table.  A neighbourhood of one class is not fitted (info = 1, src/locwlv.jl:25-28
+                                            // on the label column); a response whose local weighted sd is 0 (a class absent from the neighbourhood) is a zero column
+    int *info = nullptr;                    // [m], written with da: 1 = unanimous neighbourhood (nothing else written for the query), 0 otherwise
 };
 
 // lwplsr_kspace.hip: _feasible: the k-space kernel can take this shape (k <= 208, q <= 8, nlv <= 48, p <= 2048);
@@ -72,6 +81,45 @@ int32_t jch_launch_knn_generic(jch_ctx *ctx, const knn_args &a);
 // local fits one query at a time: gather the neighbour rows, jch_plskern_fit on them, jch_predict on the query row (the
 // reference's own schedule, src/locwlv.jl:18-39); dpred [m][le][q] device
 int32_t jch_lw_generic_fits(jch_ctx *ctx, const locw_args &g, int64_t n, const int *only = nullptr /*host: query indices to fit (null: all)*/, int n_only = 0);
+
+// The model-constant part of a prediction (jch_lwplsr_prepare, lwplsr.hip): the handle of include/jchemo_hip.h
+struct jch_lwplsr_model {
+    int device = 0;
+    int64_t n = 0, p = 0, q = 0, dd = 0;
+    int ldr = 0;
+    double *Xrm = nullptr;   // [n][ldr]
+    double *Y = nullptr;     // n x q, column-major, ld n
+    double *Zt = nullptr;    // n x dd, column-major, ld n
+    // optional: the map that takes a query block to the neighbour-search space, as a chain of affine maps (the reference's
+    // transform(fm, X) followed by the whitening of getknn: two stages) kept on the device — jch_lwplsr_add_query_map
+    struct qmap { int p_in = 0, k_out = 0, kpad = 0; double *dB = nullptr; };   // dB: [p_in][kpad] folded B, then kpad folded biases
+    std::vector<qmap> qmaps;
+    // the operand-ordered f32 copy of the scores for the screened kNN (lwplsr_screen.hip); absent when the score space is too wide
+    bool has_screen = false;
+    mutable bool screen_off = false;   // set when a call had a quarter of its queries redone by the exact scan
+    knn_screen screen;
+    void *screen_mem = nullptr;
+};
+// lwplsr.hip: the shape fits the p-space local-fit kernel (the one that can hand out its local scores), and its launch
+bool jch_locw_pspace_fits(const locw_args &g);
+int32_t jch_launch_locw_pspace(jch_ctx *ctx, locw_args &g);
+
+// lwplsda.hip: the nested Gaussian discriminants of a neighbourhood (k_knn_gda); all pointers on the device
+struct gda_args {
+    const double *T; int64_t tstride; int ldt;   // scores: neighbour e of query i on LV j at T[i tstride + e ldt + j]
+    const double *tq; int ldq;                   // the queries' scores [m][ldq]
+    const int *cls;                              // [m][k] class codes of the neighbours
+    int m, k, a, nlev, kind, prior;              // a: the score columns that are factorised (models beyond a clamp to a); kind 1 lda, 2 qda; prior 0 unif, 1 prop
+    int nlv_lo, nlv_hi;                          // the models, 1 <= nlv_lo <= nlv_hi
+    double *post; int *code; int *info;          // [m][le][nlev], [m][le], [m][le]
+    double *scratch; size_t per_block;           // null (LDS) or one slab of per_block doubles per workgroup
+};
+size_t jch_knn_gda_slab_doubles(int64_t k, int64_t a, int64_t nlev);
+bool jch_knn_gda_plan(jch_ctx *ctx, int64_t m, int64_t k, int64_t a, int64_t nlev, int64_t *nb, size_t *slab);
+int32_t jch_launch_knn_gda(jch_ctx *ctx, const gda_args &g, int64_t nb);
+
+// lwplsr_generic.hip: the discrimination fits outside the p-space kernel's envelope, one query at a time (hcn: HOST [m][k] neighbour class codes)
+int32_t jch_lw_generic_fits_da(jch_ctx *ctx, const locw_args &g, const int *hcn);
 
 #ifdef __HIPCC__
 #define KNN_CAP 1024   // candidate buffer per query (LDS) of the scan; the finishing kernels order at most this many (distance, index) pairs

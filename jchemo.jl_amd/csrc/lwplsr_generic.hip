@@ -247,6 +247,85 @@ __global__ __launch_bounds__(64) void k_lw_place(const double *__restrict__ src,
     }
 }
 
+// discrimination: the prediction row of a fit on the LOCAL levels' dummy columns (q_loc of them, col[j] = the class of local column j) into the
+// query's [le][nlev] slot; the absent classes keep the zeros the caller wrote
+__global__ __launch_bounds__(64) void k_lw_place_cols(const double *__restrict__ src, int q_loc, const int *__restrict__ col, int lo_fit, int hi_fit, int nlv_lo,
+                                                      int nlv_hi, int nlev, double *__restrict__ dst)
+{
+    for (int e = threadIdx.x; e < (nlv_hi - nlv_lo + 1) * q_loc; e += 64) {
+        const int t = e / q_loc, j = e % q_loc;
+        const int af = min(max(nlv_lo + t, lo_fit), hi_fit);
+        dst[(size_t)t * nlev + col[j]] = src[(af - lo_fit) * q_loc + j];
+    }
+}
+// the score columns of a local fit (T: k x nfit, ld k) into the query's [k][nlv_hi] slot
+__global__ __launch_bounds__(256) void k_lw_scores_out(const double *__restrict__ T, int k, int nfit, int nlv_hi, double *__restrict__ dst)
+{
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < k * nfit; e += gridDim.x * 256) {
+        const int a = e / k, r = e - a * k;
+        dst[(size_t)r * nlv_hi + a] = T[e];
+    }
+}
+
+// The discrimination fits of jch_lwplsda_predict_prepared outside the p-space kernel's envelope, one query at a time, the reference's own schedule
+// (src/locwlv.jl:18-39 with src/plsrda.jl:71-77): a unanimous neighbourhood is not fitted (info 1); otherwise `dummy` on the LOCAL levels — the
+// columns of the global table that are present —, jch_plskern_fit on the gathered rows with its scores T, jch_predict and one jch_transform row for
+// the query's scores.  hcn: HOST [m][k] class codes of the neighbours; g.pred, g.tloc, g.tqv: zeroed by the caller; g.info [m] is written.
+int32_t jch_lw_generic_fits_da(jch_ctx *ctx, const locw_args &g, const int *hcn)
+{
+    const int p = g.p, nlev = g.q, k = g.k, m = g.m, le = g.nlv_hi - g.nlv_lo + 1;
+    const int nlv_req = std::max(g.nlv_hi, 1);
+    const int nlv_cap = std::min(std::min(nlv_req, p), k);
+    const size_t need = sizeof(double) * ((size_t)k * p + (size_t)k * nlev + (size_t)(le + 1) * nlev + (size_t)k * nlv_cap + ((size_t)m * nlev + 1) / 2 + 64);
+    JCH_TRY(jch_reserve(ctx, ctx->lw_work, need));
+    double *Xl = (double *)ctx->lw_work.ptr, *Yl = Xl + (size_t)k * p, *prow = Yl + (size_t)k * nlev, *Tl = prow + (size_t)(le + 1) * nlev;
+    int *dcol = (int *)(Tl + (size_t)k * nlv_cap);
+    // the local levels of every query, in code order
+    std::vector<int> hcol((size_t)m * nlev, 0), nloc((size_t)m, 0), hinfo((size_t)m, 0);
+    for (int i = 0; i < m; ++i) {
+        std::vector<char> seen((size_t)nlev, 0);
+        for (int e = 0; e < k; ++e) { const int c = hcn[(size_t)i * k + e]; if (c >= 0 && c < nlev) seen[(size_t)c] = 1; }
+        for (int c = 0; c < nlev; ++c) if (seen[(size_t)c]) hcol[(size_t)i * nlev + nloc[(size_t)i]++] = c;
+        hinfo[(size_t)i] = nloc[(size_t)i] <= 1 ? 1 : 0;
+    }
+    JCH_HIP(ctx, hipMemcpyAsync(dcol, hcol.data(), sizeof(int) * hcol.size(), hipMemcpyHostToDevice, ctx->stream));
+    JCH_HIP(ctx, hipMemcpyAsync(g.info, hinfo.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+    JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the two host images go out of scope with this function)
+    std::vector<double> P((size_t)p * nlv_cap), R((size_t)p * nlv_cap), W((size_t)p * nlv_cap), C((size_t)nlev * nlv_cap), TT(nlv_cap), xm(p), xs(p), ym(nlev), ys(nlev);
+    const bool prof = ctx->profiling;
+    ctx->profiling = false;
+    int32_t st = JCH_OK;
+    for (int i = 0; i < m && st == JCH_OK; ++i) {
+        if (hinfo[(size_t)i]) continue;
+        const int ql = nloc[(size_t)i];
+        const int *ind = g.ind + (size_t)i * k;
+        hipLaunchKernelGGL(k_lw_gather_x, dim3((k + 63) / 64, (p + 63) / 64), dim3(256), 0, ctx->stream, g.Xrm, g.ldr, p, ind, k, Xl);
+        for (int j = 0; j < ql; ++j)
+            hipLaunchKernelGGL(k_lw_gather_y, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, g.Y + (size_t)hcol[(size_t)i * nlev + j] * (size_t)g.ldy, g.ldy, 1, ind, k,
+                               Yl + (size_t)j * k);
+        jch_pls_desc d{};
+        d.n = k; d.p = p; d.q = ql; d.nlv = nlv_req; d.scal = g.scal; d.dtype = JCH_F64; d.loc = JCH_LOC_DEVICE; d.inplace = 0; d.reserved = 0;
+        int32_t nlv_fit = 0;
+        st = jch_plskern_fit(ctx, &d, Xl, k, Yl, k, g.w + (size_t)i * k, Tl, P.data(), R.data(), W.data(), C.data(), TT.data(), xm.data(), xs.data(), ym.data(), ys.data(),
+                             nullptr, &nlv_fit);
+        if (st != JCH_OK) break;
+        const int hi_fit = std::min(g.nlv_hi, (int)nlv_fit), lo_fit = std::min(g.nlv_lo, hi_fit);
+        st = jch_predict(ctx, JCH_LOC_DEVICE, g.Xq + i, 1, p, g.ldxq, xm.data(), xs.data(), ym.data(), ys.data(), R.data(), C.data(), ql, lo_fit, hi_fit, prow, 1);
+        if (st != JCH_OK) break;
+        hipLaunchKernelGGL(k_lw_place_cols, dim3(1), dim3(64), 0, ctx->stream, prow, ql, dcol + (size_t)i * nlev, lo_fit, hi_fit, g.nlv_lo, g.nlv_hi, nlev,
+                           g.pred + (size_t)i * le * nlev);
+        if (hi_fit >= 1) {
+            if (g.tloc) hipLaunchKernelGGL(k_lw_scores_out, dim3((k * hi_fit + 255) / 256), dim3(256), 0, ctx->stream, Tl, k, hi_fit, g.nlv_hi, g.tloc + (size_t)i * k * g.nlv_hi);
+            if (g.tqv) st = jch_transform(ctx, JCH_LOC_DEVICE, g.Xq + i, 1, p, g.ldxq, xm.data(), xs.data(), R.data(), hi_fit, g.tqv + (size_t)i * g.nlv_hi, 1);
+        }
+        if (st == JCH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = jch_fail(ctx, JCH_EHIP, "jch_lwplsda_predict_prepared: a per-query fit failed");   // (the host model pieces are rewritten by the next fit)
+    }
+    ctx->profiling = prof;
+    if (st != JCH_OK) return st;
+    JCH_HIP(ctx, hipGetLastError());
+    return JCH_OK;
+}
+
 int32_t jch_lw_generic_fits(jch_ctx *ctx, const locw_args &g, int64_t n, const int *only, int n_only)
 {
     (void)n;

@@ -18,3 +18,5 @@ from .lwmlr import (Lwmlr, LwmlrS, Lwmlrda, LwmlrdaS, knn_wls, knn_wls_lds_bytes
 from .kde import Dmkern, Kernda, dmkern, dmkern_predict, kde_dens, kdeda, kdeda_predict, plskdeda, plskdeda_predict  # noqa: F401
 from .gda import (Dmnorm, Lda, Qda, class_cov, dmnorm, dmnorm_predict, gauss_factor, lda, lda_predict, mahsq_chol, mahsqchol, matB, matW,  # noqa: F401
                   qda, qda_predict)
+from .lwplsda import (LwplsdaPred, LwplsLda, LwplsQda, LwplsrS, Lwplsrda, LwplsrdaS, knn_gda, knn_gda_lds_bytes, locw_pspace_lds_bytes, lwplslda, lwplslda_predict,  # noqa: F401
+                      lwplsqda, lwplsqda_predict, lwplsr_s, lwplsr_s_predict, lwplsrda, lwplsrda_predict, lwplsrda_s, lwplsrda_s_predict)

@@ -43,7 +43,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Knnr, Knnda, Occknndis, Occlknndis, getknn, knnr, knnda, occknndis, occlknndis, knn_search, knn_wmean, knn_vote, knn_gather_median,
        Dmkern, Kernda, dmkern, kdeda, plskdeda, kde_dens,
        Lwmlr, LwmlrS, Lwmlrda, LwmlrdaS, lwmlr, lwmlr_s, lwmlrda, lwmlrda_s, knn_wls,
-       Dmnorm, Lda, Qda, dmnorm, lda, qda, matW, matB, mahsqchol, class_cov, gauss_factor, mahsq_chol
+       Dmnorm, Lda, Qda, dmnorm, lda, qda, matW, matB, mahsqchol, class_cov, gauss_factor, mahsq_chol,
+       Lwplsrda, LwplsLda, LwplsQda, LwplsrS, LwplsrdaS, lwplsrda, lwplslda, lwplsqda, lwplsr_s, lwplsrda_s, knn_gda
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -2660,6 +2661,148 @@ function mahsqchol(X, Y, Uinv = nothing; ctx = default_ctx())
         Uinv = f.Uinv
     end
     mahsq_chol(X, Y, ensure_mat(Uinv); ctx = ctx)
+end
+
+# ---- local PLS discrimination and the LWPLS models on global scores (src/lwplsrda.jl, src/lwplslda.jl, src/lwplsqda.jl, src/lwplsr_s.jl,
+# src/lwplsrda_s.jl through src/locwlv.jl; DESIGN.md §25): one jch_lwplsda_predict_prepared per predict.  NOT EXECUTED in the build image (no
+# Julia toolchain).
+"""`knn_gda(T, tq, cls_nb, nlev; kind = "lda", prior = "unif", nlv)` — jch_knn_gda on host arrays: the Gaussian discriminants of m neighbourhoods
+for all the nested score spaces 1:a, a in nlv, from one factorisation per covariance.  T: a_hi x k x m (the C layout [m][k][a_hi]), tq: a_hi x m,
+cls_nb: k x m codes in 1:nlev.  Returns (post nlev x le x m, code le x m (1-based; 0 where info is 2), info le x m)."""
+function knn_gda(T, tq, cls_nb, nlev; kind = "lda", prior = "unif", nlv = nothing, ctx = default_ctx())
+    kind in ("lda", "qda") || throw(ArgumentError("kind must be \"lda\" or \"qda\""))
+    prior in ("unif", "prop") || throw(ArgumentError("prior must be \"unif\" or \"prop\""))
+    Tm = Array{Float64, 3}(T); qm = Matrix{Float64}(tq); c0 = Matrix{Int32}(cls_nb .- 1)
+    a_hi, k, m = size(Tm)
+    (size(qm) == (a_hi, m) && size(c0) == (k, m)) || throw(DimensionMismatch("knn_gda: T, tq and cls_nb do not fit"))
+    rng = nlv === nothing ? (a_hi:a_hi) : (minimum(nlv):maximum(nlv))
+    (first(rng) >= 1 && last(rng) <= a_hi) || throw(ArgumentError("nlv must lie in 1:$a_hi"))
+    le = length(rng)
+    post = zeros(nlev, le, m); code = zeros(Int32, le, m); info = zeros(Int32, le, m)
+    GC.@preserve Tm qm c0 post code info begin
+        check(ctx, ccall((:jch_knn_gda, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Int32, Int32, Int32, Int32, Int32, Ptr{Float64},
+                          Ptr{Int32}, Ptr{Int32}),
+                         ctx.h, Int32(0), pointer(Tm), m, Int32(k), Int32(a_hi), pointer(qm), pointer(c0), Int32(nlev), Int32(kind == "lda" ? 1 : 2),
+                         Int32(prior == "unif" ? 0 : 1), Int32(first(rng)), Int32(last(rng)), pointer(post), pointer(code), pointer(info)))
+    end
+    (post = post, code = Int.(code) .+ 1, info = Int.(info))
+end
+
+struct Lwplsrda                   # src/lwplsrda.jl:1-14
+    X; y; fm; metric::String; h::Real; k::Int; nlv::Int; tol::Real; scal::Bool; verbose::Bool; lev; ni
+end
+struct LwplsLda                   # src/lwplslda.jl:1-15
+    X; y; fm; metric::String; h::Real; k::Int; nlv::Int; prior::String; tol::Real; scal::Bool; verbose::Bool; lev; ni
+end
+struct LwplsQda                   # src/lwplsqda.jl:1-15
+    X; y; fm; metric::String; h::Real; k::Int; nlv::Int; prior::String; tol::Real; scal::Bool; verbose::Bool; lev; ni
+end
+struct LwplsrS                    # src/lwplsr_s.jl:1-12
+    T; Y; fm; metric::String; h::Real; k::Int; nlv::Int; tol::Real; scal::Bool; verbose::Bool
+end
+struct LwplsrdaS                  # src/lwplsrda_s.jl:1-12
+    T; y; fm; metric::String; h::Real; k::Int; nlv::Int; tol::Real; scal::Bool; verbose::Bool
+end
+function _lwda_fit(X, y, nlvdis, metric, h, k, scal, ctx)
+    _lw_check(metric, h, k)
+    X = _in(X); yv = vec(Array(y)); dm = dummy(yv)
+    size(X, 1) == length(yv) || throw(DimensionMismatch("X has $(size(X, 1)) rows, y has $(length(yv))"))
+    fm = nlvdis == 0 ? nothing : plskern(X, _colocate_mat(dm.Y, X); nlv = nlvdis, scal = scal, ctx = ctx)   # src/lwplsrda.jl:89
+    X, fm, dm.lev, [count(==(l), yv) for l in dm.lev]
+end
+"`lwplsrda(X, y; nlvdis, metric, h, k, nlv, tol = 1e-4, scal = false, verbose = false)` — src/lwplsrda.jl:81-94."
+function lwplsrda(X, y; nlvdis, metric, h, k, nlv, tol = 1e-4, scal = false, verbose = false, ctx = default_ctx())
+    X, fm, lev, ni = _lwda_fit(X, y, nlvdis, metric, h, k, scal, ctx)
+    Lwplsrda(X, ensure_mat(y), fm, metric, h, k, nlv, tol, scal, verbose, lev, ni)
+end
+"`lwplslda(X, y; nlvdis, metric, h, k, nlv, prior = \"unif\", tol = 1e-4, scal = false, verbose = false)` — src/lwplslda.jl:84-97."
+function lwplslda(X, y; nlvdis, metric, h, k, nlv, prior = "unif", tol = 1e-4, scal = false, verbose = false, ctx = default_ctx())
+    prior in ("unif", "prop") || throw(ArgumentError("prior must be \"unif\" or \"prop\""))
+    X, fm, lev, ni = _lwda_fit(X, y, nlvdis, metric, h, k, scal, ctx)
+    LwplsLda(X, ensure_mat(y), fm, metric, h, k, nlv, prior, tol, scal, verbose, lev, ni)
+end
+"`lwplsqda(X, y; nlvdis, metric, h, k, nlv, prior = \"unif\", tol = 1e-4, scal = false, verbose = false)` — src/lwplsqda.jl:89-102."
+function lwplsqda(X, y; nlvdis, metric, h, k, nlv, prior = "unif", tol = 1e-4, scal = false, verbose = false, ctx = default_ctx())
+    prior in ("unif", "prop") || throw(ArgumentError("prior must be \"unif\" or \"prop\""))
+    X, fm, lev, ni = _lwda_fit(X, y, nlvdis, metric, h, k, scal, ctx)
+    LwplsQda(X, ensure_mat(y), fm, metric, h, k, nlv, prior, tol, scal, verbose, lev, ni)
+end
+"""`lwplsr_s(X, Y; nlv0, reduc = "pls", metric = "eucl", h, k, gamma = 1, psamp = 1, samp = "sys", nlv, tol = 1e-4, scal = false, verbose = false)` —
+src/lwplsr_s.jl:115-141: kNN-LWPLSR on the n x nlv0 score table of a global reduction, nlv = min(nlv0, nlv)."""
+function lwplsr_s(X, Y; nlv0, reduc = "pls", metric = "eucl", h, k, gamma = 1, psamp = 1, samp = "sys", nlv, tol = 1e-4, scal = false, verbose = false,
+                  seed = nothing, ctx = default_ctx())
+    _lw_check(metric, h, k)
+    samp in ("sys", "random") || throw(ArgumentError("samp must be \"sys\" or \"random\""))
+    X = _in(X); Y = _in(Y); n = size(X, 1)
+    ms = Int64(round(psamp * n))
+    s = ms >= n ? nothing : (samp == "sys" ? sampsys(vec(sum(Array(Y); dims = 2)); k = ms).train : randperm(MersenneTwister(seed), n)[1:ms])
+    fm, T = _lw_reduce(X, Y, nothing, s, nlv0, reduc, gamma, scal, ctx)
+    LwplsrS(T, Y, fm, metric, h, k, min(nlv0, nlv), tol, scal, verbose)
+end
+"""`lwplsrda_s(X, y; nlv0, reduc = "pls", metric = "eucl", h, k, gamma = 1, psamp = 1, samp = "cla", nlv, tol = 1e-4, scal = false, verbose = false)` —
+src/lwplsrda_s.jl:77-105."""
+function lwplsrda_s(X, y; nlv0, reduc = "pls", metric = "eucl", h, k, gamma = 1, psamp = 1, samp = "cla", nlv, tol = 1e-4, scal = false, verbose = false,
+                    seed = nothing, ctx = default_ctx())
+    _lw_check(metric, h, k)
+    samp in ("cla", "random") || throw(ArgumentError("samp must be \"cla\" or \"random\""))
+    X = _in(X); yv = vec(Array(y)); n = size(X, 1)
+    ms = Int64(round(psamp * n))
+    nlev = length(unique(yv))
+    s = ms >= n ? nothing : (samp == "cla" ? sampcla(yv; k = max(Int64(round(ms / nlev)), 1), seed = seed).train : randperm(MersenneTwister(seed), n)[1:ms])
+    Yd = reduc == "dkpls" ? _colocate_mat(dummy(yv).Y, X) : nothing
+    fm, T = _lw_reduce(X, Yd, yv, s, nlv0, reduc, gamma, scal, ctx)
+    LwplsrdaS(T, ensure_mat(y), fm, metric, h, k, min(nlv0, nlv), tol, scal, verbose)
+end
+# the engine: an Lwplsr record on the dummy table, prepared, then one call for search, weights, local fits and discriminants
+function _lwda_predict(object, coords, fm, Q, nlv, kind, prior, ctx, who)
+    yv = vec(Array(object.y)); dm = dummy(yv); nlev = length(dm.lev)
+    cls = Vector{Int32}([searchsortedfirst(dm.lev, v) - 1 for v in yv])
+    Q = _in(Q); m = size(Q, 1); n, p = size(coords)
+    a = object.nlv
+    rng = nlv === nothing ? (a:a) : (max(minimum(nlv), 0):min(maximum(nlv), a, p))
+    (kind == 0 || first(rng) >= 1) || throw(ArgumentError("$who: a Gaussian discriminant needs at least one score column (nlv = 0 requested)"))
+    eng = Lwplsr(coords, _colocate_mat(dm.Y, coords), fm, object.metric, object.h, object.k, object.nlv, object.tol, object.scal, false)
+    pm = prepare(eng; ctx = ctx)
+    Zq = pm.device_map ? Q : _colocate_mat(pm.qmap(Q), Q)
+    cl = _colocate_vec(cls, Q)
+    k = min(object.k, n); le = length(rng)
+    code = zeros(Int32, le, m); info = zeros(Int32, le, m); post = zeros(nlev, le, m); ind = zeros(Int32, k, m); dist = zeros(k, m); w = zeros(k, m)
+    GC.@preserve Zq Q cl code info post ind dist w begin
+        check(ctx, ccall((:jch_lwplsda_predict_prepared, LIB), Int32,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, Int32, Int32, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int32, Float64,
+                          Float64, Int32, Int32, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64},
+                          Ptr{Float64}),
+                         ctx.h, pm.h, pointer(cl), Int32(nlev), Int32(kind), Int32(prior == "unif" ? 0 : 1), _loc(Q),
+                         pm.device_map ? Ptr{Float64}(C_NULL) : pointer(Zq), stride(Zq, 2), pointer(Q), m, stride(Q, 2), Int32(k), Float64(object.h),
+                         Float64(object.tol), Int32(object.scal ? 1 : 0), Int32(first(rng)), Int32(last(rng)), pointer(code), pointer(post), pointer(info),
+                         Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), pointer(ind), pointer(dist), pointer(w)))
+    end
+    release!(pm)
+    nbad = count(i -> any(==(2), info[:, i]), 1:m)
+    nbad > 0 && @warn "$who: $nbad of $m neighbourhoods have a covariance that is not positive definite; their labels are the weighted vote"
+    object.verbose && println(join(1:m, " "))
+    preds = [reshape(dm.lev[Int.(code[i, :]) .+ 1], :, 1) for i in 1:le]
+    posts = [permutedims(post[:, i, :]) for i in 1:le]
+    (pred = le == 1 ? preds[1] : preds, listnn = [Int.(ind[:, i]) .+ 1 for i in 1:m], listd = [dist[:, i] for i in 1:m], listw = [w[:, i] for i in 1:m],
+     posterior = le == 1 ? posts[1] : posts, info = permutedims(Int.(info)))
+end
+_colocate_vec(v::Vector{Int32}, like::Array) = v
+_colocate_vec(v::Vector{Int32}, like) = copyto!(similar(like, Int32, length(v)), v)
+"`predict(object::Lwplsrda, X; nlv)` — src/lwplsrda.jl:102-131."
+predict(object::Lwplsrda, X; nlv = nothing, ctx = default_ctx()) = _lwda_predict(object, object.X, object.fm, X, nlv, 0, "unif", ctx, "predict(::Lwplsrda)")
+"`predict(object::LwplsLda, X; nlv)` — src/lwplslda.jl:105-134."
+predict(object::LwplsLda, X; nlv = nothing, ctx = default_ctx()) = _lwda_predict(object, object.X, object.fm, X, nlv, 1, object.prior, ctx, "predict(::LwplsLda)")
+"`predict(object::LwplsQda, X; nlv)` — src/lwplsqda.jl:110-139."
+predict(object::LwplsQda, X; nlv = nothing, ctx = default_ctx()) = _lwda_predict(object, object.X, object.fm, X, nlv, 2, object.prior, ctx, "predict(::LwplsQda)")
+"`predict(object::LwplsrS, X; nlv)` — src/lwplsr_s.jl:149-178: `lwplsr` on the score table."
+function predict(object::LwplsrS, X; nlv = nothing, ctx = default_ctx())
+    eng = Lwplsr(object.T, object.Y, nothing, object.metric, object.h, object.k, object.nlv, object.tol, object.scal, object.verbose)
+    _predict_lwplsr(eng, _lw_transform(object.fm, _in(X), ctx), nlv, ctx)
+end
+"`predict(object::LwplsrdaS, X; nlv)` — src/lwplsrda_s.jl:113-142."
+function predict(object::LwplsrdaS, X; nlv = nothing, ctx = default_ctx())
+    _lwda_predict(object, object.T, nothing, _lw_transform(object.fm, _in(X), ctx), nlv, 0, "unif", ctx, "predict(::LwplsrdaS)")
 end
 
 end # module
