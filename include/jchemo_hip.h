@@ -316,6 +316,37 @@ JCH_API int32_t jch_score_sums_lv(jch_ctx *ctx, int32_t loc, const double *T, in
                                   const double *ymeans, const double *yscales, const double *Y, int64_t q, int64_t ldy, const double *mask,
                                   int32_t nlv_lo, int32_t nlv_hi, double *sums);
 
+/* ---- permutation importance: what the reference's `viperm` evaluates per replication (src/viperm.jl:89-107) -- DESIGN.md §26.  Both entries
+ * serve one rank only (a communicator of more ranks: JCH_EINVAL), Float64 only, and end synchronised with the ctx stream.
+ * jch_perm_fill -- perm (m x ncols int32, column-major, ld ldperm >= m, [loc]): column j = pi_j(0 .. m - 1), the permutation of 0 .. m - 1 for
+ *   (seed, j).  Counter-based: pi_j(i) is a function of (seed, j, m, i) alone.  1 <= m < 2^31; m = 1 gives 0.  With all arithmetic modulo 2^64,
+ *     mix64(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)   (the splitmix64 finaliser
+ *       of jch_fill_uniform); G = 0x9E3779B97F4A7C15; key_j = mix64(seed + (j + 1) G);
+ *     b = the smallest even number >= 2 with 2^b >= m, h = b / 2; rounds = 24 when b <= 12, else 8;
+ *     one walk of v < 2^b: L = v >> h, R = v & (2^h - 1); for r = 1 .. rounds: (L, R) <- (R, L ^ (mix64((key_j + r G) ^ R) >> (64 - h)));
+ *       v <- (L << h) | R;
+ *     pi_j(i) = the first of walk(i), walk(walk(i)), ... that is < m (cycle walking: a balanced Feistel network is a permutation of [0, 2^b)).
+ * jch_perm_score_sums -- for a model that predicts as int + X B: the six sums of jch_score_sums for the p predictions in which ONE column of the
+ *   held-out block was shuffled, from one read of the held-out rows of X and the unshuffled predictions.  With r = rows (m entries, int64,
+ *   0-based, [loc]; NULL = the rows 0 .. m - 1, m <= n) and pi_j = column j of perm (m x p int32, ld ldperm, [loc]; NULL = generated from `seed`
+ *   exactly as jch_perm_fill would), for j < p:
+ *       e[i, k] = y[r_i, k] - (pred[r_i, k] + (x[r_pi_j(i), j] - x[r_i, j]) * B[j, k]),
+ *   sums[(j q + k) 6 + 0..5] = { sum e, sum e^2, sum y e, sum y, sum y^2, m } over i < m; row j = p holds the unshuffled sums (the difference taken
+ *   as 0), from the same code in the same summation order: a column whose row of B is zero gives that row's bits, and an importance of exactly 0.
+ *   X n x p (ld ldx), Pred and Y n x q (ld ldp, ldy; indexed by the same row numbers as X) [loc], read only; B p x q (ld ldb) HOST, in the
+ *   units of the raw X (`coef(fm).B`); sums (p + 1) x q x 6 HOST.  Any n, m, p, q >= 1 (m < 2^31, (p + 1) q <= 2^27).  Rows not listed are
+ *   never read.  The residual is formed per element; fixed-order sums, no floating-point atomics: the same call gives the same bits, and so do a
+ *   host and a device X, an aligned and an unaligned X, and an explicit perm equal to the generated one.  No guards beyond IEEE: a non-finite
+ *   value in column j makes the sums of row j non-finite and touches no other row.  An entry of rows outside 0 .. n - 1 or of perm outside
+ *   0 .. m - 1 is JCH_EINVAL: host lists are checked before any device work, device lists inside the pass (the index is not followed, `sums` is
+ *   left untouched).  That a column of perm IS a permutation is the caller's promise.  loc JCH_LOC_DEVICE: the call enqueues on the ctx stream
+ *   and synchronises once, for the download of the sums.  The workspace is the ctx's own (the X copy a fit left for JCH_REUSE_XCOPY is not
+ *   touched). */
+JCH_API int32_t jch_perm_fill(jch_ctx *ctx, int32_t loc, int32_t *perm, int64_t m, int64_t ncols, int64_t ldperm, uint64_t seed);
+JCH_API int32_t jch_perm_score_sums(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const int64_t *rows, int64_t m,
+                                    const double *Pred, int64_t ldp, const double *Y, int64_t q, int64_t ldy, const double *B, int64_t ldb,
+                                    const int32_t *perm, int64_t ldperm, uint64_t seed, double *sums);
+
 /* ---- direct kernel PLS (src/dkplsr.jl:1-163): plskern on a Gram matrix built on the device -------------------------------
  * Kernel kinds: JCH_KERN_RBF = `krbf(X, Y; gamma)` = exp(-gamma * euclsq(X, Y)) (src/kernels.jl:26-30, euclsq src/distances.jl:24-28:
  * expanded norms clamped at 0; here on rows shifted by the column means of the second argument, which leaves the distances unchanged

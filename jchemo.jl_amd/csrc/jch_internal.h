@@ -100,6 +100,7 @@ struct jch_ctx {
     jch_buf kn_ws;   // knn.hip: the search's lists ahead of the drop of `self`, the results of a host call, the sort buffers and class accumulators of shapes beyond the LDS
     jch_buf kd_ws;   // kde.hip: the bandwidth factors, class offsets and model dimensions of a call, the per-split partial sums, the staging of a host call
     jch_buf gd_ws;   // gda.hip: per entry, the vectors, one or two p x p matrices, the padded transposed factors and the staging of a host call
+    jch_buf vp_ws;   // viperm.hip: B, the slice partials, the sums and the range flag of a permutation pass; the staging of a host call
     const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
     int64_t chol_n = 0, chol_ld = 0;
     // profiling

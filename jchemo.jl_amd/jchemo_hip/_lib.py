@@ -39,6 +39,7 @@ SYMBOLS = (
     "jch_kde_dens", "jch_knn_wls",
     "jch_class_cov", "jch_gauss_factor", "jch_mahsq_chol",
     "jch_knn_gda", "jch_lwplsda_predict_prepared",
+    "jch_perm_fill", "jch_perm_score_sums",
 )
 
 
@@ -155,6 +156,8 @@ def load():
     L.jch_mahsq_chol.argtypes = [vp, i32, dp, i64, i64, i64, dp, i32, dp, i64, i64, i32, dp, i64]
     L.jch_knn_gda.argtypes = [vp, i32, dp, i64, i32, i32, dp, dp, i32, i32, i32, i32, i32, dp, dp, dp]
     L.jch_lwplsda_predict_prepared.argtypes = [vp, vp, dp, i32, i32, i32, i32, dp, i64, dp, i64, i64, i32, f64, f64, i32, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp]
+    L.jch_perm_fill.argtypes = [vp, i32, dp, i64, i64, i64, C.c_uint64]
+    L.jch_perm_score_sums.argtypes = [vp, i32, dp, i64, i64, i64, dp, i64, dp, i64, dp, i64, i64, dp, i64, dp, i64, C.c_uint64, dp]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]
     L.jch_ctx_set_profiling.argtypes = [vp, i32]
     L.jch_ctx_synchronize.argtypes = [vp]

@@ -44,7 +44,8 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        Dmkern, Kernda, dmkern, kdeda, plskdeda, kde_dens,
        Lwmlr, LwmlrS, Lwmlrda, LwmlrdaS, lwmlr, lwmlr_s, lwmlrda, lwmlrda_s, knn_wls,
        Dmnorm, Lda, Qda, dmnorm, lda, qda, matW, matB, mahsqchol, class_cov, gauss_factor, mahsq_chol,
-       Lwplsrda, LwplsLda, LwplsQda, LwplsrS, LwplsrdaS, lwplsrda, lwplslda, lwplsqda, lwplsr_s, lwplsrda_s, knn_gda
+       Lwplsrda, LwplsLda, LwplsQda, LwplsrS, LwplsrdaS, lwplsrda, lwplslda, lwplsqda, lwplsr_s, lwplsrda_s, knn_gda,
+       viperm, isel, perm_fill, perm_score_sums
 
 const LIB = get(ENV, "JCHEMO_HIP_LIB", joinpath(@__DIR__, "..", "lib", "libjchemo_hip.so"))
 
@@ -2803,6 +2804,152 @@ end
 "`predict(object::LwplsrdaS, X; nlv)` — src/lwplsrda_s.jl:113-142."
 function predict(object::LwplsrdaS, X; nlv = nothing, ctx = default_ctx())
     _lwda_predict(object, object.T, nothing, _lw_transform(object.fm, _in(X), ctx), nlv, 0, "unif", ctx, "predict(::LwplsrdaS)")
+end
+
+# ---- permutation importance and interval selection (src/viperm.jl, src/isel.jl) over jch_perm_fill / jch_perm_score_sums and jch_score_sums
+# (include/jchemo_hip.h; DESIGN.md §26).  Row and column numbers are 1-based here; the C ABI, and the values of a permutation matrix, are
+# 0-based.  NOT EXECUTED in the build image (no Julia toolchain).
+_colocate_int(v::Array, like::Array) = v
+_colocate_int(v::Array, like) = copyto!(similar(like, eltype(v), size(v)...), v)
+
+"`perm_fill(m, ncols, seed)` — jch_perm_fill: m x ncols Int32 on the host, column j the permutation of 0 .. m - 1 for (seed, j - 1)."
+function perm_fill(m::Integer, ncols::Integer, seed::Integer; ctx = default_ctx())
+    (1 <= m < 2^31 && ncols >= 1) || throw(ArgumentError("perm_fill: 1 <= m < 2^31 and ncols >= 1"))
+    perm = zeros(Int32, m, ncols)
+    GC.@preserve perm check(ctx, ccall((:jch_perm_fill, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Int64, Int64, Int64, UInt64),
+        ctx.h, Int32(0), pointer(perm), m, ncols, m, UInt64(seed)))
+    perm
+end
+
+"""`perm_score_sums(X, Pred, Y, B; rows = nothing, perm = nothing, seed = 0)` — jch_perm_score_sums: 6 x q x (p + 1), [stat, response, column];
+column j <= p holds the sums for the prediction in which column j of the held-out block was shuffled, column p + 1 the unshuffled ones.
+`rows`: 1-based held-out rows (nothing: all rows); `perm`: m x p with 0-based values as `perm_fill` gives them (nothing: generated from `seed`)."""
+function perm_score_sums(X, Pred, Y, B; rows = nothing, perm = nothing, seed = 0, ctx = default_ctx())
+    X = _in(X); Pred = _colocate_mat(_in(Pred), X); Y = _colocate_mat(_in(Y), X)
+    n, p = size(X); q = size(Y, 2)
+    (size(Pred) == (n, q) && size(Y, 1) == n) || throw(DimensionMismatch("X is $n x $p, Pred $(size(Pred)), Y $(size(Y))"))
+    Bm = Matrix{Float64}(ensure_mat(B))
+    size(Bm) == (p, q) || throw(DimensionMismatch("B is $(size(Bm)), expected ($p, $q)"))
+    rows0 = rows === nothing ? nothing : _colocate_int(Vector{Int64}(vec(Array(rows)) .- 1), X)
+    m = rows0 === nothing ? n : length(rows0)
+    perm0 = perm === nothing ? nothing : _colocate_int(Matrix{Int32}(Array(perm)), X)
+    (perm0 === nothing || size(perm0) == (m, p)) || throw(DimensionMismatch("perm is $(size(perm0)), expected ($m, $p)"))
+    sums = zeros(6, q, p + 1)
+    GC.@preserve X Pred Y Bm rows0 perm0 check(ctx, ccall((:jch_perm_score_sums, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+         Ptr{Int32}, Int64, UInt64, Ptr{Float64}),
+        ctx.h, _loc(X), pointer(X), n, p, stride(X, 2), rows0 === nothing ? Ptr{Int64}(C_NULL) : pointer(rows0), m, pointer(Pred), max(stride(Pred, 2), n),
+        pointer(Y), q, max(stride(Y, 2), n), pointer(Bm), p, perm0 === nothing ? Ptr{Int32}(C_NULL) : pointer(perm0), m, UInt64(seed), sums))
+    sums
+end
+
+# per replication (held-out rows, 64-bit permutation seed) from one stream; `s` pins the rows
+function _vi_splits(n, nval, nrep, seed, s)
+    (1 <= nval < n) || throw(ArgumentError("psamp leaves $nval of $n rows for the test set"))
+    (s === nothing || length(s) == nrep) || throw(ArgumentError("s has $(length(s)) index vectors for $nrep replications"))
+    rng = seed === nothing ? Random.default_rng() : MersenneTwister(seed)
+    pseeds = rand(rng, UInt64, nrep)                        # the seeds first: pinning the rows leaves them what they were
+    map(1:nrep) do i
+        rows = s === nothing ? sort(randperm(rng, n)[1:nval]) : Vector{Int64}(vec(s[i]))
+        (rows, pseeds[i])
+    end
+end
+_vi_reuse(fun) = fun === plskern || fun === plsnipals || fun === plssimp || fun === plsrosa || fun === plswold
+_vi_weights(fun) = _vi_reuse(fun) || fun === pcr
+_vi_fast(fun) = _vi_weights(fun) || fun === covselr
+function _vi_full_B(fm, p)
+    B = Matrix{Float64}(coef(fm).B)
+    hasproperty(fm, :sel) || return B
+    full = zeros(p, size(B, 2)); full[fm.sel.sel, :] .= B
+    full
+end
+
+"""
+    viperm(X, Y; perm = 50, psamp = 1/3, score = rmsep, fun, seed = nothing, s = nothing, kwargs...)
+
+src/viperm.jl:74-110.  Returns `(imp = p x q, res = p x q x perm)`.  `seed` seeds the stream the held-out rows and one 64-bit permutation
+seed per replication are drawn from; `s`, a vector of `perm` index vectors, pins the rows.  Where `fun` is one of `plskern, plsnipals,
+plssimp, plsrosa, plswold, pcr, covselr` and `score` one of `msep, rmsep, ssr, bias, r2, cor2`, a replication is one fit with weight 0 on the
+held-out rows (X is never copied; `covselr` gets gathered rows), one `predict` over X and one jch_perm_score_sums.  Anything else runs the
+reference's loop, on the same permutations.
+"""
+function viperm(X, Y; perm = 50, psamp = 1/3, score = rmsep, fun, seed = nothing, s = nothing, ctx = default_ctx(), kwargs...)
+    X = _in(X); Y = _colocate_mat(_in(Y), X); n, p = size(X); q = size(Y, 2)
+    nval = Int64(round(psamp * n))
+    splits = _vi_splits(n, nval, perm, seed, s)
+    fast = score isa ScoreFun && _vi_fast(fun)
+    res = zeros(p, q, perm)
+    _same_x[] = Int32(0)
+    for (i, (rows, pseed)) in enumerate(splits)
+        keep = setdiff(1:n, rows)
+        if fast
+            fm = if _vi_weights(fun)
+                w = ones(n); w[rows] .= 0.0
+                try fun(X, Y, w; kwargs...) catch; _same_x[] = Int32(0); rethrow() end
+            else
+                fun(X[keep, :], Y[keep, :]; kwargs...)
+            end
+            _vi_reuse(fun) && (_same_x[] = Int32(8))        # the later fits of this call see the same X (JCH_REUSE_XCOPY)
+            S = perm_score_sums(X, predict(fm, X).pred, Y, _vi_full_B(fm, p); rows = rows, seed = pseed, ctx = ctx)
+            res[:, :, i] .= _score_from_sums(score.name, S[:, :, 1:p]) .- _score_from_sums(score.name, S[:, :, (p + 1):(p + 1)])
+        else
+            Xval = X[rows, :]; Yval = Y[rows, :]
+            fm = fun(X[keep, :], Y[keep, :]; kwargs...)
+            score0 = vec(collect(score(predict(fm, Xval).pred, Yval)))
+            zs = perm_fill(length(rows), p, pseed; ctx = ctx)
+            for j in 1:p
+                col = Xval[:, j]
+                Xval[:, j] .= col[Int.(zs[:, j]) .+ 1]
+                res[j, :, i] .= vec(collect(score(predict(fm, Xval).pred, Yval))) .- score0
+                Xval[:, j] .= col
+            end
+        end
+    end
+    _same_x[] = Int32(0)
+    (imp = reshape(sum(res; dims = 3) ./ perm, p, q), res = res)
+end
+
+"""
+    isel(X, Y, wl = 1:nco(X); rep = 1, nint = 5, psamp = 1/3, score = rmsep, fun, seed = nothing, s = nothing, kwargs...)
+
+src/isel.jl:76-129.  Returns `(res, res0, res_rep, res0_rep, int)` with the reference's columns `lo, up, mid, y1 ... yq`.  The split works as
+in `viperm`.  Where `fun` takes weights and `score` is a named one, an interval is a view of the column-major X (same leading dimension, no
+copy) fitted with weight 0 on the held-out rows and scored from jch_score_sums with the held-out mask.
+"""
+function isel(X, Y, wl = 1:size(ensure_mat(X), 2); rep = 1, nint = 5, psamp = 1/3, score = rmsep, fun, seed = nothing, s = nothing, ctx = default_ctx(), kwargs...)
+    X = _in(X); Y = _colocate_mat(_in(Y), X); n, p = size(X); q = size(Y, 2)
+    nint = Int64(nint)
+    z = collect(round.(range(1, p + 1; length = nint + 1)))
+    int = [z[1:nint] z[2:(nint + 1)] .- 1]
+    int = Int64.(hcat(int, round.(sum(int; dims = 2) ./ 2)))
+    nval = Int64(round(psamp * n))
+    splits = _vi_splits(n, nval, rep, seed, s)
+    masked = score isa ScoreFun && _vi_weights(fun)
+    res_rep = zeros(nint, q, rep); res0_rep = zeros(1, q, rep)
+    for (i, (rows, _)) in enumerate(splits)
+        keep = setdiff(1:n, rows)
+        held = zeros(n); held[rows] .= 1.0
+        w = 1.0 .- held
+        Xcal = masked ? nothing : X[keep, :]; Ycal = masked ? nothing : Y[keep, :]
+        Xval = masked ? nothing : X[rows, :]; Yval = masked ? nothing : Y[rows, :]
+        function one(u)
+            if masked
+                Xu = view(X, :, u)
+                fm = fun(Xu, Y, w; kwargs...)
+                return _score_from_sums(score.name, _score_sums(predict(fm, Xu).pred, Y, held, ctx))[1:1, :]
+            end
+            fm = fun(Xcal[:, u], Ycal; kwargs...)
+            reshape(collect(score(predict(fm, Xval[:, u]).pred, Yval)), 1, :)
+        end
+        res0_rep[:, :, i] .= one(1:p)
+        for j in 1:nint
+            res_rep[j:j, :, i] .= one(int[j, 1]:int[j, 2])
+        end
+    end
+    dat = (lo = wl[int[:, 1]], up = wl[int[:, 2]], mid = wl[int[:, 3]])
+    zres = sum(res_rep; dims = 3)[:, :, 1] ./ rep; zres0 = sum(res0_rep; dims = 3)[:, :, 1] ./ rep
+    ycols(A) = NamedTuple{_ynames(q)}(Tuple(A[:, k] for k in 1:q))
+    (res = _table(merge(dat, ycols(zres))), res0 = _table(ycols(zres0)), res_rep = res_rep, res0_rep = res0_rep, int = int)
 end
 
 end # module
