@@ -237,7 +237,7 @@ extern "C" int32_t jch_gauss_factor(jch_ctx *ctx, int32_t loc, const double *S, 
     const bool host = loc == JCH_LOC_HOST;
     const size_t pp = (size_t)p * (size_t)p;
     jch_carve cv;
-    const size_t o_a = cv.take(pp), o_w = cv.take(host ? pp : 0), o_d = cv.take((size_t)p * (size_t)nfac), o_i = cv.take(((size_t)nfac + 1) / 2);
+    const size_t o_a = cv.take(pp), o_w = cv.take(host ? pp : 0), o_d = cv.take((size_t)p * (size_t)nfac), o_i = cv.take(jch_ints_as_doubles((size_t)nfac));
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     JCH_TRY(jch_reserve(ctx, ctx->gd_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->gd_ws.ptr;

@@ -143,6 +143,7 @@ struct jch_carve {
     size_t off = 0;
     size_t take(size_t count) { const size_t o = off; off += (count + 31) & ~(size_t)31; return o; }
 };
+inline size_t jch_ints_as_doubles(size_t count) { return (count + 1) / 2; }   // doubles that hold `count` ints: what an int array takes of a carve
 
 // ---- error plumbing --------------------------------------------------------------------------------
 int32_t jch_fail(jch_ctx *ctx, int32_t code, const char *fmt, ...);

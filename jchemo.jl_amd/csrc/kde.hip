@@ -241,7 +241,7 @@ extern "C" int32_t jch_kde_dens(jch_ctx *ctx, int32_t loc, const double *Z, int6
     const bool host = loc == JCH_LOC_HOST;
     // ---- one reservation: class offsets | dims | u | v2 | coef by output column | partials | the staging of a host call
     jch_carve cv;
-    const size_t o_cs = cv.take((size_t)ncls + 1), o_dm = cv.take(((size_t)nmod + 1) / 2), o_u = cv.take((size_t)d * ncls), o_v = cv.take((size_t)ncm),
+    const size_t o_cs = cv.take((size_t)ncls + 1), o_dm = cv.take(jch_ints_as_doubles((size_t)nmod)), o_u = cv.take((size_t)d * ncls), o_v = cv.take((size_t)ncm),
                  o_cf = cv.take((size_t)ncm);
     const size_t n_small = cv.off;
     const size_t o_pt = cv.take((size_t)m * (size_t)ncm * (size_t)nsplit);

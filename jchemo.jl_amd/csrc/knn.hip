@@ -107,10 +107,6 @@ __global__ __launch_bounds__(256) void k_knn_wmean(const double *__restrict__ Y,
     }
 }
 
-// a beats b as a class score: a NaN beats a number (Julia's `argmax`), else the larger one
-__device__ __forceinline__ bool knn_vote_better(double a, double b) { return (a != a && b == b) || a > b; }
-__device__ __forceinline__ bool knn_vote_same(double a, double b) { return a == b || (a != a && b != b); }
-
 __global__ __launch_bounds__(256) void k_knn_vote(const int *__restrict__ cls, int64_t n, int ncls, const int *__restrict__ ind, const double *__restrict__ w,
                                                   int m, int k, int *__restrict__ pred, double *__restrict__ score, double *gacc, int *gcnt)
 {
@@ -238,8 +234,6 @@ extern "C" int32_t jch_knn_release(jch_ctx *ctx, jch_knn_model *model)
     return JCH_OK;
 }
 
-static size_t ints_as_doubles(size_t count) { return (count + 1) / 2; }
-
 extern "C" int32_t jch_knn_search(jch_ctx *ctx, const jch_knn_model *model, int32_t loc, const double *Zq, int64_t m, int64_t ldzq, int32_t k,
                                   const int64_t *self, double h, double tol, int32_t out_loc, int32_t *ind, double *dist, double *w, double *dmed)
 {
@@ -261,9 +255,9 @@ extern "C" int32_t jch_knn_search(jch_ctx *ctx, const jch_knn_model *model, int3
     // ---- one reservation: staged inputs | the search's lists | the results of a host call | sort scratch beyond the LDS
     jch_carve cv;
     const size_t o_zq = hin ? cv.take((size_t)m * dd) : 0, o_self = (hin && self) ? cv.take((size_t)m) : 0;
-    const size_t o_ad = cv.take(mk1), o_aw = cv.take(mk1), o_ai = cv.take(ints_as_doubles(mk1));
+    const size_t o_ad = cv.take(mk1), o_aw = cv.take(mk1), o_ai = cv.take(jch_ints_as_doubles(mk1));
     const bool bres = post && hout;
-    const size_t o_bd = bres ? cv.take(mk) : 0, o_bw = bres ? cv.take(mk) : 0, o_bi = bres ? cv.take(ints_as_doubles(mk)) : 0, o_bm = bres ? cv.take((size_t)m) : 0;
+    const size_t o_bd = bres ? cv.take(mk) : 0, o_bw = bres ? cv.take(mk) : 0, o_bi = bres ? cv.take(jch_ints_as_doubles(mk)) : 0, o_bm = bres ? cv.take((size_t)m) : 0;
     const bool big = post && k > KNN_CAP;
     const size_t o_sc = big ? cv.take((size_t)post_blocks * 2 * (size_t)k) : 0;
     JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
@@ -279,10 +273,7 @@ extern "C" int32_t jch_knn_search(jch_ctx *ctx, const jch_knn_model *model, int3
             dself = (const int64_t *)(ws + o_self);
         }
         int *sflags = nullptr;
-        knn_args a;
-        a.Zt = model->Zt; a.ldzt = n; a.n = n; a.Zq = dZq; a.ldzq = ldq; a.m = (int)m; a.dd = (int)dd; a.k = k1;
-        a.h = h; a.cri = 4.0; a.tol = tol;
-        a.ind = (int *)(ws + o_ai); a.dist = ws + o_ad; a.w = ws + o_aw;
+        knn_args a = jch_knn_make_args(model->Zt, n, dd, dZq, ldq, m, k1, h, tol, (int *)(ws + o_ai), ws + o_ad, ws + o_aw);
         if (!self && !hout) {   // no removal behind the search: it writes the caller's device arrays itself
             if (ind) a.ind = ind;
             if (dist) a.dist = dist;
@@ -348,7 +339,7 @@ extern "C" int32_t jch_knn_wmean(jch_ctx *ctx, int32_t loc, const double *Y, int
     const size_t mk = (size_t)m * k;
     const bool host = loc == JCH_LOC_HOST;
     jch_carve cv;
-    const size_t o_y = host ? cv.take((size_t)n * q) : 0, o_i = host ? cv.take(ints_as_doubles(mk)) : 0, o_w = host ? cv.take(mk) : 0, o_p = host ? cv.take((size_t)m * q) : 0;
+    const size_t o_y = host ? cv.take((size_t)n * q) : 0, o_i = host ? cv.take(jch_ints_as_doubles(mk)) : 0, o_w = host ? cv.take(mk) : 0, o_p = host ? cv.take((size_t)m * q) : 0;
     if (host) JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kn_ws.ptr;
     return jch_synced(ctx, host, [&]() -> int32_t {
@@ -382,9 +373,9 @@ extern "C" int32_t jch_knn_vote(jch_ctx *ctx, int32_t loc, const int32_t *cls, i
     // beyond the LDS: one accumulator row per workgroup, within 1 GiB
     const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, (int64_t)ctx->cus * 8), glob ? ((int64_t)1 << 30) / (12 * (int64_t)ncls) : m));
     jch_carve cv;
-    const size_t o_c = host ? cv.take(ints_as_doubles((size_t)n)) : 0, o_i = host ? cv.take(ints_as_doubles(mk)) : 0, o_w = host ? cv.take(mk) : 0;
-    const size_t o_p = host ? cv.take(ints_as_doubles((size_t)m)) : 0, o_s = (host && score) ? cv.take((size_t)m * ncls) : 0;
-    const size_t o_ga = glob ? cv.take((size_t)nb * ncls) : 0, o_gc = glob ? cv.take(ints_as_doubles((size_t)nb * ncls)) : 0;
+    const size_t o_c = host ? cv.take(jch_ints_as_doubles((size_t)n)) : 0, o_i = host ? cv.take(jch_ints_as_doubles(mk)) : 0, o_w = host ? cv.take(mk) : 0;
+    const size_t o_p = host ? cv.take(jch_ints_as_doubles((size_t)m)) : 0, o_s = (host && score) ? cv.take((size_t)m * ncls) : 0;
+    const size_t o_ga = glob ? cv.take((size_t)nb * ncls) : 0, o_gc = glob ? cv.take(jch_ints_as_doubles((size_t)nb * ncls)) : 0;
     if (cv.off) JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kn_ws.ptr;
     return jch_synced(ctx, host, [&]() -> int32_t {
@@ -420,8 +411,8 @@ extern "C" int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double
     while (cap < k) cap <<= 1;
     const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, (int64_t)ctx->cus * 8), glob ? ((int64_t)1 << 30) / (12 * (int64_t)cap) : m));
     jch_carve cv;
-    const size_t o_v = host ? cv.take((size_t)n) : 0, o_i = host ? cv.take(ints_as_doubles(mk)) : 0, o_o = host ? cv.take((size_t)m) : 0;
-    const size_t o_gk = glob ? cv.take((size_t)nb * cap) : 0, o_gi = glob ? cv.take(ints_as_doubles((size_t)nb * cap)) : 0;
+    const size_t o_v = host ? cv.take((size_t)n) : 0, o_i = host ? cv.take(jch_ints_as_doubles(mk)) : 0, o_o = host ? cv.take((size_t)m) : 0;
+    const size_t o_gk = glob ? cv.take((size_t)nb * cap) : 0, o_gi = glob ? cv.take(jch_ints_as_doubles((size_t)nb * cap)) : 0;
     if (cv.off) JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kn_ws.ptr;
     return jch_synced(ctx, host, [&]() -> int32_t {

@@ -79,9 +79,6 @@ __global__ __launch_bounds__(256) void k_wls_rowmajor(const double *__restrict__
     }
 }
 
-template <bool LDS> __device__ __forceinline__ void wls_bsync() { if (!LDS) __threadfence_block(); __syncthreads(); }
-template <bool LDS> __device__ __forceinline__ void wls_wsync() { if (!LDS) __threadfence_block(); knn_wavesync(); }
-
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_knn_wls(wls_args g)
 {
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(256) void k_knn_wls(wls_args g)
     for (int qi = blockIdx.x; qi < g.m; qi += gridDim.x) {
         const int *ii = g.ind + (size_t)qi * k;
         const double *ww = g.w + (size_t)qi * k;
-        wls_bsync<LDS>();                                      // (the previous query is done with the slab)
+        slab_bsync<LDS>();                                      // (the previous query is done with the slab)
         // ---- 1. the weights
         double s = 0.0;
         for (int e = lane; e < k; e += 64) s += ww[e];
@@ -113,14 +110,14 @@ __global__ __launch_bounds__(256) void k_knn_wls(wls_args g)
             wt[e] = wn;
             sq[e] = sqrt(wn);
         }
-        wls_bsync<LDS>();
+        slab_bsync<LDS>();
         // ---- 2. the gather: G lanes per row, 4 * per rows at a time
         for (int j = wv * per + sub; j < k; j += 4 * per) {
             const int r = rows[j];
             const double *src = g.XY + (size_t)(r < 0 ? 0 : r) * (size_t)g.ldr;
             for (int c = c0; c < nc; c += G) S[(size_t)c * L + j] = r >= 0 ? src[c] : nan;
         }
-        wls_bsync<LDS>();
+        slab_bsync<LDS>();
         // ---- 3. the shortcuts (block-uniform)
         if (q == 1) {                                          // src/locw.jl:33-34
             const double *yc = S + (size_t)d * L;
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(256) void k_knn_wls(wls_args g)
                 if (c < d) dx[c] = g.Xq[(size_t)qi + (size_t)c * (size_t)g.ldq] - mu;
             }
         }
-        wls_bsync<LDS>();
+        slab_bsync<LDS>();
         // ---- 5. Householder QR of A, applied to the columns behind it and to B
         double rmax = 0.0, rmin = __builtin_inf();
         for (int j = 0; j < d; ++j) {
@@ -171,7 +168,7 @@ __global__ __launch_bounds__(256) void k_knn_wls(wls_args g)
                     for (int i = j + lane; i < k; i += 64) col[i] -= f * (i == j ? v1 : vj[i]);
                 }
             }
-            wls_bsync<LDS>();
+            slab_bsync<LDS>();
         }
         // ---- 6. the rank test, then per response one wave: back substitution and the prediction
         if (rmin <= (double)min(k, d) * 0x1p-52 * rmax) { fail_row(qi, 1); continue; }
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(256) void k_knn_wls(wls_args g)
                 acc += dx[j] * bj;
                 const double *rj = S + (size_t)j * L;
                 for (int i = lane; i < j; i += 64) b[i] -= rj[i] * bj;
-                wls_wsync<LDS>();
+                slab_wsync<LDS>();
             }
             if (lane == 0) g.pred[(size_t)qi + (size_t)c * (size_t)g.m] = mean[d + c] + acc;
         }
@@ -191,7 +188,6 @@ __global__ __launch_bounds__(256) void k_knn_wls(wls_args g)
     }
 }
 
-static size_t wls_ints_as_doubles(size_t count) { return (count + 1) / 2; }
 
 extern "C" int32_t jch_knn_wls(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t d, int64_t ldx, const double *Y, int64_t q, int64_t ldy,
                                const double *Xq, int64_t m, int64_t ldq, const int32_t *ind, const double *w, int32_t k, double *pred, int32_t *info)
@@ -205,16 +201,12 @@ extern "C" int32_t jch_knn_wls(jch_ctx *ctx, int32_t loc, const double *X, int64
     const size_t mk = (size_t)m * k, nc = (size_t)(d + q);
     const bool host = loc == JCH_LOC_HOST;
     const size_t slab = wls_slab_doubles(k, d, q);
-    const bool glob = slab * sizeof(double) > WLS_LDS_MAX;
-    // workgroups: what the LDS lets a CU hold (at most 8 of 256 threads); beyond the LDS one slab per workgroup within 1 GiB
-    int64_t nb;
-    if (glob) nb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, (int64_t)ctx->cus * 4), (int64_t)(((size_t)1 << 30) / (slab * sizeof(double)))));
-    else nb = std::min<int64_t>(m, (int64_t)ctx->cus * std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / (int64_t)(slab * sizeof(double)))));
+    const jch_slab_where at = jch_slab_plan(ctx, m, slab, WLS_LDS_MAX, false);
     jch_carve cv;
     const size_t o_x = host ? cv.take((size_t)n * d) : 0, o_y = host ? cv.take((size_t)n * q) : 0, o_q = host ? cv.take((size_t)m * d) : 0;
-    const size_t o_i = host ? cv.take(wls_ints_as_doubles(mk)) : 0, o_w = host ? cv.take(mk) : 0, o_p = host ? cv.take((size_t)m * q) : 0;
-    const size_t o_f = (host && info) ? cv.take(wls_ints_as_doubles((size_t)m)) : 0;
-    const size_t o_xy = cv.take((size_t)n * nc), o_sc = glob ? cv.take((size_t)nb * slab) : 0;
+    const size_t o_i = host ? cv.take(jch_ints_as_doubles(mk)) : 0, o_w = host ? cv.take(mk) : 0, o_p = host ? cv.take((size_t)m * q) : 0;
+    const size_t o_f = (host && info) ? cv.take(jch_ints_as_doubles((size_t)m)) : 0;
+    const size_t o_xy = cv.take((size_t)n * nc), o_sc = at.glob ? cv.take((size_t)at.nb * slab) : 0;
     JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off));
     double *ws = (double *)ctx->kn_ws.ptr;
     return jch_synced(ctx, host, [&]() -> int32_t {
@@ -240,17 +232,8 @@ extern "C" int32_t jch_knn_wls(jch_ctx *ctx, int32_t loc, const double *X, int64
         a.gshift = 0;
         while (a.gshift < 6 && ((size_t)1 << a.gshift) < nc) ++a.gshift;
         a.pred = dp; a.info = df;
-        a.scratch = glob ? ws + o_sc : nullptr; a.per_block = slab;
-        if (glob) hipLaunchKernelGGL(k_knn_wls<false>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a);
-        else {
-            static jch_per_device_once attr;
-            if (!attr.done(ctx->device)) {
-                JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_knn_wls<true>, hipFuncAttributeMaxDynamicSharedMemorySize, WLS_LDS_MAX));
-                attr.mark(ctx->device);
-            }
-            hipLaunchKernelGGL(k_knn_wls<true>, dim3((unsigned)nb), dim3(256), slab * sizeof(double), ctx->stream, a);
-        }
-        JCH_HIP(ctx, hipGetLastError());
+        a.scratch = at.glob ? ws + o_sc : nullptr; a.per_block = slab;
+        JCH_TRY((jch_launch_slab<k_knn_wls<true>, k_knn_wls<false>>(ctx, at, slab, WLS_LDS_MAX, a)));
         if (host) {
             JCH_HIP(ctx, hipMemcpyAsync(pred, dp, sizeof(double) * (size_t)m * q, hipMemcpyDeviceToHost, ctx->stream));
             if (info) JCH_HIP(ctx, hipMemcpyAsync(info, df, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));

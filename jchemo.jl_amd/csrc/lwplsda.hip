@@ -41,9 +41,6 @@ size_t jch_knn_gda_slab_doubles(int64_t k, int64_t a, int64_t nlev)
     return (size_t)k * a + (size_t)a * ld + 2 * (size_t)a + ((size_t)nlev + 1) * a + 4 * (size_t)a + (size_t)a + ((size_t)nlev + (size_t)k + 1) / 2 + 2;
 }
 
-template <bool LDS> __device__ __forceinline__ void gda_bsync() { if (!LDS) __threadfence_block(); __syncthreads(); }
-template <bool LDS> __device__ __forceinline__ void gda_wsync() { if (!LDS) __threadfence_block(); knn_wavesync(); }
-
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_knn_gda(gda_args g)
 {
@@ -63,7 +60,7 @@ __global__ __launch_bounds__(256) void k_knn_gda(gda_args g)
     for (int qi = blockIdx.x; qi < g.m; qi += gridDim.x) {
         double *post = g.post + (size_t)qi * le * nlev;
         int *code = g.code + (size_t)qi * le, *info = g.info + (size_t)qi * le;
-        gda_bsync<LDS>();                                      // (the previous query is done with the slab)
+        slab_bsync<LDS>();                                      // (the previous query is done with the slab)
         // ---- 1. the slab
         for (int e = tid; e < k; e += 256) { const int c = g.cls[(size_t)qi * k + e]; cl[e] = (c >= 0 && c < nlev) ? c : -1; }
         {
@@ -77,13 +74,9 @@ __global__ __launch_bounds__(256) void k_knn_gda(gda_args g)
             }
         }
         for (int j = tid; j < a; j += 256) tqv[j] = g.tq[(size_t)qi * g.ldq + j];
-        gda_bsync<LDS>();
-        for (int c = tid; c < nlev; c += 256) {
-            int n = 0;
-            for (int e = 0; e < k; ++e) n += cl[e] == c ? 1 : 0;
-            cnt[c] = n;
-        }
-        gda_bsync<LDS>();
+        slab_bsync<LDS>();
+        knn_class_counts(cl, k, nlev, cnt);
+        slab_bsync<LDS>();
         int nloc = 0, n1 = 0, first = -1, nvalid = 0;          // (every thread the same walk: block-uniform)
         for (int c = 0; c < nlev; ++c) {
             const int n = cnt[c];
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(256) void k_knn_gda(gda_args g)
                     if (all || cl[e] == c) s += Tl[(size_t)e * a + j];
             mu[it] = cn > 0 ? s / (double)cn : 0.0;
         }
-        gda_bsync<LDS>();
+        slab_bsync<LDS>();
         // ---- 3. the factors
         const double *mug = mu + (size_t)nlev * a;
         int jfmin = a;                                         // the first pivot (0-based) that was not positive, over the factors
@@ -145,7 +138,7 @@ __global__ __launch_bounds__(256) void k_knn_gda(gda_args g)
                 Lm[(size_t)i * ld + j] = s;
                 if (i == j) sd[i] = s;
             }
-            gda_bsync<LDS>();
+            slab_bsync<LDS>();
             int jfail = a;
             for (int j = 0; j < a; ++j) {
                 for (int i = j + tid; i < a; i += 256) {
@@ -158,11 +151,11 @@ __global__ __launch_bounds__(256) void k_knn_gda(gda_args g)
                         dg[j] = ok ? sqrt(s) : (s != s ? s : 0.0);   // (a NaN pivot stays a NaN: non-finite scores, not a rank deficiency)
                     } else Lm[(size_t)i * ld + j] = s;
                 }
-                gda_bsync<LDS>();
+                slab_bsync<LDS>();
                 const double r = dg[j];
                 if (!(r > 0.0)) { jfail = j; if (r != r) jnan = min(jnan, j); break; }   // (block-uniform: every thread reads the same dg[j])
                 for (int i = j + 1 + tid; i < a; i += 256) Lm[(size_t)i * ld + j] /= r;
-                gda_bsync<LDS>();
+                slab_bsync<LDS>();
             }
             jfmin = min(jfmin, jfail);
             // per class under this factor one wave: z = L^-1 (tq - mu_c), then prefix sums of z^2 and prefix products of the diagonal
@@ -170,13 +163,13 @@ __global__ __launch_bounds__(256) void k_knn_gda(gda_args g)
                 if (cnt[c] == 0) continue;                     // (wave-uniform)
                 double *z = zb + (size_t)wv * a;
                 for (int j = lane; j < a; j += 64) z[j] = tqv[j] - mu[(size_t)c * a + j];
-                gda_wsync<LDS>();
+                slab_wsync<LDS>();
                 const double wprior = g.prior == 0 ? 1.0 / (double)nloc : (double)cnt[c] / (double)k;
                 double d2 = 0.0, pd = 1.0;
                 for (int j = 0; j < jfail; ++j) {
                     const double zj = z[j] / dg[j];
                     for (int i = j + 1 + lane; i < jfail; i += 64) z[i] -= Lm[(size_t)i * ld + j] * zj;
-                    gda_wsync<LDS>();
+                    slab_wsync<LDS>();
                     d2 += zj * zj;
                     pd *= dg[j];
                     const int am = j + 1;                      // the model on the first am score columns; requests beyond a clamp to a
@@ -206,49 +199,32 @@ __global__ __launch_bounds__(256) void k_knn_gda(gda_args g)
             int bad = 0;
             for (int c = 0; c < nlev; ++c)
                 if (cnt[c] > 0) { const double v = pt[c]; s += v; bad |= (v - v == 0.0) ? 0 : 1; }
-            int best = first;
+            int best = -1;                                     // (two local levels at least: one is taken)
             double bv = 0.0;
-            bool have = false, bnan = false;
             for (int c = 0; c < nlev; ++c) {
                 if (cnt[c] == 0) { pt[c] = 0.0; continue; }
                 const double v = pt[c] / s;
                 pt[c] = v;
-                // the first maximum over the local levels, a NaN counting as the largest value (Julia's argmax)
-                if (!have) { best = c; bv = v; have = true; bnan = v != v; }
-                else if (!bnan && (v != v || v > bv)) { best = c; bv = v; bnan = v != v; }
+                if (best < 0 || knn_vote_better(v, bv)) { best = c; bv = v; }   // the label rule (lwplsr_dev.h)
             }
             code[t] = best; info[t] = bad ? 3 : 0;
         }
     }
 }
 
-// the slab of this shape lives in the workspace (true) or in LDS (false); nb: the workgroups of the launch
-bool jch_knn_gda_plan(jch_ctx *ctx, int64_t m, int64_t k, int64_t a, int64_t nlev, int64_t *nb, size_t *slab)
+// *slab: the doubles of this shape's slab; where it lives and the workgroups of the launch: jch_slab_plan (JCH_GDA_WS=1: the workspace path at any shape — tests)
+jch_slab_where jch_knn_gda_plan(jch_ctx *ctx, int64_t m, int64_t k, int64_t a, int64_t nlev, size_t *slab)
 {
     *slab = (jch_knn_gda_slab_doubles(k, a, nlev) + 31) & ~(size_t)31;
-    const bool glob = *slab * sizeof(double) > GDA_LDS_MAX || jch_knob("JCH_GDA_WS", 0) == 1;   // JCH_GDA_WS=1: the workspace path at any shape (tests)
-    if (glob) *nb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, (int64_t)ctx->cus * 4), (int64_t)(((size_t)1 << 30) / (*slab * sizeof(double)))));
-    else *nb = std::min<int64_t>(m, (int64_t)ctx->cus * std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / (int64_t)(*slab * sizeof(double)))));
-    return glob;
+    return jch_slab_plan(ctx, m, *slab, GDA_LDS_MAX, jch_knob("JCH_GDA_WS", 0) == 1);
 }
 
 // g: all pointers on the device; g.scratch: null (LDS) or nb slabs of g.per_block doubles, as jch_knn_gda_plan said
 int32_t jch_launch_knn_gda(jch_ctx *ctx, const gda_args &g, int64_t nb)
 {
-    if (g.scratch) hipLaunchKernelGGL(k_knn_gda<false>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, g);
-    else {
-        static jch_per_device_once attr;
-        if (!attr.done(ctx->device)) {
-            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_knn_gda<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GDA_LDS_MAX));
-            attr.mark(ctx->device);
-        }
-        hipLaunchKernelGGL(k_knn_gda<true>, dim3((unsigned)nb), dim3(256), g.per_block * sizeof(double), ctx->stream, g);
-    }
-    JCH_HIP(ctx, hipGetLastError());
-    return JCH_OK;
+    return jch_launch_slab<k_knn_gda<true>, k_knn_gda<false>>(ctx, {g.scratch != nullptr, nb}, g.per_block, GDA_LDS_MAX, g);
 }
 
-static size_t gda_ints_as_doubles(size_t count) { return (count + 1) / 2; }
 
 extern "C" int32_t jch_knn_gda(jch_ctx *ctx, int32_t loc, const double *T, int64_t m, int32_t k, int32_t a_hi, const double *tq, const int32_t *cls_nb,
                                int32_t nlev, int32_t kind, int32_t prior, int32_t nlv_lo, int32_t nlv_hi, double *post, int32_t *code, int32_t *info)
@@ -265,12 +241,11 @@ extern "C" int32_t jch_knn_gda(jch_ctx *ctx, int32_t loc, const double *T, int64
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const bool host = loc == JCH_LOC_HOST;
     const size_t le = (size_t)(nlv_hi - nlv_lo + 1), nt = (size_t)m * k * a_hi, nq = (size_t)m * a_hi, nc = (size_t)m * k, np = (size_t)m * le * nlev, ni = (size_t)m * le;
-    int64_t nb = 0;
     size_t slab = 0;
-    const bool glob = jch_knn_gda_plan(ctx, m, k, nlv_hi, nlev, &nb, &slab);
+    const jch_slab_where at = jch_knn_gda_plan(ctx, m, k, nlv_hi, nlev, &slab);
     jch_carve cv;
-    const size_t o_t = host ? cv.take(nt) : 0, o_q = host ? cv.take(nq) : 0, o_c = host ? cv.take(gda_ints_as_doubles(nc)) : 0, o_p = host ? cv.take(np) : 0;
-    const size_t o_k = host ? cv.take(gda_ints_as_doubles(ni)) : 0, o_f = host ? cv.take(gda_ints_as_doubles(ni)) : 0, o_sc = glob ? cv.take((size_t)nb * slab) : 0;
+    const size_t o_t = host ? cv.take(nt) : 0, o_q = host ? cv.take(nq) : 0, o_c = host ? cv.take(jch_ints_as_doubles(nc)) : 0, o_p = host ? cv.take(np) : 0;
+    const size_t o_k = host ? cv.take(jch_ints_as_doubles(ni)) : 0, o_f = host ? cv.take(jch_ints_as_doubles(ni)) : 0, o_sc = at.glob ? cv.take((size_t)at.nb * slab) : 0;
     JCH_TRY(jch_reserve(ctx, ctx->kn_ws, sizeof(double) * cv.off + 256));
     double *ws = (double *)ctx->kn_ws.ptr;
     return jch_synced(ctx, host, [&]() -> int32_t {
@@ -284,8 +259,8 @@ extern "C" int32_t jch_knn_gda(jch_ctx *ctx, int32_t loc, const double *T, int64
         }
         // the factor spans the first nlv_hi score columns: the columns behind them are never read
         g.tstride = (int64_t)k * a_hi; g.ldt = a_hi; g.ldq = a_hi; g.m = (int)m; g.k = k; g.a = nlv_hi; g.nlev = nlev; g.kind = kind; g.prior = prior;
-        g.nlv_lo = nlv_lo; g.nlv_hi = nlv_hi; g.scratch = glob ? ws + o_sc : nullptr; g.per_block = slab;
-        JCH_TRY(jch_launch_knn_gda(ctx, g, nb));
+        g.nlv_lo = nlv_lo; g.nlv_hi = nlv_hi; g.scratch = at.glob ? ws + o_sc : nullptr; g.per_block = slab;
+        JCH_TRY(jch_launch_knn_gda(ctx, g, at.nb));
         if (host) {
             JCH_HIP(ctx, hipMemcpyAsync(post, g.post, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream));
             JCH_HIP(ctx, hipMemcpyAsync(code, g.code, sizeof(int) * ni, hipMemcpyDeviceToHost, ctx->stream));
@@ -312,11 +287,7 @@ __global__ __launch_bounds__(256) void k_rda_finish(const double *__restrict__ p
     for (int qi = blockIdx.x; qi < m; qi += gridDim.x) {
         __syncthreads();
         const int *cn = cls_nb + (size_t)qi * k;
-        for (int c = tid; c < nlev; c += 256) {
-            int n = 0;
-            for (int e = 0; e < k; ++e) n += cn[e] == c ? 1 : 0;
-            rda_cnt[c] = n;
-        }
+        knn_class_counts(cn, k, nlev, rda_cnt);
         __syncthreads();
         const double *pq = pred + (size_t)qi * le * nlev;
         double *po = post + (size_t)qi * le * nlev;
@@ -329,14 +300,12 @@ __global__ __launch_bounds__(256) void k_rda_finish(const double *__restrict__ p
         for (int t = tid; t < le; t += 256) {
             int best = -1, bad = 0;
             double bv = 0.0;
-            bool bnan = false;
             for (int c = 0; c < nlev; ++c) {
                 const double v = pq[(size_t)t * nlev + c];
                 po[(size_t)t * nlev + c] = v;
                 if (rda_cnt[c] == 0) continue;
                 bad |= (v - v == 0.0) ? 0 : 1;
-                if (best < 0) { best = c; bv = v; bnan = v != v; }
-                else if (!bnan && (v != v || v > bv)) { best = c; bv = v; bnan = v != v; }
+                if (best < 0 || knn_vote_better(v, bv)) { best = c; bv = v; }
             }
             code[(size_t)qi * le + t] = best;
             info[(size_t)qi * le + t] = bad ? 3 : 0;
@@ -351,7 +320,6 @@ __global__ __launch_bounds__(256) void k_da_vote_fill(const int *__restrict__ in
         if (info[e] == 2) code[e] = vote[e / le];
 }
 
-static size_t lw_ints_as_doubles(size_t count) { return (count + 1) / 2; }
 
 extern "C" int32_t jch_lwplsda_predict_prepared(jch_ctx *ctx, const jch_lwplsr_model *model, const int32_t *cls_train, int32_t nlev, int32_t kind, int32_t prior,
                                                 int32_t loc, const double *Zq, int64_t ldzq, const double *Xq, int64_t m, int64_t ldxq, int32_t k, double h,
@@ -364,9 +332,7 @@ extern "C" int32_t jch_lwplsda_predict_prepared(jch_ctx *ctx, const jch_lwplsr_m
     if (kind < 0 || kind > 2) return jch_fail(ctx, JCH_EINVAL, "%s: kind must be 0 (rda), 1 (lda) or 2 (qda), not %d", who, kind);
     if (prior != 0 && prior != 1) return jch_fail(ctx, JCH_EINVAL, "%s: prior must be 0 (unif) or 1 (prop), not %d", who, prior);
     if (nlev < 1 || nlev != model->q) return jch_fail(ctx, JCH_EINVAL, "%s: the model's Ytrain must be the n x nlev dummy table (it has %lld columns, nlev = %d)", who, (long long)model->q, nlev);
-    if (!Zq && (model->qmaps.empty() || model->qmaps.back().k_out != model->dd))
-        return jch_fail(ctx, JCH_EINVAL, "%s: Zq is NULL and the model has no query map ending in %lld columns (jch_lwplsr_add_query_map)", who, (long long)model->dd);
-    if (model->device != ctx->device) return jch_fail(ctx, JCH_EINVAL, "%s: the model lives on device %d, the ctx on %d", who, model->device, ctx->device);
+    JCH_TRY(jch_lw_front_check(ctx, who, model, Zq));
     if (m < 1 || k < 1 || nlv_lo < 0 || nlv_hi < nlv_lo || m >= ((int64_t)1 << 31) - 1) return jch_fail(ctx, JCH_EINVAL, "%s: bad arguments", who);
     if (k > model->n) k = (int32_t)model->n;                      // src/getknn.jl:33
     if (kind != 0 && nlv_lo < 1) return jch_fail(ctx, JCH_EINVAL, "%s: a Gaussian discriminant needs at least one score column (nlv_lo = %d)", who, nlv_lo);
@@ -383,18 +349,16 @@ extern "C" int32_t jch_lwplsda_predict_prepared(jch_ctx *ctx, const jch_lwplsr_m
     const bool generic = !jch_locw_pspace_fits(g) || jch_knob("JCH_LOCW_GENERIC", 0) == 1;
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     const bool host = loc == JCH_LOC_HOST;
-    if (host) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * dd + (size_t)m * p)));
     const size_t mk = (size_t)m * k, ntl = mk * (size_t)std::max(nlv_hi, 1), ntq = (size_t)m * std::max(nlv_hi, 1), np = (size_t)m * le * nlev, nm = (size_t)m * le;
     // the local model's LVs: what k_locw_plskern fits, and what jch_plskern_fit reports back on the per-query route (min(k, p, nlv) there too), so
     // the score columns beyond a_fit are the zeros of both routes and the models beyond a_fit clamp to it
     const int a_fit = std::min(std::min((int)k, (int)p), (int)nlv_hi);
-    int64_t nb = 0;
     size_t slab = 0;
-    const bool glob = kind != 0 && jch_knn_gda_plan(ctx, m, k, a_fit, nlev, &nb, &slab);
+    const jch_slab_where at = kind != 0 ? jch_knn_gda_plan(ctx, m, k, a_fit, nlev, &slab) : jch_slab_where{false, 0};
     jch_carve cv;
-    const size_t o_tl = cv.take(ntl), o_tq = cv.take(ntq), o_cn = cv.take(lw_ints_as_doubles(mk)), o_po = cv.take(np), o_co = cv.take(lw_ints_as_doubles(nm));
-    const size_t o_in = cv.take(lw_ints_as_doubles(nm)), o_i1 = cv.take(lw_ints_as_doubles((size_t)m)), o_vo = cv.take(lw_ints_as_doubles((size_t)m));
-    const size_t o_cl = host ? cv.take(lw_ints_as_doubles((size_t)n)) : 0, o_sc = glob ? cv.take((size_t)nb * slab) : 0;
+    const size_t o_tl = cv.take(ntl), o_tq = cv.take(ntq), o_cn = cv.take(jch_ints_as_doubles(mk)), o_po = cv.take(np), o_co = cv.take(jch_ints_as_doubles(nm));
+    const size_t o_in = cv.take(jch_ints_as_doubles(nm)), o_i1 = cv.take(jch_ints_as_doubles((size_t)m)), o_vo = cv.take(jch_ints_as_doubles((size_t)m));
+    const size_t o_cl = host ? cv.take(jch_ints_as_doubles((size_t)n)) : 0, o_sc = at.glob ? cv.take((size_t)at.nb * slab) : 0;
     JCH_TRY(jch_reserve(ctx, ctx->gd_ws, sizeof(double) * cv.off + 256));
     JCH_TRY(jch_reserve(ctx, ctx->gemm_out, sizeof(double) * (mk * 2 + np) + sizeof(int) * mk + 256));
     return jch_synced(ctx, true, [&]() -> int32_t {
@@ -403,46 +367,24 @@ extern "C" int32_t jch_lwplsda_predict_prepared(jch_ctx *ctx, const jch_lwplsr_m
         int *dcn = (int *)(ws + o_cn), *dcode = (int *)(ws + o_co), *dinfo = (int *)(ws + o_in), *dinfo1 = (int *)(ws + o_i1), *dvote = (int *)(ws + o_vo);
         double *ddist = (double *)ctx->gemm_out.ptr, *dw = ddist + mk, *dpred = dw + mk;
         int *dind = (int *)(dpred + np);
-        const double *dZq = Zq, *dXq = Xq;
         const int *dcls = cls_train;
-        int64_t ldzqd = ldzq, ldxqd = ldxq;
+        lw_queries qs{Zq, ldzq, Xq, ldxq};
+        JCH_TRY(jch_lw_front_stage(ctx, model, host, m, &qs));
         if (host) {
-            double *b = (double *)ctx->xq.ptr;
-            if (Zq) JCH_TRY(jch_stage_in(ctx, host, b, m, dd, &dZq, &ldzqd));
-            JCH_TRY(jch_stage_in(ctx, host, b + (size_t)m * dd, m, p, &dXq, &ldxqd));
             JCH_HIP(ctx, hipMemcpyAsync(ws + o_cl, cls_train, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
             dcls = (const int *)(ws + o_cl);
         }
-        ctx->ev_used = 0;
-        ctx->prof = jch_profile{};
-        if (!Zq) {   // the model's query map, as in jch_lwplsr_predict_prepared
-            size_t wmax = 0;
-            for (const auto &qm : model->qmaps) wmax = std::max(wmax, (size_t)qm.k_out);
-            JCH_TRY(jch_reserve(ctx, ctx->qz, sizeof(double) * 2 * (size_t)m * wmax));
-            double *zb[2] = {(double *)ctx->qz.ptr, (double *)ctx->qz.ptr + (size_t)m * wmax};
-            const double *src = dXq;
-            int64_t lds_ = ldxqd;
-            int w = 0;
-            for (const auto &qm : model->qmaps) {
-                JCH_TRY(jch_launch_affine_gemm(ctx, src, m, qm.p_in, lds_, qm.dB, qm.k_out, qm.kpad, qm.dB + (size_t)qm.p_in * qm.kpad, zb[w], m));
-                src = zb[w]; lds_ = m; w ^= 1;
-            }
-            dZq = src; ldzqd = m;
-        }
-        {
-            knn_args a;
-            a.Zt = model->Zt; a.ldzt = n; a.n = n; a.Zq = dZq; a.ldzq = ldzqd; a.m = (int)m; a.dd = (int)dd; a.k = k;
-            a.h = h; a.cri = 4.0; a.tol = tol; a.ind = dind; a.dist = ddist; a.w = dw;
-            int *sflags = nullptr;
-            JCH_TRY(jch_knn_dispatch(ctx, a, model->has_screen ? &model->screen : nullptr, &model->screen_off, &sflags));
-        }
+        if (!Zq) JCH_TRY(jch_lw_front_map(ctx, model, m, &qs));
+        int *sflags = nullptr;
+        JCH_TRY(jch_knn_dispatch(ctx, jch_knn_make_args(model->Zt, n, dd, qs.Zq, qs.ldzq, m, k, h, tol, dind, ddist, dw), model->has_screen ? &model->screen : nullptr,
+                                 &model->screen_off, &sflags));
         const unsigned gb = (unsigned)std::max<size_t>(1, std::min<size_t>((mk + 255) / 256, (size_t)ctx->cus * 8));
         hipLaunchKernelGGL(k_da_gather_cls, dim3(gb), dim3(256), 0, ctx->stream, dcls, dind, mk, dcn);
         // (a unanimous neighbourhood is not fitted: its scores and predictions stay the zeros written here)
         JCH_HIP(ctx, hipMemsetAsync(dtl, 0, sizeof(double) * ntl, ctx->stream));
         JCH_HIP(ctx, hipMemsetAsync(dtq, 0, sizeof(double) * ntq, ctx->stream));
         JCH_HIP(ctx, hipMemsetAsync(dpred, 0, sizeof(double) * np, ctx->stream));
-        g.Xq = dXq; g.ldxq = ldxqd; g.ind = dind; g.w = dw; g.pred = dpred; g.tloc = dtl; g.tqv = dtq; g.cls = dcls; g.info = dinfo1;
+        g.Xq = qs.Xq; g.ldxq = qs.ldxq; g.ind = dind; g.w = dw; g.pred = dpred; g.tloc = dtl; g.tqv = dtq; g.cls = dcls; g.info = dinfo1;
         if (generic) {
             std::vector<int> hcn(mk);
             JCH_HIP(ctx, hipMemcpyAsync(hcn.data(), dcn, sizeof(int) * mk, hipMemcpyDeviceToHost, ctx->stream));
@@ -456,8 +398,8 @@ extern "C" int32_t jch_lwplsda_predict_prepared(jch_ctx *ctx, const jch_lwplsr_m
             gda_args a;
             a.T = dtl; a.tstride = (int64_t)k * nlv_hi; a.ldt = nlv_hi; a.tq = dtq; a.ldq = nlv_hi; a.cls = dcn; a.m = (int)m; a.k = k; a.a = a_fit; a.nlev = nlev;
             a.kind = kind; a.prior = prior; a.nlv_lo = nlv_lo; a.nlv_hi = nlv_hi; a.post = dpost; a.code = dcode; a.info = dinfo;
-            a.scratch = glob ? ws + o_sc : nullptr; a.per_block = slab;
-            JCH_TRY(jch_launch_knn_gda(ctx, a, nb));
+            a.scratch = at.glob ? ws + o_sc : nullptr; a.per_block = slab;
+            JCH_TRY(jch_launch_knn_gda(ctx, a, at.nb));
             JCH_TRY(jch_knn_vote(ctx, JCH_LOC_DEVICE, dcls, n, nlev, dind, dw, m, k, dvote, nullptr));
             hipLaunchKernelGGL(k_da_vote_fill, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((nm + 255) / 256, (size_t)ctx->cus * 8))), dim3(256), 0, ctx->stream,
                                dinfo, dvote, (int)m, le, dcode);

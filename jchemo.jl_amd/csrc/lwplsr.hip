@@ -806,7 +806,7 @@ static bool locw_batched_fits(const locw_args &g)
     return jch_locw_kspace_feasible(g) || jch_locw_pspace_fits(g);
 }
 
-// the p-space kernel for this row width (the caller has checked jch_locw_pspace_fits: no k-space fallback is taken)
+// the p-space kernel for this row width (lwplsda.hip has checked jch_locw_pspace_fits: no k-space fallback is taken there)
 int32_t jch_launch_locw_pspace(jch_ctx *ctx, locw_args &g)
 {
     if (g.ldr <= 128) return launch_locw<1>(ctx, g);
@@ -926,9 +926,8 @@ static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64
     locw_args kargs{};
     int *sflags = nullptr;          // screened kNN: per-query "redone by the exact selection" flags (device; read back with the predictions)
     {
-        knn_args a;
-        a.Zt = dZt; a.ldzt = ldztd; a.n = n; a.Zq = dZq; a.ldzq = ldzqd; a.m = (int)m; a.dd = (int)dd; a.k = k;
-        a.h = h; a.cri = 4.0; a.tol = tol; a.ind = dind; a.dist = ddist; a.w = dw;
+        knn_args a = jch_knn_make_args(dZt, n, dd, dZq, ldzqd, m, k, h, tol, dind, ddist, dw);
+        a.ldzt = ldztd;
         JCH_TRY(jch_knn_dispatch(ctx, a, scr, screen_off, &sflags));
     }
     ev2 = jch_ev(ctx);
@@ -969,12 +968,7 @@ static int32_t lw_run(jch_ctx *ctx, const double *Xrm, int ldr, int64_t n, int64
             g.flags = (int *)ctx->lw_flags.ptr;
             JCH_TRY(jch_launch_locw_kspace(ctx, g));
             kflags = g.flags; kargs = g;
-        } else
-        if (ldr <= 128) JCH_TRY(launch_locw<1>(ctx, g));
-        else if (ldr <= 256) JCH_TRY(launch_locw<2>(ctx, g));
-        else if (ldr <= 512) JCH_TRY(launch_locw<4>(ctx, g));
-        else if (ldr <= 1024) JCH_TRY(launch_locw<8>(ctx, g));
-        else JCH_TRY(launch_locw<16>(ctx, g));
+        } else JCH_TRY(jch_launch_locw_pspace(ctx, g));
     }
     JCH_HIP(ctx, hipGetLastError());
     ev3 = generic_fits ? nullptr : jch_ev(ctx);
@@ -1188,48 +1182,65 @@ extern "C" int32_t jch_lwplsr_add_query_map(jch_ctx *ctx, jch_lwplsr_model *mode
     return JCH_OK;
 }
 
+// ---- the front end of a prediction on a prepared model (lwplsr_dev.h), for the entry below and jch_lwplsda_predict_prepared (lwplsda.hip)
+int32_t jch_lw_front_check(jch_ctx *ctx, const char *who, const jch_lwplsr_model *model, const double *Zq)
+{
+    if (!Zq && (model->qmaps.empty() || model->qmaps.back().k_out != model->dd))
+        return jch_fail(ctx, JCH_EINVAL, "%s: Zq is NULL and the model has no query map ending in %lld columns (jch_lwplsr_add_query_map)", who, (long long)model->dd);
+    if (model->device != ctx->device) return jch_fail(ctx, JCH_EINVAL, "%s: the model lives on device %d, the ctx on %d", who, model->device, ctx->device);
+    return JCH_OK;
+}
+
+int32_t jch_lw_front_stage(jch_ctx *ctx, const jch_lwplsr_model *model, bool host, int64_t m, lw_queries *q)
+{
+    if (host) {
+        const int64_t p = model->p, dd = model->dd;
+        JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * dd + (size_t)m * p)));
+        double *b = (double *)ctx->xq.ptr;
+        if (q->Zq) JCH_TRY(jch_stage_in(ctx, host, b, m, dd, &q->Zq, &q->ldzq));
+        JCH_TRY(jch_stage_in(ctx, host, b + (size_t)m * dd, m, p, &q->Xq, &q->ldxq));
+    }
+    ctx->ev_used = 0;
+    ctx->prof = jch_profile{};
+    return JCH_OK;
+}
+
+// Xq -> the neighbour-search space, stage by stage in two alternating device buffers
+int32_t jch_lw_front_map(jch_ctx *ctx, const jch_lwplsr_model *model, int64_t m, lw_queries *q)
+{
+    size_t wmax = 0;
+    for (const auto &qm : model->qmaps) wmax = std::max(wmax, (size_t)qm.k_out);
+    JCH_TRY(jch_reserve(ctx, ctx->qz, sizeof(double) * 2 * (size_t)m * wmax));
+    double *zb[2] = {(double *)ctx->qz.ptr, (double *)ctx->qz.ptr + (size_t)m * wmax};
+    const double *src = q->Xq;
+    int64_t lds_ = q->ldxq;
+    int w = 0;
+    for (const auto &qm : model->qmaps) {
+        JCH_TRY(jch_launch_affine_gemm(ctx, src, m, qm.p_in, lds_, qm.dB, qm.k_out, qm.kpad, qm.dB + (size_t)qm.p_in * qm.kpad, zb[w], m));
+        src = zb[w]; lds_ = m; w ^= 1;
+    }
+    q->Zq = src; q->ldzq = m;
+    return JCH_OK;
+}
+
 extern "C" int32_t jch_lwplsr_predict_prepared(jch_ctx *ctx, const jch_lwplsr_model *model, int32_t loc, const double *Zq, int64_t ldzq,
                                                const double *Xq, int64_t m, int64_t ldxq, int32_t k, double h, double tol, int32_t scal,
                                                int32_t nlv_lo, int32_t nlv_hi, double *pred, int32_t *ind_out, double *dist_out, double *w_out)
 {
     if (!ctx) return JCH_EINVAL;
-    if (!model || !Xq || !pred || ldxq < m || (Zq && ldzq < m)) return jch_fail(ctx, JCH_EINVAL, "jch_lwplsr_predict_prepared: bad arguments");
-    if (!Zq && (model->qmaps.empty() || model->qmaps.back().k_out != model->dd))
-        return jch_fail(ctx, JCH_EINVAL, "jch_lwplsr_predict_prepared: Zq is NULL and the model has no query map ending in %lld columns (jch_lwplsr_add_query_map)", (long long)model->dd);
-    if (model->device != ctx->device) return jch_fail(ctx, JCH_EINVAL, "jch_lwplsr_predict_prepared: the model lives on device %d, the ctx on %d", model->device, ctx->device);
-    JCH_TRY(lw_check(ctx, "jch_lwplsr_predict_prepared", model->n, model->p, model->q, model->dd, m, k, nlv_lo, nlv_hi));
-    if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "jch_lwplsr_predict_prepared: bad loc");
+    const char *who = "jch_lwplsr_predict_prepared";
+    if (!model || !Xq || !pred || ldxq < m || (Zq && ldzq < m)) return jch_fail(ctx, JCH_EINVAL, "%s: bad arguments", who);
+    JCH_TRY(jch_lw_front_check(ctx, who, model, Zq));
+    JCH_TRY(lw_check(ctx, who, model->n, model->p, model->q, model->dd, m, k, nlv_lo, nlv_hi));
+    if (loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) return jch_fail(ctx, JCH_EINVAL, "%s: bad loc", who);
     JCH_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t p = model->p, dd = model->dd;
-    const bool host = loc == JCH_LOC_HOST;
-    if (host) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * ((size_t)m * dd + (size_t)m * p)));
     return jch_synced_on_failure(ctx, true, [&]() -> int32_t {   // (lw_run ends synchronised)
-        const double *dZq = Zq, *dXq = Xq;
-        int64_t ldzqd = ldzq, ldxqd = ldxq;
-        if (host) {
-            double *b = (double *)ctx->xq.ptr;
-            if (Zq) JCH_TRY(jch_stage_in(ctx, host, b, m, dd, &dZq, &ldzqd));
-            JCH_TRY(jch_stage_in(ctx, host, b + (size_t)m * dd, m, p, &dXq, &ldxqd));
-        }
-        ctx->ev_used = 0;
-        ctx->prof = jch_profile{};
+        lw_queries qs{Zq, ldzq, Xq, ldxq};
+        JCH_TRY(jch_lw_front_stage(ctx, model, loc == JCH_LOC_HOST, m, &qs));
         hipEvent_t ev0 = jch_ev(ctx);
-        if (!Zq) {   // the model's query map: Xq -> the neighbour-search space, stage by stage in two alternating device buffers
-            size_t wmax = 0;
-            for (const auto &qm : model->qmaps) wmax = std::max(wmax, (size_t)qm.k_out);
-            JCH_TRY(jch_reserve(ctx, ctx->qz, sizeof(double) * 2 * (size_t)m * wmax));
-            double *zb[2] = {(double *)ctx->qz.ptr, (double *)ctx->qz.ptr + (size_t)m * wmax};
-            const double *src = dXq;
-            int64_t lds_ = ldxqd;
-            int w = 0;
-            for (const auto &qm : model->qmaps) {
-                JCH_TRY(jch_launch_affine_gemm(ctx, src, m, qm.p_in, lds_, qm.dB, qm.k_out, qm.kpad, qm.dB + (size_t)qm.p_in * qm.kpad, zb[w], m));
-                src = zb[w]; lds_ = m; w ^= 1;
-            }
-            dZq = src; ldzqd = m;
-        }
-        return lw_run(ctx, model->Xrm, model->ldr, model->n, p, model->Y, model->q, model->n, model->Zt, model->n, dZq, ldzqd, dd, dXq, m, ldxqd, k, h, tol,
-                      scal, nlv_lo, nlv_hi, pred, ind_out, dist_out, w_out, ev0, model->has_screen ? &model->screen : nullptr, &model->screen_off);
+        if (!Zq) JCH_TRY(jch_lw_front_map(ctx, model, m, &qs));
+        return lw_run(ctx, model->Xrm, model->ldr, model->n, model->p, model->Y, model->q, model->n, model->Zt, model->n, qs.Zq, qs.ldzq, model->dd, qs.Xq, m, qs.ldxq,
+                      k, h, tol, scal, nlv_lo, nlv_hi, pred, ind_out, dist_out, w_out, ev0, model->has_screen ? &model->screen : nullptr, &model->screen_off);
     });
 }
 

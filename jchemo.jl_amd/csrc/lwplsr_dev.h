@@ -1,6 +1,7 @@
 // Arguments shared by the batched local-fit kernels of the kNN-LWPLSR prediction path (lwplsr.hip: k_locw_plskern, the
 // p-space kernel; lwplsr_kspace.hip: k_locw_kspace, the Gram / k-space kernel) — src/locwlv.jl:9-48.
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "jch_internal.h"
@@ -46,6 +47,15 @@ struct knn_args {
     int *cidx;     // [m][nseg][k]
     const int *only_flags = nullptr;   // null, or [m] device flags — only the queries with a non-zero flag are done (k_knn_scan: only their groups of qb)
 };
+// the search of m queries (Zq, ld ldzq) among the n rows of Zt (ld n; a caller with another pitch sets ldzt), cri = 4 (src/wdist.jl:64); nseg, ckey, cidx: the scan's own
+inline knn_args jch_knn_make_args(const double *Zt, int64_t n, int64_t dd, const double *Zq, int64_t ldzq, int64_t m, int k, double h, double tol, int *ind,
+                                  double *dist, double *w)
+{
+    knn_args a{};
+    a.Zt = Zt; a.ldzt = n; a.n = n; a.Zq = Zq; a.ldzq = ldzq; a.m = (int)m; a.dd = (int)dd; a.k = k;
+    a.h = h; a.cri = 4.0; a.tol = tol; a.ind = ind; a.dist = dist; a.w = w;
+    return a;
+}
 
 // lwplsr_screen.hip: the screened kNN (round 4).  Squared distances of ALL (row, query) pairs on the matrix cores
 // (v_mfma_f32_32x32x16_bf16 on two-piece bf16, norm-augmented operands), an error-bounded bar per query from the k-th smallest GROUP minimum, exact
@@ -103,6 +113,27 @@ struct jch_lwplsr_model {
 // lwplsr.hip: the shape fits the p-space local-fit kernel (the one that can hand out its local scores), and its launch
 bool jch_locw_pspace_fits(const locw_args &g);
 int32_t jch_launch_locw_pspace(jch_ctx *ctx, locw_args &g);
+// lwplsr.hip: the front end of a prediction on a prepared model, for jch_lwplsr_predict_prepared and jch_lwplsda_predict_prepared (lwplsda.hip); who: the
+// entry's name in the messages.  _check: Zq or a query map that ends in the model's dd columns, and the model on the ctx's device — called among the
+// entry's own argument checks, so that every bad call keeps its message.  Then, inside the entry's jch_synced frame, _stage: the ctx->xq reservation and
+// the upload of a host call's Zq / Xq (q: the caller's pointers and pitches in, the device's out), the profile reset; _map (Zq null): Xq -> the
+// neighbour-search space, stage by stage in the two halves of ctx->qz.
+struct lw_queries { const double *Zq; int64_t ldzq; const double *Xq; int64_t ldxq; };
+int32_t jch_lw_front_check(jch_ctx *ctx, const char *who, const jch_lwplsr_model *model, const double *Zq);
+int32_t jch_lw_front_stage(jch_ctx *ctx, const jch_lwplsr_model *model, bool host, int64_t m, lw_queries *q);
+int32_t jch_lw_front_map(jch_ctx *ctx, const jch_lwplsr_model *model, int64_t m, lw_queries *q);
+
+// A per-query slab of slab_doubles doubles (k_knn_wls, lwmlr.hip; k_knn_gda, lwplsda.hip) lives in dynamic LDS or, beyond lds_max_bytes or with
+// force_workspace, in one piece per workgroup of a workspace (glob).  nb, the workgroups of the launch: what the LDS lets a CU hold (at most 8 of 256
+// threads); beyond the LDS four per CU, their slabs within 1 GiB
+struct jch_slab_where { bool glob; int64_t nb; };
+inline jch_slab_where jch_slab_plan(const jch_ctx *ctx, int64_t m, size_t slab_doubles, size_t lds_max_bytes, bool force_workspace)
+{
+    const size_t bytes = slab_doubles * sizeof(double);
+    if (bytes > lds_max_bytes || force_workspace)
+        return {true, std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, (int64_t)ctx->cus * 4), (int64_t)(((size_t)1 << 30) / bytes)))};
+    return {false, std::min<int64_t>(m, (int64_t)ctx->cus * std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / (int64_t)bytes)))};
+}
 
 // lwplsda.hip: the nested Gaussian discriminants of a neighbourhood (k_knn_gda); all pointers on the device
 struct gda_args {
@@ -115,13 +146,31 @@ struct gda_args {
     double *scratch; size_t per_block;           // null (LDS) or one slab of per_block doubles per workgroup
 };
 size_t jch_knn_gda_slab_doubles(int64_t k, int64_t a, int64_t nlev);
-bool jch_knn_gda_plan(jch_ctx *ctx, int64_t m, int64_t k, int64_t a, int64_t nlev, int64_t *nb, size_t *slab);
+jch_slab_where jch_knn_gda_plan(jch_ctx *ctx, int64_t m, int64_t k, int64_t a, int64_t nlev, size_t *slab);
 int32_t jch_launch_knn_gda(jch_ctx *ctx, const gda_args &g, int64_t nb);
 
 // lwplsr_generic.hip: the discrimination fits outside the p-space kernel's envelope, one query at a time (hcn: HOST [m][k] neighbour class codes)
 int32_t jch_lw_generic_fits_da(jch_ctx *ctx, const locw_args &g, const int *hcn);
 
 #ifdef __HIPCC__
+// The launch of a slab kernel pair as jch_slab_plan placed it: KWS (the workspace instantiation, K<false>) without dynamic LDS, or KLDS (K<true>) with the
+// slab in it, after the once-per-device rise of its dynamic LDS limit to lds_max_bytes; 256 threads
+template <auto KLDS, auto KWS, class A>
+static int32_t jch_launch_slab(jch_ctx *ctx, jch_slab_where at, size_t slab_doubles, int lds_max_bytes, const A &a)
+{
+    if (at.glob) hipLaunchKernelGGL(KWS, dim3((unsigned)at.nb), dim3(256), 0, ctx->stream, a);
+    else {
+        static jch_per_device_once attr;
+        if (!attr.done(ctx->device)) {
+            JCH_HIP(ctx, hipFuncSetAttribute((const void *)KLDS, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max_bytes));
+            attr.mark(ctx->device);
+        }
+        hipLaunchKernelGGL(KLDS, dim3((unsigned)at.nb), dim3(256), slab_doubles * sizeof(double), ctx->stream, a);
+    }
+    JCH_HIP(ctx, hipGetLastError());
+    return JCH_OK;
+}
+
 #define KNN_CAP 1024   // candidate buffer per query (LDS) of the scan; the finishing kernels order at most this many (distance, index) pairs
 
 // bitonic sort of `cap` (a power of two <= KNN_CAP) (key, idx) pairs in LDS, ascending by (key, idx); NT threads
@@ -151,6 +200,24 @@ __device__ __forceinline__ void knn_wavesync()
 {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+// the barriers of a slab kernel (jch_slab_plan): a slab in the workspace (LDS = false) needs its stores fenced in front of them
+template <bool LDS> __device__ __forceinline__ void slab_bsync() { if (!LDS) __threadfence_block(); __syncthreads(); }
+template <bool LDS> __device__ __forceinline__ void slab_wsync() { if (!LDS) __threadfence_block(); knn_wavesync(); }
+
+// The label rule of the family: the first maximum over the classes PRESENT in the neighbourhood, in code order, a NaN counting as the largest value
+// (Julia's `argmax`) — `if (present && (best < 0 || knn_vote_better(v, bv))) { best = c; bv = v; }` over c ascending.
+// a beats b as a class score: a NaN beats a number, else the larger one
+__device__ __forceinline__ bool knn_vote_better(double a, double b) { return (a != a && b == b) || a > b; }
+__device__ __forceinline__ bool knn_vote_same(double a, double b) { return a == b || (a != a && b != b); }
+// cnt[c] = how many of the k neighbour class codes cl are c, for c < nlev: one class per thread of 256; every thread calls, a barrier follows
+__device__ __forceinline__ void knn_class_counts(const int *cl, int k, int nlev, int *cnt)
+{
+    for (int c = threadIdx.x; c < nlev; c += 256) {
+        int n = 0;
+        for (int e = 0; e < k; ++e) n += cl[e] == c ? 1 : 0;
+        cnt[c] = n;
+    }
 }
 // The same network run by ONE wave (no workgroup barrier between the passes: a wave's LDS operations complete in order): the four
 // waves of a scan workgroup sort the four queries' buffers side by side — 7 us per 1024 entries against 14 us x 4 queries with

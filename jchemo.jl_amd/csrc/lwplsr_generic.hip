@@ -267,6 +267,32 @@ __global__ __launch_bounds__(256) void k_lw_scores_out(const double *__restrict_
     }
 }
 
+// One query, one fit, for the two loops below: jch_plskern_fit on the gathered neighbour rows (Xl k x p, Yl k x ql, ld k; Tl: null, or k x nlv_cap for the
+// scores) under the query's weights, then jch_predict of the query's own row for the models lo_fit .. hi_fit — the requested range clamped to the LVs the
+// local model has — into prow.  The host images of the model are rewritten by the next fit: the caller synchronises before it reads or refits.
+struct lw_one_fit {
+    std::vector<double> P, R, W, C, TT, xm, xs, ym, ys;
+    int nlv_req, lo_fit = 0, hi_fit = 0;
+    lw_one_fit(const locw_args &g, int nlv_cap)
+        : P((size_t)g.p * nlv_cap), R(P.size()), W(P.size()), C((size_t)g.q * nlv_cap), TT(nlv_cap), xm(g.p), xs(g.p), ym(g.q), ys(g.q), nlv_req(std::max(g.nlv_hi, 1)) {}
+    int32_t run(jch_ctx *ctx, const locw_args &g, int i, int ql, double *Xl, double *Yl, double *Tl, double *prow)
+    {
+        jch_pls_desc d{};
+        d.n = g.k; d.p = g.p; d.q = ql; d.nlv = nlv_req; d.scal = g.scal; d.dtype = JCH_F64; d.loc = JCH_LOC_DEVICE; d.inplace = 0; d.reserved = 0;
+        int32_t nlv_fit = 0;
+        JCH_TRY(jch_plskern_fit(ctx, &d, Xl, g.k, Yl, g.k, g.w + (size_t)i * g.k, Tl, P.data(), R.data(), W.data(), C.data(), TT.data(), xm.data(), xs.data(), ym.data(),
+                                ys.data(), nullptr, &nlv_fit));
+        hi_fit = std::min(g.nlv_hi, (int)nlv_fit); lo_fit = std::min(g.nlv_lo, hi_fit);
+        return jch_predict(ctx, JCH_LOC_DEVICE, g.Xq + i, 1, g.p, g.ldxq, xm.data(), xs.data(), ym.data(), ys.data(), R.data(), C.data(), ql, lo_fit, hi_fit, prow, 1);
+    }
+};
+// profiling off for the per-query fits (they would recycle the event pool of the enclosing call), restored on every way out
+struct lw_profiling_off {
+    jch_ctx *ctx; bool was;
+    explicit lw_profiling_off(jch_ctx *c) : ctx(c), was(c->profiling) { c->profiling = false; }
+    ~lw_profiling_off() { ctx->profiling = was; }
+};
+
 // The discrimination fits of jch_lwplsda_predict_prepared outside the p-space kernel's envelope, one query at a time, the reference's own schedule
 // (src/locwlv.jl:18-39 with src/plsrda.jl:71-77): a unanimous neighbourhood is not fitted (info 1); otherwise `dummy` on the LOCAL levels — the
 // columns of the global table that are present —, jch_plskern_fit on the gathered rows with its scores T, jch_predict and one jch_transform row for
@@ -276,7 +302,7 @@ int32_t jch_lw_generic_fits_da(jch_ctx *ctx, const locw_args &g, const int *hcn)
     const int p = g.p, nlev = g.q, k = g.k, m = g.m, le = g.nlv_hi - g.nlv_lo + 1;
     const int nlv_req = std::max(g.nlv_hi, 1);
     const int nlv_cap = std::min(std::min(nlv_req, p), k);
-    const size_t need = sizeof(double) * ((size_t)k * p + (size_t)k * nlev + (size_t)(le + 1) * nlev + (size_t)k * nlv_cap + ((size_t)m * nlev + 1) / 2 + 64);
+    const size_t need = sizeof(double) * ((size_t)k * p + (size_t)k * nlev + (size_t)(le + 1) * nlev + (size_t)k * nlv_cap + jch_ints_as_doubles((size_t)m * nlev) + 64);
     JCH_TRY(jch_reserve(ctx, ctx->lw_work, need));
     double *Xl = (double *)ctx->lw_work.ptr, *Yl = Xl + (size_t)k * p, *prow = Yl + (size_t)k * nlev, *Tl = prow + (size_t)(le + 1) * nlev;
     int *dcol = (int *)(Tl + (size_t)k * nlv_cap);
@@ -291,11 +317,9 @@ int32_t jch_lw_generic_fits_da(jch_ctx *ctx, const locw_args &g, const int *hcn)
     JCH_HIP(ctx, hipMemcpyAsync(dcol, hcol.data(), sizeof(int) * hcol.size(), hipMemcpyHostToDevice, ctx->stream));
     JCH_HIP(ctx, hipMemcpyAsync(g.info, hinfo.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the two host images go out of scope with this function)
-    std::vector<double> P((size_t)p * nlv_cap), R((size_t)p * nlv_cap), W((size_t)p * nlv_cap), C((size_t)nlev * nlv_cap), TT(nlv_cap), xm(p), xs(p), ym(nlev), ys(nlev);
-    const bool prof = ctx->profiling;
-    ctx->profiling = false;
-    int32_t st = JCH_OK;
-    for (int i = 0; i < m && st == JCH_OK; ++i) {
+    lw_one_fit fit(g, nlv_cap);
+    lw_profiling_off quiet(ctx);
+    for (int i = 0; i < m; ++i) {
         if (hinfo[(size_t)i]) continue;
         const int ql = nloc[(size_t)i];
         const int *ind = g.ind + (size_t)i * k;
@@ -303,25 +327,16 @@ int32_t jch_lw_generic_fits_da(jch_ctx *ctx, const locw_args &g, const int *hcn)
         for (int j = 0; j < ql; ++j)
             hipLaunchKernelGGL(k_lw_gather_y, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, g.Y + (size_t)hcol[(size_t)i * nlev + j] * (size_t)g.ldy, g.ldy, 1, ind, k,
                                Yl + (size_t)j * k);
-        jch_pls_desc d{};
-        d.n = k; d.p = p; d.q = ql; d.nlv = nlv_req; d.scal = g.scal; d.dtype = JCH_F64; d.loc = JCH_LOC_DEVICE; d.inplace = 0; d.reserved = 0;
-        int32_t nlv_fit = 0;
-        st = jch_plskern_fit(ctx, &d, Xl, k, Yl, k, g.w + (size_t)i * k, Tl, P.data(), R.data(), W.data(), C.data(), TT.data(), xm.data(), xs.data(), ym.data(), ys.data(),
-                             nullptr, &nlv_fit);
-        if (st != JCH_OK) break;
-        const int hi_fit = std::min(g.nlv_hi, (int)nlv_fit), lo_fit = std::min(g.nlv_lo, hi_fit);
-        st = jch_predict(ctx, JCH_LOC_DEVICE, g.Xq + i, 1, p, g.ldxq, xm.data(), xs.data(), ym.data(), ys.data(), R.data(), C.data(), ql, lo_fit, hi_fit, prow, 1);
-        if (st != JCH_OK) break;
+        JCH_TRY(fit.run(ctx, g, i, ql, Xl, Yl, Tl, prow));
+        const int lo_fit = fit.lo_fit, hi_fit = fit.hi_fit;
         hipLaunchKernelGGL(k_lw_place_cols, dim3(1), dim3(64), 0, ctx->stream, prow, ql, dcol + (size_t)i * nlev, lo_fit, hi_fit, g.nlv_lo, g.nlv_hi, nlev,
                            g.pred + (size_t)i * le * nlev);
         if (hi_fit >= 1) {
             if (g.tloc) hipLaunchKernelGGL(k_lw_scores_out, dim3((k * hi_fit + 255) / 256), dim3(256), 0, ctx->stream, Tl, k, hi_fit, g.nlv_hi, g.tloc + (size_t)i * k * g.nlv_hi);
-            if (g.tqv) st = jch_transform(ctx, JCH_LOC_DEVICE, g.Xq + i, 1, p, g.ldxq, xm.data(), xs.data(), R.data(), hi_fit, g.tqv + (size_t)i * g.nlv_hi, 1);
+            if (g.tqv) JCH_TRY(jch_transform(ctx, JCH_LOC_DEVICE, g.Xq + i, 1, p, g.ldxq, fit.xm.data(), fit.xs.data(), fit.R.data(), hi_fit, g.tqv + (size_t)i * g.nlv_hi, 1));
         }
-        if (st == JCH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = jch_fail(ctx, JCH_EHIP, "jch_lwplsda_predict_prepared: a per-query fit failed");   // (the host model pieces are rewritten by the next fit)
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return jch_fail(ctx, JCH_EHIP, "jch_lwplsda_predict_prepared: a per-query fit failed");   // (the host model pieces are rewritten by the next fit)
     }
-    ctx->profiling = prof;
-    if (st != JCH_OK) return st;
     JCH_HIP(ctx, hipGetLastError());
     return JCH_OK;
 }
@@ -342,12 +357,10 @@ int32_t jch_lw_generic_fits(jch_ctx *ctx, const locw_args &g, int64_t n, const i
         JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     const int nlv_cap = std::min(std::min(nlv_req, p), k);
-    std::vector<double> P((size_t)p * nlv_cap), R((size_t)p * nlv_cap), W((size_t)p * nlv_cap), C((size_t)q * nlv_cap), TT(nlv_cap), xm(p), xs(p), ym(q), ys(q);
-    const bool prof = ctx->profiling;
-    ctx->profiling = false;                                  // (the per-query fits would recycle the event pool of the enclosing call)
-    int32_t st = JCH_OK;
+    lw_one_fit fit(g, nlv_cap);
+    lw_profiling_off quiet(ctx);
     const int nloop = only ? n_only : m;
-    for (int ii = 0; ii < nloop && st == JCH_OK; ++ii) {
+    for (int ii = 0; ii < nloop; ++ii) {
         const int i = only ? only[ii] : ii;
         double *dst = g.pred + (size_t)i * le * q;
         if (q == 1 && hflags[2 * (size_t)i] != 0.0) {
@@ -357,19 +370,9 @@ int32_t jch_lw_generic_fits(jch_ctx *ctx, const locw_args &g, int64_t n, const i
         const int *ind = g.ind + (size_t)i * k;
         hipLaunchKernelGGL(k_lw_gather_x, dim3((k + 63) / 64, (p + 63) / 64), dim3(256), 0, ctx->stream, g.Xrm, g.ldr, p, ind, k, Xl);
         hipLaunchKernelGGL(k_lw_gather_y, dim3((k * q + 255) / 256), dim3(256), 0, ctx->stream, g.Y, g.ldy, q, ind, k, Yl);
-        jch_pls_desc d{};
-        d.n = k; d.p = p; d.q = q; d.nlv = nlv_req; d.scal = g.scal; d.dtype = JCH_F64; d.loc = JCH_LOC_DEVICE; d.inplace = 0; d.reserved = 0;
-        int32_t nlv_fit = 0;
-        st = jch_plskern_fit(ctx, &d, Xl, k, Yl, k, g.w + (size_t)i * k, nullptr, P.data(), R.data(), W.data(), C.data(), TT.data(), xm.data(), xs.data(),
-                             ym.data(), ys.data(), nullptr, &nlv_fit);
-        if (st != JCH_OK) break;
-        const int hi_fit = std::min(g.nlv_hi, (int)nlv_fit), lo_fit = std::min(g.nlv_lo, hi_fit);
-        st = jch_predict(ctx, JCH_LOC_DEVICE, g.Xq + i, 1, p, g.ldxq, xm.data(), xs.data(), ym.data(), ys.data(), R.data(), C.data(), q, lo_fit, hi_fit, prow, 1);
-        if (st != JCH_OK) break;
-        hipLaunchKernelGGL(k_lw_place, dim3(1), dim3(64), 0, ctx->stream, prow, q, lo_fit, hi_fit, g.nlv_lo, g.nlv_hi, dst);
+        JCH_TRY(fit.run(ctx, g, i, q, Xl, Yl, nullptr, prow));
+        hipLaunchKernelGGL(k_lw_place, dim3(1), dim3(64), 0, ctx->stream, prow, q, fit.lo_fit, fit.hi_fit, g.nlv_lo, g.nlv_hi, dst);
     }
-    ctx->profiling = prof;
-    if (st != JCH_OK) return st;
     JCH_HIP(ctx, hipGetLastError());
     return JCH_OK;
 }

@@ -220,7 +220,7 @@ extern "C" int32_t jch_perm_score_sums(jch_ctx *ctx, int32_t loc, const double *
     jch_carve cv;
     const size_t oB = cv.take((size_t)p * qi), opart = cv.take(nout * (size_t)nslice), oout = cv.take(nout + 1 /*the range flag behind the sums*/),
                  oX = cv.take(host ? (size_t)n * (size_t)p : 0), oP = cv.take(host ? (size_t)n * qi : 0), oY = cv.take(host ? (size_t)n * qi : 0),
-                 orows = cv.take(host && rows ? (size_t)m : 0), operm = cv.take(host && perm ? ((size_t)m * (size_t)p + 1) / 2 : 0);
+                 orows = cv.take(host && rows ? (size_t)m : 0), operm = cv.take(host && perm ? jch_ints_as_doubles((size_t)m * (size_t)p) : 0);
     JCH_TRY(jch_reserve(ctx, ctx->vp_ws, sizeof(double) * cv.off));
     JCH_TRY(jch_reserve_host(ctx, sizeof(double) * (nout + 1)));
     double *ws = (double *)ctx->vp_ws.ptr, *dB = ws + oB, *part = ws + opart, *out = ws + oout, *hs = (double *)ctx->hstage;

@@ -141,6 +141,24 @@ def test_slabs_beyond_the_lds_and_just_under_the_threshold(J, ctx):
         assert (info == 0).all()
 
 
+def test_workspace_instantiation_beside_the_lds_one_at_199_neighbours(J, ctx):
+    """The same rows, responses, queries and k = 199, m = 3 at two widths of X: its first 91 columns (d + q = 92: a slab of 152 640 bytes, in LDS)
+    and all 96 (d + q = 97: 160 720 bytes, beyond WLS_LDS_MAX = 153 600: one piece of the workspace per workgroup, the <false> instantiation).
+    Both sizes are csrc/lwmlr.hip `wls_slab_doubles` x 8 as the Python mirror restates it; the threshold itself lies between 92 and 93 columns.
+    Each run against the longdouble restatement inside the bound of DESIGN.md §23, from host arrays and from device arrays."""
+    n, q, m, k = 260, 1, 3, 199
+    lds_max = importlib.import_module("jchemo_hip.lwmlr").WLS_LDS_MAX
+    assert J.knn_wls_lds_bytes(k, 91, q) == 152640 <= lds_max == 153600 < J.knn_wls_lds_bytes(k, 96, q) == 160720
+    X, Y, _, Xq = clustered(n, 96, q, m, 5151)
+    for d in (91, 96):
+        Xd, Qd = np.asfortranarray(X[:, :d]), np.asfortranarray(Xq[:, :d])
+        ind, w = lists_for(Xd, Qd, k)
+        ref = wls_reference(Xd, Y, Qd, ind, w)
+        for mode in ("host", "dev"):
+            _, info = check_against(J, ctx, Xd, Y, Qd, ind, w, mode, f"d = {d} ({J.knn_wls_lds_bytes(k, d, q)} bytes of slab)", ref=ref)
+            assert (info == 0).all()
+
+
 def test_special_cases(J, ctx):
     """Disjoint hand-made neighbourhoods (query i owns the rows i k .. (i + 1) k - 1), so that a special case touches one query only."""
     rng = np.random.default_rng(77)

@@ -119,11 +119,13 @@ def test_knn_gda_workspace_path_equals_lds_path(J, ctx, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------- score outputs of the local fit
-def _engine_call(J, ctx, X, y, Xq, nlev, k, lo, hi, scal, kind=0, prior=0, want_scores=True):
-    """jch_lwplsda_predict_prepared through the C ABI on a handle built as the mirror builds it (nlvdis = 0, eucl): dict of the host results."""
+def _engine_call(J, ctx, X, y, Xq, nlev, k, lo, hi, scal, kind=0, prior=0, want_scores=True, Yd=None):
+    """jch_lwplsda_predict_prepared through the C ABI on a handle built as the mirror builds it (nlvdis = 0, eucl): dict of the host results.
+    Yd: the handle's n x nlev response table when it is not the dummy table of y."""
     from jchemo_hip import _lib
     from jchemo_hip.plsr import Lwplsr, _addr_ld, _lwplsr_prepared
-    Yd = np.asfortranarray((y[:, None] == np.arange(nlev)[None, :]).astype(F64))
+    if Yd is None:
+        Yd = np.asfortranarray((y[:, None] == np.arange(nlev)[None, :]).astype(F64))
     eng = Lwplsr(X, Yd, None, "eucl", H, k, hi, TOL, scal, False)
     hd = _lwplsr_prepared(eng, ctx, False, nlev)
     m, le = Xq.shape[0], hi - lo + 1
@@ -201,6 +203,78 @@ def test_generic_route_equals_the_batched_kernel(J, ctx, monkeypatch):
     s_ = np.sign((a["tloc"] * b["tloc"]).sum(axis=1, keepdims=True))
     assert np.max(np.abs(a["tloc"] - b["tloc"] * s_)) <= 1e-9 * np.max(np.abs(a["tloc"]))
     assert np.nanmax(np.abs(a["post"] - b["post"])) <= 1e-9
+
+
+# ---------------------------------------------------------------------------------- the label rule
+def julia_argmax_present(v, present):
+    """Julia's `argmax` of v over the levels that are present, in code order: the first NaN when there is one, else the first maximum."""
+    lev = np.flatnonzero(present)
+    nan = np.isnan(v[lev])
+    return int(lev[np.flatnonzero(nan)[0]] if nan.any() else lev[np.argmax(v[lev])])
+
+
+def test_label_rule_of_the_rda_route(J, ctx):
+    """k_rda_finish on m = 4 queries, nlev = 3, k = 6, the models 0 .. 2.  Every query owns one far cluster of six training rows, so its neighbourhood
+    and its class codes are hand-made; the handle's response table is hand-made too (the label rule reads the local predictions whatever they are):
+      0. the columns of the two present classes 1 and 2 are equal: a tie in every model, the lower code wins;
+      1. a NaN in the column of the last present class (2, beside 0): model 0 — the weighted means — is NaN there only and 2 wins;
+      2. a NaN in the column of the first present class;
+      3. the absent class 2 holds by far the largest predictions: it is written out and never wins.
+    Labels and flags against `julia_argmax_present` on the posteriors the call returned, for equality."""
+    nlev, k, m, p, hi = 3, 6, 4, 4, 2
+    rng = np.random.default_rng(61)
+    cen = 100.0 * np.eye(m, p)
+    X = np.asfortranarray(np.repeat(cen, k, axis=0) + rng.standard_normal((m * k, p)))
+    Xq = np.asfortranarray(cen + 0.1 * rng.standard_normal((m, p)))
+    y = np.array([1, 1, 1, 2, 2, 2] + [0, 0, 0, 2, 2, 2] + [0, 0, 0, 2, 2, 2] + [0, 0, 0, 1, 1, 1], dtype=np.int32)
+    Yd = (y[:, None] == np.arange(nlev)[None, :]).astype(F64)
+    Yd[0:6, 1] = Yd[0:6, 2] = rng.standard_normal(6)
+    Yd[10, 2] = np.nan
+    Yd[13, 0] = np.nan
+    Yd[18:24, 2] = 10.0 + rng.standard_normal(6)
+    r = _engine_call(J, ctx, X, y, Xq, nlev, k, 0, hi, False, kind=0, Yd=np.asfortranarray(Yd))
+    ctx.check(r["status"])
+    assert np.array_equal(np.sort(r["ind"], axis=1), np.arange(m * k).reshape(m, k))
+    post, code, info = r["post"], r["code"], r["info"]
+    present = np.stack([np.bincount(y[r["ind"][i]], minlength=nlev) > 0 for i in range(m)])
+    # the four cases are what they claim to be
+    assert np.array_equal(post[0, :, 1], post[0, :, 2]) and np.isfinite(post[0]).all()
+    assert np.isnan(post[1, 0, 2]) and np.isfinite(post[1, 0, :2]).all()
+    assert np.isnan(post[2, 0, 0]) and np.isfinite(post[2, 0, 1:]).all()
+    assert not present[3, 2] and post[3, 0, 2] > 5.0 > post[3, 0, :2].max()
+    want = np.array([[julia_argmax_present(post[i, t], present[i]) for t in range(hi + 1)] for i in range(m)])
+    winfo = np.array([[0 if np.isfinite(post[i, t][present[i]]).all() else 3 for t in range(hi + 1)] for i in range(m)])
+    print("rda labels", code.tolist(), "flags", info.tolist())
+    assert np.array_equal(code, want) and np.array_equal(info, winfo)
+    assert code[0].tolist() == [1, 1, 1] and code[1, 0] == 2 and code[2, 0] == 0 and (code[3] != 2).all()
+
+
+@pytest.mark.parametrize("kind", ["lda", "qda"])
+def test_label_rule_of_knn_gda(J, ctx, kind):
+    """Step 4 of k_knn_gda on m = 4 queries, nlev = 3, k = 6, a = 2.  A posterior is a density over the sum of the densities, so a NaN in one class is a
+    NaN in all of them; the cases this kernel can reach:
+      0. the rows of class 2 mirror those of class 1 about the query (class 0 absent): equal densities bit for bit, a tie, the lower code wins;
+      1. a query so far away that every density is 0: 0 / 0, NaN in the first and in the last present class, the first one wins;
+      2. a NaN in the query's scores: NaN densities, the first present class (1) wins;
+      3. class 2 absent, the query inside class 1: its posterior is 0 and it never wins.
+    Labels against `julia_argmax_present` on the posteriors the call returned, flags against the longdouble restatement, for equality."""
+    nlev, k, a, m = 3, 6, 2, 4
+    rng = np.random.default_rng(62)
+    A = rng.standard_normal((3, a)) + np.array([1.5, 0.5])
+    two = np.vstack([rng.standard_normal((3, a)), rng.standard_normal((3, a)) + 3.0])
+    T = np.stack([np.vstack([A, -A]), two, two, two])
+    tq = np.array([[0.0, 0.0], [1e6, -1e6], [np.nan, 0.3], [3.1, 2.9]])
+    cls = np.array([[1, 1, 1, 2, 2, 2], [0, 0, 0, 2, 2, 2], [1, 1, 1, 2, 2, 2], [0, 0, 0, 1, 1, 1]], dtype=np.int32)
+    post, code, info = (host(x) for x in J.knn_gda(T, tq, cls, nlev, kind=kind, prior="unif", nlv=range(1, a + 1), ctx=ctx))
+    present = np.stack([np.bincount(c, minlength=nlev) > 0 for c in cls])
+    assert np.array_equal(post[0, :, 1], post[0, :, 2]) and (post[0, :, 1] == 0.5).all()
+    assert np.isnan(post[1][:, present[1]]).all() and np.isnan(post[2][:, present[2]]).all()
+    assert (post[3, :, 2] == 0).all() and np.isfinite(post[3]).all()
+    want = np.array([[julia_argmax_present(post[i, t], present[i]) for t in range(a)] for i in range(m)])
+    winfo = np.stack([gda_reference(T[i], tq[i], cls[i], nlev, kind, "unif", 1, a)["info"] for i in range(m)])
+    print(f"{kind} labels", code.tolist(), "flags", info.tolist())
+    assert np.array_equal(code, want) and np.array_equal(info, winfo)
+    assert code[0].tolist() == [1, 1] and code[1].tolist() == [0, 0] and code[2].tolist() == [1, 1] and code[3].tolist() == [1, 1]
 
 
 # ---------------------------------------------------------------------------------- end to end

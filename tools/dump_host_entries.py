@@ -1,7 +1,8 @@
 """Every family once from host arrays and once from device tensors, on seeded inputs, every output array into one .npz: the A/B record of a
 change to the host plumbing (profiles/hostcall_frame_ab.json was made by running this file on two builds and comparing the two .npz files with
 np.array_equal, array by array).  The families, their inputs and their shapes (S1 = 613 x 37 x 3) are those of tests/test_gpu_used_ctx.py; the
-kNN and density families, which that file does not have, run here on inputs of the same size.
+kNN, density, local-MLR, local-PLS-discrimination and permutation-importance families, which that file does not have, run here on inputs of the
+same size (profiles/lwfamily_refactor_ab.json was made the same way).
 
     python tools/dump_host_entries.py OUT.npz          # the dump
     python tools/dump_host_entries.py --time           # host-mode timing probe: one JSON line, median of 5 after one warm-up
@@ -62,6 +63,66 @@ def kde_family(where):
     return run
 
 
+def _class_data(shape, seed, m=67):
+    n, p, _ = shape
+    rng = np.random.default_rng(seed)
+    y = rng.integers(0, 3, n)
+    cen = 2.0 * rng.standard_normal((3, p))
+    return cen[y] + rng.standard_normal((n, p)), y.astype(np.int64), cen[rng.integers(0, 3, m)] + rng.standard_normal((m, p)), rng
+
+
+def lwmlr_family(where):
+    def run(ctx, shape):
+        n, p, q = shape
+        X, y, Xq, rng = _class_data(shape, n + 3 * p)
+        X, Xq = X[:, :6], Xq[:, :6]                           # (a local MLR needs k > d)
+        Y = X[:, :q] @ rng.standard_normal((q, q)) + 0.1 * rng.standard_normal((n, q))
+        inp = U.Inputs(where)
+        Xi, Yi, Qi = inp(X), inp(Y), inp(Xq)
+        ind, _ = J.getknn(Xi, Qi, k=35, ctx=ctx)
+        w = inp(rng.uniform(0.2, 1.0, (Xq.shape[0], 35)))
+        pred, info = J.knn_wls(Xi, Yi, Qi, ind, w, info=True, ctx=ctx)
+        fm = J.lwmlr(Xi, Yi, metric="mahal", h=2.0, k=35, ctx=ctx)
+        fd = J.lwmlrda(Xi, y, h=2.0, k=35, ctx=ctx)
+        return dict(knn_wls=pred, knn_wls_info=info, lwmlr=J.lwmlr_predict(fm, Qi, ctx=ctx), lwmlrda=J.lwmlrda_predict(fd, Qi, ctx=ctx)), inp
+    return run
+
+
+def lwplsda_family(where):
+    def run(ctx, shape):
+        n, p, _ = shape
+        X, y, Xq, rng = _class_data(shape, n + 5 * p)
+        inp = U.Inputs(where)
+        Xi, Qi = inp(X), inp(Xq)
+        out = {}
+        for name, fit, pred, kw in (("lwplsrda", J.lwplsrda, J.lwplsrda_predict, {}), ("lwplslda", J.lwplslda, J.lwplslda_predict, dict(prior="prop")),
+                                    ("lwplsqda", J.lwplsqda, J.lwplsqda_predict, dict(prior="unif"))):
+            fm = fit(Xi, y, nlvdis=4, metric="mahal", h=2.0, k=60, nlv=3, ctx=ctx, **kw)
+            out[name] = pred(fm, Qi, nlv=range(1, 4), ctx=ctx)
+        m, k, a = 9, 40, 3
+        T = np.ascontiguousarray(rng.standard_normal((m, k, a)))
+        cls = rng.integers(0, 3, (m, k)).astype(np.int32)
+        T += cls[:, :, None]
+        tq = np.ascontiguousarray(rng.standard_normal((m, a)) + 1.0)
+        if where == "device":
+            import torch
+            T, tq, cls = (torch.as_tensor(x, device="cuda:0") for x in (T, tq, cls))
+        for kind in ("lda", "qda"):
+            out[f"knn_gda_{kind}"] = J.knn_gda(T, tq, cls, 3, kind=kind, prior="prop", nlv=range(1, a + 1), ctx=ctx)
+        return out, inp
+    return run
+
+
+def viperm_family(where):
+    def run(ctx, shape):
+        n, p, q = shape
+        X, _, _, rng = _class_data(shape, n + 7 * p)
+        Y = X[:, :q] @ rng.standard_normal((q, q)) + 0.1 * rng.standard_normal((n, q))
+        inp = U.Inputs(where)
+        return dict(viperm=J.viperm(inp(X), inp(Y), perm=1, score=J.rmsep, fun=J.plskern, seed=31, ctx=ctx, nlv=3)), inp
+    return run
+
+
 def families():
     """name -> run(ctx, shape), every family of the used-ctx test in both modes (its bf16 fit takes device inputs only)."""
     out = {}
@@ -84,6 +145,9 @@ def families():
         out.update({f"{k}@{where}": v[0] for k, v in made.items()})
         out[f"knn@{where}"] = knn_family(where)
         out[f"kde@{where}"] = kde_family(where)
+        out[f"lwmlr@{where}"] = lwmlr_family(where)
+        out[f"lwplsda@{where}"] = lwplsda_family(where)
+        out[f"viperm@{where}"] = viperm_family(where)
     out["gridscorelv@host"] = U.gridscorelv_victim()[0]
     return out
 
