@@ -575,6 +575,16 @@ JCH_API int32_t jch_pca_fit(jch_ctx *ctx, int32_t loc, const double *X, int64_t 
  * reaches out[i] only.  One rank only. */
 JCH_API int32_t jch_row_resid_ss(jch_ctx *ctx, int32_t loc, const double *X, int64_t m, int64_t p, int64_t ldx, const double *shift, const double *Z,
                                  int64_t k, int64_t ldz, const double *B, int64_t ldb, double *out);
+/* jch_row_resid_ss_lv -- the nested form, every level a_lo .. a_hi in ONE read of X (src/wshenk.jl:59-62 forms nlv `xresid` matrices):
+ * out[i + (a - a_lo) ldo] = sum_j ( X[i, j] - shift[j] - sum_{l < a} Z[i, l] B[j, l] )^2 for 0 <= a_lo <= a_hi <= kz.  X m x p (ldx >= m), Z m x kz
+ * (ldz >= m) and out m x (a_hi - a_lo + 1) (ldo >= m) [loc], X and Z read only; shift (p, NULL = zeros) and B (p x kz, ldb >= p) HOST.  a_hi = 0 is
+ * valid (Z and B may then be NULL).  The residual of level a is the residual of level a - 1 minus one rank-one term, subtracted and then squared (no
+ * expanded form).  Any m, p, kz: one read of X holds for a_hi <= 32; beyond, every further 32 levels are one more launch that reads X again and replays the terms before its chunk.  Rows >= m, columns >= p and score columns >= a_hi
+ * are never read; out beyond row m of a column is never written.  Every sum has a fixed order and no atomics: two runs give identical bits, and so do
+ * a host and a device X or Z and an aligned and an unaligned one, and level a has the same bits whatever a_lo and a_hi.  A NaN at X[i, j] or Z[i, l]
+ * reaches row i only.  One rank only. */
+JCH_API int32_t jch_row_resid_ss_lv(jch_ctx *ctx, int32_t loc, const double *X, int64_t m, int64_t p, int64_t ldx, const double *shift, const double *Z,
+                                    int64_t kz, int64_t ldz, const double *B, int64_t ldb, int32_t a_lo, int32_t a_hi, double *out, int64_t ldo);
 
 /* ---- exact column medians and MADs, Stahel-Donoho outlyingness (src/utility.jl:162, src/stah.jl, src/occstah.jl) ---------------
  * jch_col_median_mad -- med[j] = median(X[:, j]), mad[j] = 1.4826022185056018 * median(|X[:, j] - med[j]|) (StatsBase's `mad`), by an
@@ -745,6 +755,22 @@ JCH_API int32_t jch_lwplsda_predict_prepared(jch_ctx *ctx, const jch_lwplsr_mode
                                              int32_t k, double h, double tol, int32_t scal, int32_t nlv_lo, int32_t nlv_hi, int32_t *code,
                                              double *post, int32_t *info, double *tloc_out, double *tq_out, int32_t *ind_out, double *dist_out,
                                              double *w_out);
+/* jch_lwplsravg_predict_prepared -- kNN-LWPLSR-AVG (src/lwplsravg.jl, typf = "unif" / "shenk") on a prepared handle: the search and the
+ * weights of jch_lwplsr_predict_prepared (the same front end), ONE launch of the p-space local-fit kernel over the level range, the average on the host.
+ * The levels are clamped once, as the reference does inside the model of a neighbourhood (n = k): lo = min(nlv_lo, k, p), hi = min(nlv_hi, k, p), for
+ * typf = 1 lo = max(lo, 1); le = hi - lo + 1 distinct levels, and every array below is sized with these clamped lo, hi, le.  typf = 0: pred = the mean of
+ * the le level predictions in level order.  typf = 1: wlv[a] proportional to 1 / (rss_r[a] rss_b[a]), normalised over lo..hi (what the reference's three
+ * `mweight` calls cancel to), pred = sum_a wlv[a] pred_a in level order; rss_r[a - 1] = |xresid| of the query after a local LVs (original scale),
+ * rss_b[a - 1] = sqrt((|int|^2 + |B|^2) / q) of the local model with a LVs (src/wshenk.jl:59-67), a = 1..hi.
+ *   Zq m x dd or NULL (the handle's query map), Xq m x p [loc].  Results on the HOST: pred [m][q]; each may be NULL: pred_lv [m][le][q], wlv [m][le],
+ *   rss_r and rss_b [m][hi] (typf = 1 only), info [m], ind_out / dist_out / w_out [m][k].
+ *   info[i] (typf = 1; 0 throughout for typf = 0): 0 = fitted; 1 = a constant univariate y in the neighbourhood (src/locw.jl:34-36): pred = that value, the
+ *   wlv and rss rows NaN; 2 = a Shenk norm of lo..hi is 0 or not finite: the reference's arithmetic gives NaN there and so do pred[i] and wlv.
+ * Outside the envelope of the p-space kernel (jch_lwplsda_predict_prepared's): JCH_EINVAL with a message naming k, p, q, nlv.  One rank only. */
+JCH_API int32_t jch_lwplsravg_predict_prepared(jch_ctx *ctx, const jch_lwplsr_model *model, int32_t loc, const double *Zq, int64_t ldzq, const double *Xq,
+                                               int64_t m, int64_t ldxq, int32_t k, double h, double tol, int32_t scal, int32_t nlv_lo, int32_t nlv_hi,
+                                               int32_t typf, double *pred, double *pred_lv, double *wlv, double *rss_r, double *rss_b, int32_t *info,
+                                               int32_t *ind_out, double *dist_out, double *w_out);
 
 /* ---- Gaussian kernel density estimates: what the reference's `dmkern`, `kdeda` and `plskdeda` evaluate (src/dmkern.jl:151-163,
  * src/kdeda.jl:81-97, src/plskdeda.jl:52-64 with the prediction of src/plslda.jl:107-130) -- DESIGN.md §21.

@@ -343,7 +343,10 @@ __device__ __forceinline__ void locw_block_sums(double (&v)[NV], double *scratch
 }
 
 // Q = number of responses padded to {1, 2, 4, 8, 16}; the actual q = g.q <= Q (pad responses are all-zero columns).
-template <int KC, int Q>
+// SHENK (lwplsravg.hip): also the two Shenk norms of every local model 1 .. nlv_hi (src/wshenk.jl:59-67 with `xresid` and `coef`
+// applied to the local fit), from a running residual e [ldr] (starts at the centred query, e -= tq P_a) and a running coefficient matrix Bm [Q][ldr]
+// (starts at 0, Bm[y] += r_a c_a[y]) kept in the slab behind Rm.  SHENK = false is the kernel without any of it.
+template <int KC, int Q, bool SHENK = false>
 __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -369,6 +372,8 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
     double *Xg = g.scratch + (size_t)blockIdx.x * g.slab;
     double *Pm = Xg + (size_t)k * ldr;
     double *Rm = Pm + (size_t)g.nlv_hi * ldr;
+    double *em = Rm + (size_t)g.nlv_hi * ldr;   // SHENK only: [ldr] running residual, then Bm [Q][ldr]
+    double *Bm = em + ldr;
     const int le = g.nlv_hi - g.nlv_lo + 1;
     const int nlvloc = min(min(k, p), g.nlv_hi);
     double *ymean = ys, *ysd = ys + Q, *prun = ys + 3 * Q;
@@ -415,6 +420,7 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
         __syncthreads();
         const double gmin = fmin(fmin(sc[8], sc[9]), fmin(sc[10], sc[11])), gmax = fmax(fmax(sc[12], sc[13]), fmax(sc[14], sc[15]));
         __syncthreads();
+        if constexpr (SHENK) { if (tid == 0) g.shenk_info[qi] = (q == 1 && gmin == gmax) ? 1 : 0; }
         if (q == 1 && gmin == gmax) {
             for (int a = tid; a < le; a += 256) g.pred[(size_t)qi * le + a] = gmin;
             continue;
@@ -506,6 +512,12 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
         for (int j = tid; j < ldr; j += 256)
             xq[j] = j < p ? (g.scal ? (g.Xq[(size_t)qi + (size_t)j * (size_t)g.ldxq] - mu[j]) / sg[j]
                                     : g.Xq[(size_t)qi + (size_t)j * (size_t)g.ldxq] - mu[j]) : 0.0;
+        if constexpr (SHENK)
+            for (int j = tid; j < ldr; j += 256) {   // (own entries: thread tid owns the columns tid + 256 i of e and Bm throughout)
+                em[j] = xq[j];
+#pragma unroll
+                for (int y = 0; y < Q; ++y) Bm[(size_t)y * ldr + j] = 0.0;
+            }
         {
             constexpr bool FUSEK = Q * KC <= 16;
             v2f64 mf[KC], sf[KC], kacc[FUSEK ? Q : 1][KC];
@@ -720,12 +732,38 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
             locw_block_sums<Q + 1>(cs, red);
             const double tq = cs[Q];
             if (g.tqv && tid == 0) g.tqv[(size_t)qi * g.nlv_hi + a] = tq;
+            double sh[SHENK ? Q + 2 : 1];   // SHENK: sum (sg e)^2, sum Bo^2, sum_j mu[j] Bo[j, y] per response
+#pragma unroll
+            for (int y = 0; y < (SHENK ? Q + 2 : 1); ++y) sh[y] = 0.0;
             for (int j = tid; j < ldr; j += 256) {
                 const double z = ((zred[j] + zred[KC * 128 + j]) + zred[2 * KC * 128 + j]) + zred[3 * KC * 128 + j];
 #pragma unroll
                 for (int y = 0; y < Q; ++y) Kv[(size_t)y * ldr + j] -= z * (cs[y] / ttot);
                 Pm[(size_t)a * ldr + j] = z / ttot;
                 Rm[(size_t)a * ldr + j] = rv[j];
+                if constexpr (SHENK) {   // (columns >= p: xq, P and r are 0 there and sg is 1, so they add exact zeros)
+                    const double ej = em[j] - tq * (z / ttot);
+                    em[j] = ej;
+                    const double se = sg[j] * ej;
+                    sh[0] += se * se;
+#pragma unroll
+                    for (int y = 0; y < Q; ++y) {
+                        const double bm = Bm[(size_t)y * ldr + j] + rv[j] * (cs[y] / ttot);
+                        Bm[(size_t)y * ldr + j] = bm;
+                        const double bo = bm * ysd[y] / sg[j];
+                        sh[1] += bo * bo;
+                        sh[2 + y] += mu[j] * bo;
+                    }
+                }
+            }
+            if constexpr (SHENK) {
+                locw_block_sums<Q + 2>(sh, red);
+                if (tid == 0) {
+                    double si = 0.0;
+                    for (int y = 0; y < q; ++y) { const double iy = ymean[y] - sh[2 + y]; si += iy * iy; }
+                    g.rss_r[(size_t)qi * g.nlv_hi + a] = sqrt(sh[0]);
+                    g.rss_b[(size_t)qi * g.nlv_hi + a] = sqrt((si + sh[1]) / (double)q);
+                }
             }
             const int kk = a + 1;
             if (tid < Q) {
@@ -748,6 +786,8 @@ __global__ __launch_bounds__(256) void k_locw_plskern(locw_args g)
             }
         if (g.tqv)
             for (int a = nlvloc + tid; a < g.nlv_hi; a += 256) g.tqv[(size_t)qi * g.nlv_hi + a] = 0.0;
+        if constexpr (SHENK)   // (levels the local model does not have: the caller clamps, so there are none; NaN if there were)
+            for (int a = nlvloc + tid; a < g.nlv_hi; a += 256) g.rss_r[(size_t)qi * g.nlv_hi + a] = g.rss_b[(size_t)qi * g.nlv_hi + a] = __builtin_nan("");
     }
 }
 
@@ -772,9 +812,18 @@ static int32_t launch_locw_q(jch_ctx *ctx, locw_args &g)
         return jch_fail(ctx, JCH_EINVAL, "jch_lwplsr_predict: k / p / q too large for the batched local-PLS kernels (k = %d, p = %d, q = %d)", g.k, g.p, g.q);
     }
     const int nb = std::min(g.m, ctx->cus * 2);
-    g.slab = ((size_t)g.k * g.ldr + 2 * (size_t)g.nlv_hi * g.ldr + 31) & ~(size_t)31;
+    const bool shenk = g.rss_r != nullptr;   // (with rss_b and shenk_info: lwplsravg.hip passes all three or none)
+    g.slab = ((size_t)g.k * g.ldr + 2 * (size_t)g.nlv_hi * g.ldr + (shenk ? (size_t)(1 + Q) * g.ldr : 0) + 31) & ~(size_t)31;
     JCH_TRY(jch_reserve_xstage(ctx, sizeof(double) * g.slab * nb));   // (the staging buffer of a host-array fit is re-used for the slabs)
     g.scratch = (double *)ctx->xstage.ptr;
+    if (shenk) {
+        static jch_per_device_once attr_s;
+        if (!attr_s.done(ctx->device)) {
+            JCH_HIP(ctx, hipFuncSetAttribute((const void *)k_locw_plskern<KC, Q, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr_s.mark(ctx->device);
+        }
+        hipLaunchKernelGGL((k_locw_plskern<KC, Q, true>), dim3(nb), dim3(256), lds, ctx->stream, g);
+    } else
     hipLaunchKernelGGL((k_locw_plskern<KC, Q>), dim3(nb), dim3(256), lds, ctx->stream, g);
     JCH_HIP(ctx, hipGetLastError());
     return JCH_OK;

@@ -24,6 +24,10 @@ struct locw_args {
     int da = 0;                             // discrimination: Y is a dummy table.  A neighbourhood of one class is not fitted (info = 1, src/locwlv.jl:25-28
                                             // on the label column); a response whose local weighted sd is 0 (a class absent from the neighbourhood) is a zero column
     int *info = nullptr;                    // [m], written with da: 1 = unanimous neighbourhood (nothing else written for the query), 0 otherwise
+    // p-space kernel only, optional, all three or none (null: the kernel without them) — the Shenk norms of the local models (lwplsravg.hip)
+    double *rss_r = nullptr;                // [m][nlv_hi]: |xresid| of the query after a + 1 local LVs at (i nlv_hi + a), in the original scale
+    double *rss_b = nullptr;                // [m][nlv_hi]: sqrt((|int|^2 + |B|^2) / q) of the local model with a + 1 LVs
+    int *shenk_info = nullptr;              // [m]: 1 = constant univariate y in the neighbourhood (nothing fitted, the norms not written), 0 otherwise
 };
 
 // lwplsr_kspace.hip: _feasible: the k-space kernel can take this shape (k <= 208, q <= 8, nlv <= 48, p <= 2048);

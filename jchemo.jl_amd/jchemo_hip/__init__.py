@@ -21,3 +21,5 @@ from .gda import (Dmnorm, Lda, Qda, class_cov, dmnorm, dmnorm_predict, gauss_fac
 from .lwplsda import (LwplsdaPred, LwplsLda, LwplsQda, LwplsrS, Lwplsrda, LwplsrdaS, knn_gda, knn_gda_lds_bytes, locw_pspace_lds_bytes, lwplslda, lwplslda_predict,  # noqa: F401
                       lwplsqda, lwplsqda_predict, lwplsr_s, lwplsr_s_predict, lwplsrda, lwplsrda_predict, lwplsrda_s, lwplsrda_s_predict)
 from .viperm import PERM_QGROUP, PERM_SLICE_ROWS, Isel, Viperm, isel, isel_intervals, perm_fill, perm_score_sums, viperm  # noqa: F401
+from .plsavg import (LwplsdaAvg, LwplsrAvg, LwplsrAvgPred, lwplsravg_prepared_call, lwplsdaavg_predict, lwplsldaavg, lwplsqdaavg, lwplsravg, lwplsravg_predict, lwplsrdaavg, Plsdaavg, Plsravg, PlsravgCri, PlsravgShenk, PlsravgUnif, Plsrstack, findmax_cla, fweight, plsdaavg_predict, plsldaavg, plsqdaavg,  # noqa: F401
+                     plsravg, plsravg_, plsravg_predict, plsrdaavg, row_resid_ss_lv, wshenk)

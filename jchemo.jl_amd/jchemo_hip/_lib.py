@@ -40,6 +40,7 @@ SYMBOLS = (
     "jch_class_cov", "jch_gauss_factor", "jch_mahsq_chol",
     "jch_knn_gda", "jch_lwplsda_predict_prepared",
     "jch_perm_fill", "jch_perm_score_sums",
+    "jch_row_resid_ss_lv", "jch_lwplsravg_predict_prepared",
 )
 
 
@@ -139,6 +140,7 @@ def load():
     L.jch_xtdx.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, dp, dp, dp]
     L.jch_pca_fit.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i64, i32, i32, f64, i32] + [dp] * 11 + [C.POINTER(i32), dp, C.POINTER(i32), C.POINTER(i32)]
     L.jch_row_resid_ss.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, i64, dp]
+    L.jch_row_resid_ss_lv.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, i64, i32, i32, dp, i64]
     L.jch_col_median_mad.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i32]
     L.jch_stah.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, dp, i64, i64, i32, dp, dp, dp]
     L.jch_farthest_pair.argtypes = [vp, i32, dp, i64, i64, i64, dp, i32, dp, dp]
@@ -156,6 +158,7 @@ def load():
     L.jch_mahsq_chol.argtypes = [vp, i32, dp, i64, i64, i64, dp, i32, dp, i64, i64, i32, dp, i64]
     L.jch_knn_gda.argtypes = [vp, i32, dp, i64, i32, i32, dp, dp, i32, i32, i32, i32, i32, dp, dp, dp]
     L.jch_lwplsda_predict_prepared.argtypes = [vp, vp, dp, i32, i32, i32, i32, dp, i64, dp, i64, i64, i32, f64, f64, i32, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp]
+    L.jch_lwplsravg_predict_prepared.argtypes = [vp, vp, i32, dp, i64, dp, i64, i64, i32, f64, f64, i32, i32, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp]
     L.jch_perm_fill.argtypes = [vp, i32, dp, i64, i64, i64, C.c_uint64]
     L.jch_perm_score_sums.argtypes = [vp, i32, dp, i64, i64, i64, dp, i64, dp, i64, dp, i64, i64, dp, i64, dp, i64, C.c_uint64, dp]
     L.jch_fill_uniform.argtypes = [vp, dp, i64, i64, i64, i64, i64, C.c_uint64]

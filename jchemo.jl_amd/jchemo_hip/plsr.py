@@ -439,6 +439,10 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
     if type(fm).__name__ in ("Knnr", "Knnda", "Occknndis", "Occlknndis"):
         from . import knn
         return {"Knnr": knn.knnr_predict, "Knnda": knn.knnda_predict}.get(type(fm).__name__, knn.occknn_predict)(fm, X, ctx=ctx)
+    if type(fm).__name__ in ("Plsravg", "Plsdaavg", "LwplsrAvg", "LwplsdaAvg"):   # src/plsravg.jl:155-158, src/plsrdaavg.jl:80-97, src/lwplsravg.jl:120 (plsavg.py)
+        from . import plsavg
+        return dict(Plsravg=plsavg.plsravg_predict, Plsdaavg=plsavg.plsdaavg_predict, LwplsrAvg=plsavg.lwplsravg_predict,
+                    LwplsdaAvg=plsavg.lwplsdaavg_predict)[type(fm).__name__](fm, X, ctx=ctx)
     if isinstance(fm, Lwplsr):
         return lwplsr_predict(fm, X, nlv=nlv, ctx=ctx, rank=rank, world=world)
     if isinstance(fm, Plsrda):

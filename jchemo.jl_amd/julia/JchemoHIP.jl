@@ -37,7 +37,7 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        snv, snv!, detrend, detrend!, savgol, savgol!, savgk, mavg, mavg!, mavg_runmean, fdif,
        Covsel, Covselr, covsel, covsel!, covselr,
        Pca, Pcr, pcasvd, pcasvd!, pcaeigen, pcaeigen!, pcaeigenk, pcaeigenk!, pcr, pcr!, xtdx,
-       Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss,
+       Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss, row_resid_ss_lv,
        Occstah, occstah, stah, colmad, col_median_mad,
        sampks, sampdp, sampsys, sampcla, farthest_pair, maxmin_select,
        Knnr, Knnda, Occknndis, Occlknndis, getknn, knnr, knnda, occknndis, occlknndis, knn_search, knn_wmean, knn_vote, knn_gather_median,
@@ -1690,6 +1690,28 @@ function row_resid_ss(X, shift = nothing, Z = nothing, B = nothing; ctx = defaul
     out
 end
 
+"""`row_resid_ss_lv(X, shift, Z, B, a_lo, a_hi)` — out[i, a - a_lo + 1] = sum_j (X[i, j] - shift[j] - sum_{l <= a} Z[i, l] B[j, l])^2 for a = a_lo..a_hi
+where X lives, from one read of X (jch_row_resid_ss_lv); shift and B on the host; 0 <= a_lo <= a_hi <= size(Z, 2)."""
+function row_resid_ss_lv(X, shift, Z, B, a_lo::Integer, a_hi::Integer; ctx = default_ctx())
+    X = _in(X); m, p = size(X)
+    kz = Z === nothing ? 0 : size(Z, 2)
+    0 <= a_lo <= a_hi <= kz || throw(ArgumentError("needs 0 <= a_lo <= a_hi <= $kz"))
+    out = _similar(X, m, a_hi - a_lo + 1)
+    shift = shift === nothing ? nothing : Vector{Float64}(vec(shift))
+    Bm = kz == 0 ? zeros(1, 1) : Matrix{Float64}(B)
+    kz == 0 || size(Bm) == (p, kz) || throw(DimensionMismatch("B is not $p x $kz"))
+    Zm = kz == 0 ? X : Z
+    GC.@preserve X Zm out shift begin
+        check(ctx, ccall((:jch_row_resid_ss_lv, LIB), Int32,
+                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                          Int32, Int32, Ptr{Float64}, Int64),
+                         ctx.h, _loc(X), pointer(X), m, p, max(stride(X, 2), m), shift === nothing ? Ptr{Float64}(C_NULL) : pointer(shift),
+                         kz == 0 ? Ptr{Float64}(C_NULL) : pointer(Zm), kz, kz == 0 ? 0 : max(stride(Zm, 2), m), Bm, p, a_lo, a_hi, pointer(out),
+                         max(m, 1)))
+    end
+    out
+end
+
 const _MAD_CONSTANT = 1.4826022185056018      # StatsBase 0.33 / 0.34 `mad(x)`: normalize = true is the default (DESIGN.md 6)
 _median_sorted(s) = (n = length(s); isodd(n) ? s[(n + 1) >> 1] : (s[n >> 1] + s[(n >> 1) + 1]) / 2)
 function _quantile_sorted(s, q)   # Statistics._quantile with alpha = beta = 1 (type 7)
@@ -2662,6 +2684,27 @@ function mahsqchol(X, Y, Uinv = nothing; ctx = default_ctx())
         Uinv = f.Uinv
     end
     mahsq_chol(X, Y, ensure_mat(Uinv); ctx = ctx)
+end
+
+"""`lwplsravg_prepared(pm, q, Zq, X, k, h, tol, scal, lo, hi, typf)` — jch_lwplsravg_predict_prepared on a prepared handle `pm` (q responses; typf 0 = unif, 1 = shenk; `Zq`
+= nothing: the handle's query map).  The levels are clamped as the library does (n = k).  Returns (pred q x m, pred_lv q x le x m, wlv le x m, rss_r hi x m,
+rss_b hi x m, info m, ind k x m, dist k x m, w k x m) in the C layouts.  NOT EXECUTED in the build image (no Julia toolchain)."""
+function lwplsravg_prepared(pm, q::Integer, Zq, X, k::Integer, h, tol, scal::Bool, lo::Integer, hi::Integer, typf::Integer; ctx = default_ctx())
+    Q = _in(X); m, p = size(Q)
+    kp = min(k, p); hic = min(hi, kp); loc_ = typf == 1 ? max(min(lo, kp), 1) : min(lo, kp); le = hic - loc_ + 1
+    le >= 1 || throw(ArgumentError("no level left after the clamp"))
+    pred = zeros(q, m); pred_lv = zeros(q, le, m); wlv = zeros(le, m); rss_r = zeros(max(hic, 1), m); rss_b = zeros(max(hic, 1), m); info = zeros(Int32, m)
+    ind = zeros(Int32, k, m); dist = zeros(k, m); w = zeros(k, m)
+    Zm = Zq === nothing ? Q : Zq
+    GC.@preserve Zm Q pred pred_lv wlv rss_r rss_b info ind dist w begin
+        check(ctx, ccall((:jch_lwplsravg_predict_prepared, LIB), Int32,
+                         (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int32, Float64, Float64, Int32, Int32, Int32, Int32,
+                          Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.h, pm.h, _loc(Q), Zq === nothing ? Ptr{Float64}(C_NULL) : pointer(Zm), stride(Zm, 2), pointer(Q), m, stride(Q, 2), Int32(k),
+                         Float64(h), Float64(tol), Int32(scal ? 1 : 0), Int32(lo), Int32(hi), Int32(typf), pointer(pred), pointer(pred_lv), pointer(wlv),
+                         pointer(rss_r), pointer(rss_b), pointer(info), pointer(ind), pointer(dist), pointer(w)))
+    end
+    (pred = pred, pred_lv = pred_lv, wlv = wlv, rss_r = rss_r, rss_b = rss_b, info = info, ind = ind, dist = dist, w = w)
 end
 
 # ---- local PLS discrimination and the LWPLS models on global scores (src/lwplsrda.jl, src/lwplslda.jl, src/lwplsqda.jl, src/lwplsr_s.jl,
