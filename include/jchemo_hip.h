@@ -606,6 +606,43 @@ JCH_API int32_t jch_col_median_mad(jch_ctx *ctx, int32_t loc, const double *X, i
 JCH_API int32_t jch_stah(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *mu_scal, const double *s_scal,
                          const double *P, int64_t a, int64_t ldp, int32_t fit, double *mu, double *s, double *d);
 
+/* ---- spatial median and spherical PCA (src/colmedspa.jl, src/pcasph.jl) ----------------------------------------------------------
+ * X n x p (ldx >= n) [loc], read only, never written; any n, p >= 1; rows >= n and columns >= p are never read; row numbers are 64-bit.  No atomics,
+ * every sum in a fixed order: two runs give identical bits, and so do a host and a device X and an aligned and an unaligned one.  One rank only.
+ * jch_weiszfeld_step -- ONE step of `colmedspa` (src/colmedspa.jl:15-30) from the centre mu0 in one read of X: d_i = |x_i - mu0|, w0 = median(d)
+ *   (Julia's: lo / 2 + hi / 2 for even n), ep = delta w0, u_i = ep when d_i <= ep and 1 / d_i otherwise (the literal reading of :20-23), mu =
+ *   sum u_i x_i / sum u_i, h = |mu - mu0|.  The pass cannot know ep before it has every distance: it leaves the rows with d_i <= guard out of its
+ *   sums and they are added afterwards, in ascending row order, with their true weight.  guard >= 0 must be >= ep, else JCH_EINVAL once the median
+ *   is known (mu, d, h and nleft are then not written); guard = +Inf sends every row through the second stage; guard < 0: the distances are taken
+ *   first (one more read of X) and the pass runs with guard = ep.  mu0 and mu (p) HOST; d (n) [loc], may be NULL; HOST scalars, each may be NULL:
+ *   w0, h, nleft = the rows the pass left out.  A NaN in X makes w0, h and every entry of mu NaN.
+ * jch_spatial_median -- `colmedspa(X; delta)` (:4-33): the column medians (jch_col_median_mad), then steps while h > delta sqrt(p), the first with
+ *   guard < 0, every later one with guard = delta (w0_prev + h_prev) (1 + 2^-40), an upper bound of its ep by the triangle inequality (a step whose
+ *   guard rounding has put below ep is redone with the exact clamp).  The host reads one scalar record per step.  maxit >= 1 bounds the steps (the
+ *   reference loops for ever on data that never converge): converged = 0 reports it.  mu (p) HOST; d (n) [loc], may be NULL: the distances to the
+ *   LAST centre stepped from, as the loop left them; niter, h_last, converged HOST, each may be NULL.  NaN in X: one step, mu = NaN, converged = 1
+ *   (the reference's `while h > delta1` ends on a NaN h too); n = 1 gives NaN through 0 / 0, as in the reference. */
+JCH_API int32_t jch_weiszfeld_step(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *mu0, double delta,
+                                   double guard, double *mu, double *d, double *w0, double *h, int64_t *nleft);
+JCH_API int32_t jch_spatial_median(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, double delta, int32_t maxit, double *mu,
+                                   double *d, int32_t *niter, double *h_last, int32_t *converged);
+/* jch_pcasph_fit -- `pcasph!` (src/pcasph.jl:60-92) without a copy of X, a transpose or an SVD.  xmeans = the spatial median (typc = JCH_CENT_MEDSPA;
+ *   delta, maxit_med as above) or the weighted column mean (JCH_CENT_MEAN); xscales = ones or, scal != 0, colstd(X, weights) about the weighted mean
+ *   whatever typc (:72); r_i = |(x_i - xmeans) / xscales|; G = Xs' diag(w_i / r_i^2) Xs (jch_xtdx's pass with mu = xmeans, rescaled by xscales when scal:
+ *   the Gram of the rows projected on the unit sphere); P = its nlv leading eigenvectors (jch_pca_fit's iteration, tol, maxit, sign rule); T = Xs P;
+ *   sv = the MADs of the columns of T / r (jch_col_median_mad on the device); T, P, sv, eig and resid are returned ordered by sv descending, ties in
+ *   eigen order (:87-90).  A row with r_i = 0 makes the reference's SVD fail on NaN; here it gets weight 0 in G and a zero row in T / r, and is
+ *   counted in nzero.  nlv is clamped to min(n, p); p <= 32768.
+ *   weights n or NULL [loc].  Outputs, each may be NULL: T n x nlv (ld n) and weights_norm n [loc]; HOST: P p x nlv (ld p); sv, eig (the eigenvalues
+ *   of G), resid (nlv); xmeans, xscales, colvar = the weighted variances of the columns of X about the weighted mean (p); sstot = trace(G);
+ *   niter_med, converged_med (0, 1 when typc = JCH_CENT_MEAN); niter, converged (the eigen iteration); nlv_out; nzero. */
+#define JCH_CENT_MEDSPA 0
+#define JCH_CENT_MEAN 1
+JCH_API int32_t jch_pcasph_fit(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *weights, int32_t nlv, int32_t typc,
+                               double delta, int32_t maxit_med, int32_t scal, double tol, int32_t maxit, double *T, double *P, double *sv, double *eig,
+                               double *xmeans, double *xscales, double *weights_norm, double *sstot, double *colvar, int32_t *niter_med,
+                               int32_t *converged_med, int32_t *niter, double *resid, int32_t *converged, int32_t *nlv_out, int64_t *nzero);
+
 /* ---- Kennard-Stone and Duplex sampling without an n x n distance matrix (src/sampling.jl:40-148) ---------------------------------
  * Row indices are 0-based int64_t.  X n x p (ldx >= n) [loc], read only; a host X is staged once per call.  No atomics: two runs give identical
  * bits, and so do a host and a device X and an aligned and an unaligned one.  One rank only.

@@ -94,7 +94,7 @@ extern "C" int32_t jch_ctx_destroy(jch_ctx *ctx)
     for (jch_buf *b : {&ctx->gram, &ctx->xr, &ctx->yr, &ctx->xstage, &ctx->ystage, &ctx->wstage, &ctx->tbuf, &ctx->dnorm, &ctx->part,
                        &ctx->kpart, &ctx->small, &ctx->colpart, &ctx->gemm_b, &ctx->gemm_out, &ctx->xq, &ctx->tickets, &ctx->qz, &ctx->lw_work, &ctx->lw_xrm, &ctx->lvws, &ctx->lw_flags, &ctx->lw_screen,
                        &ctx->kg_ws, &ctx->dk_x, &ctx->dk_y, &ctx->dk_k, &ctx->dk_q, &ctx->dk_o, &ctx->dk_s, &ctx->kp_ws, &ctx->kc_vt, &ctx->pc_ws,
-                       &ctx->chol_inv, &ctx->chol_a, &ctx->chol_w, &ctx->chol_s, &ctx->kr_ws, &ctx->rp_stage, &ctx->rp_rows, &ctx->rp_coef, &ctx->cs_ws, &ctx->cs_part, &ctx->pc_vec, &ctx->xt_part, &ctx->xt_ws, &ctx->sel_ws, &ctx->sel_out, &ctx->st_t, &ctx->st_ms, &ctx->sp_ws, &ctx->kn_ws, &ctx->kd_ws, &ctx->gd_ws, &ctx->vp_ws})
+                       &ctx->chol_inv, &ctx->chol_a, &ctx->chol_w, &ctx->chol_s, &ctx->kr_ws, &ctx->rp_stage, &ctx->rp_rows, &ctx->rp_coef, &ctx->cs_ws, &ctx->cs_part, &ctx->pc_vec, &ctx->xt_part, &ctx->xt_ws, &ctx->sel_ws, &ctx->sel_out, &ctx->st_t, &ctx->st_ms, &ctx->sp_ws, &ctx->kn_ws, &ctx->kd_ws, &ctx->gd_ws, &ctx->vp_ws, &ctx->ms_ws})
         free_buf(*b);
     if (ctx->hstage) (void)hipHostFree(ctx->hstage);
     for (hipEvent_t ev : ctx->ev_pool) (void)hipEventDestroy(ev);

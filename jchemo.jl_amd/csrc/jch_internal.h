@@ -100,6 +100,7 @@ struct jch_ctx {
     jch_buf kn_ws;   // knn.hip: the search's lists ahead of the drop of `self`, the results of a host call, the sort buffers and class accumulators of shapes beyond the LDS
     jch_buf kd_ws;   // kde.hip: the bandwidth factors, class offsets and model dimensions of a call, the per-split partial sums, the staging of a host call
     jch_buf gd_ws;   // gda.hip: per entry, the vectors, one or two p x p matrices, the padded transposed factors and the staging of a host call
+    jch_buf ms_ws;   // medspa.hip: the distances, two centres, the per-workgroup partial rows and sums of a Weiszfeld step, its scalar record; the staging of a host call
     jch_buf vp_ws;   // viperm.hip: B, the slice partials, the sums and the range flag of a permutation pass; the staging of a host call
     const void *chol_L = nullptr;   // the factor the blocks in chol_inv belong to (null: none); a solve against another one is JCH_EINVAL
     int64_t chol_n = 0, chol_ld = 0;
@@ -353,6 +354,12 @@ int32_t jch_launch_xtdx(jch_ctx *ctx, const double *X, int64_t n, int p, int64_t
 // jch_colselect_reserve(ctx, p) first: the launcher itself reserves nothing and only enqueues.
 int32_t jch_colselect_reserve(jch_ctx *ctx, int64_t p);
 int32_t jch_launch_col_median_mad(jch_ctx *ctx, const double *X, int64_t n, int64_t p, int64_t ldx, double *med, double *mad);
+// medspa.hip: d[i] = |(x_i - c) / s| (c, s device p-vectors, s may be null: no division), the distances-only mode of the Weiszfeld pass: one read of X,
+// enqueued only, no workspace.  jch_spatial_median_dev: the whole loop of `colmedspa` on a device X into the device vector mu_dev (d_dev: the distances
+// to the last centre the loop stepped from, or null); reserves ctx->ms_ws and the selection's workspace, synchronises once per step.
+int32_t jch_launch_weiszfeld_dist(jch_ctx *ctx, const double *X, int64_t n, int p, int64_t ldx, const double *c, const double *sdiv, double *d);
+int32_t jch_spatial_median_dev(jch_ctx *ctx, const double *X, int64_t n, int p, int64_t ldx, double delta, int maxit, double *mu_dev, double *d_dev, int32_t *niter,
+                               double *h_last, int32_t *converged);
 // kmethod.hip: what the kernel-method entry points (dkplsr.hip, kplsr.hip, kpca.hip, krr.hip) share
 int32_t jch_check_kernel(jch_ctx *ctx, const char *who, int32_t kind, int32_t degree);   // kernel kind / degree, one rank only
 int32_t jch_launch_divcols(jch_ctx *ctx, double *A, int64_t lda, int64_t n, int64_t cols, const double *s_dev);   // A[:, k] /= s[k]

@@ -23,6 +23,10 @@
 // PCA (jch_pca_fit): the reference takes svd(sqrtD Xc).  Here P and sv^2 are the leading eigenpairs of G (the reference's own `pcaeigen` route)
 // from the block subspace iteration kpca uses (jch_eig_lead, kpca.hip), which only ever touches the p x p matrix G; T = cscale(X) P is one
 // jch_transform.  scal = true rescales G by xscales = sqrt(diag G) instead of touching X; sstot = trace(G).
+//
+// Spherical PCA (jch_pcasph_fit, src/pcasph.jl:60-92): the same pass with mu = the spatial median (medspa.hip) and the row weights
+// w_i / r_i^2, r_i the norm of the centred (scaled) row, is the Gram of the rows projected on the unit sphere; P from the same iteration, T by
+// jch_transform, sv = the MADs of T / r (colselect.hip), everything reordered by sv.
 #include <math.h>
 
 #include <algorithm>
@@ -377,5 +381,138 @@ extern "C" int32_t jch_pca_fit(jch_ctx *ctx, int32_t loc, const double *X, int64
     if (niter) *niter = eg.niter;
     if (nlv_out) *nlv_out = A;
     if (converged) *converged = eg.converged ? 1 : 0;   // the iteration's own decision (on |theta_1|)
+    return JCH_OK;
+}
+
+// ---- spherical PCA (src/pcasph.jl:60-92) ----------------------------------------------------------------------------------------
+// dw[i] = wn[i] / r[i]^2: the row weight of the Gram of the rows projected on the unit sphere; a row AT the centre (r = 0) gets 0
+__global__ __launch_bounds__(XT_NT) void k_ph_rowweight(const double *__restrict__ r, const double *__restrict__ wn, int64_t n, double *__restrict__ dw)
+{
+    for (int64_t i = (int64_t)blockIdx.x * XT_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * XT_NT) {
+        const double ri = r[i];
+        dw[i] = ri == 0.0 ? 0.0 : wn[i] / (ri * ri);
+    }
+}
+
+// *out = the number of rows with r = 0 (one workgroup, integer counts)
+__global__ __launch_bounds__(XT_NT) void k_ph_nzero(const double *__restrict__ r, int64_t n, long long *out)
+{
+    __shared__ long long scr[XT_NT];
+    long long c = 0;
+    for (int64_t i = threadIdx.x; i < n; i += XT_NT) c += r[i] == 0.0 ? 1 : 0;
+    scr[threadIdx.x] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long s = 0;
+        for (int t = 0; t < XT_NT; ++t) s += scr[t];
+        *out = s;
+    }
+}
+
+// zT[i, k] = T[i, k] / r[i] (`zX * P`, :84), a zero row where r = 0
+__global__ __launch_bounds__(XT_NT) void k_ph_divrows(const double *__restrict__ T, const double *__restrict__ r, int64_t n, int a, double *__restrict__ zT)
+{
+    const int64_t tot = n * a;
+    for (int64_t e = (int64_t)blockIdx.x * XT_NT + threadIdx.x; e < tot; e += (int64_t)gridDim.x * XT_NT) {
+        const double ri = r[e % n];
+        zT[e] = ri == 0.0 ? 0.0 : T[e] / ri;
+    }
+}
+
+extern "C" int32_t jch_pcasph_fit(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *weights, int32_t nlv, int32_t typc,
+                                  double delta, int32_t maxit_med, int32_t scal, double tol, int32_t maxit, double *T, double *P, double *sv, double *eig,
+                                  double *xmeans, double *xscales, double *weights_norm, double *sstot, double *colvar, int32_t *niter_med,
+                                  int32_t *converged_med, int32_t *niter, double *resid, int32_t *converged, int32_t *nlv_out, int64_t *nzero)
+{
+    static const char *who = "jch_pcasph_fit";
+    if (!ctx) return JCH_EINVAL;
+    JCH_TRY(xt_check(ctx, who, loc, X, n, p, ldx));
+    if (nlv < 1) return jch_fail(ctx, JCH_EINVAL, "%s: nlv = %d must be >= 1", who, nlv);
+    if (maxit < 1 || maxit_med < 1) return jch_fail(ctx, JCH_EINVAL, "%s: maxit = %d and maxit_med = %d must be >= 1", who, maxit, maxit_med);
+    if (!(tol > 0.0) || !(delta > 0.0)) return jch_fail(ctx, JCH_EINVAL, "%s: tol and delta must be > 0", who);
+    if (typc != JCH_CENT_MEDSPA && typc != JCH_CENT_MEAN) return jch_fail(ctx, JCH_EINVAL, "%s: bad typc %d", who, typc);
+    JCH_HIP(ctx, hipSetDevice(ctx->device));
+    const bool host = loc == JCH_LOC_HOST;
+    const int pi = (int)p;
+    const int A = (int)std::min<int64_t>(nlv, std::min(n, p));   // src/pcasph.jl:63
+    const size_t nn = (size_t)n;
+    jch_carve cv;
+    const size_t oG = cv.take((size_t)p * p), ow = cv.take(nn), owr = cv.take(nn), omean = cv.take(pi), omu = cv.take(pi), ostd = cv.take(pi), ohdr = cv.take(8),
+                 otr = cv.take(8), ocnt = cv.take(8), orr = cv.take(nn), odw = cv.take(nn), oT = cv.take(nn * A), oz = cv.take(nn * A), omed = cv.take(A),
+                 omad = cv.take(A);
+    JCH_TRY(jch_reserve(ctx, ctx->xt_ws, sizeof(double) * cv.off));
+    JCH_TRY(jch_colselect_reserve(ctx, p));
+    double *ws = (double *)ctx->xt_ws.ptr;
+    double *G = ws + oG, *wn = ws + ow, *mean = ws + omean, *mu = ws + omu, *sd = ws + ostd, *trd = ws + otr, *rr = ws + orr, *dw = ws + odw, *Tw = ws + oT,
+           *zT = ws + oz;
+    long long *cntd = (long long *)(ws + ocnt);
+    std::vector<double> xm((size_t)pi), xs((size_t)pi, 1.0), sdh((size_t)pi), Ph((size_t)pi * A), madh((size_t)A);
+    std::vector<int> perm((size_t)A);
+    double trh = 0.0;
+    long long cnth = 0;
+    int32_t nit_med = 0, conv_med = 1;
+    jch_eig_lead_out eg;
+    JCH_TRY(jch_synced(ctx, true, [&]() -> int32_t {
+        xt_in in;
+        JCH_TRY(xt_stage(ctx, loc, X, n, p, ldx, weights, ws + owr, &in));
+        // ---- weights, the weighted mean and colstd about it (:64, :68, :72)
+        JCH_TRY(jch_launch_weights(ctx, in.dw, n, wn, ws + ohdr));
+        JCH_TRY(jch_covsel_pass(ctx, in.dX, n, p, in.ldxd, nullptr, wn, 1, n, mean));
+        JCH_TRY(jch_launch_moments(ctx, in.dX, in.ldxd, nullptr, 0, wn, n, pi, 0, mean, sd));
+        // ---- xmeans (:65-69)
+        if (typc == JCH_CENT_MEDSPA) JCH_TRY(jch_spatial_median_dev(ctx, in.dX, n, pi, in.ldxd, delta, maxit_med, mu, nullptr, &nit_med, nullptr, &conv_med));
+        else JCH_HIP(ctx, hipMemcpyAsync(mu, mean, sizeof(double) * (size_t)pi, hipMemcpyDeviceToDevice, ctx->stream));
+        // ---- r = the row norms of Xs (:79), G = Xs' diag(w / r^2) Xs (:80-82 is the SVD of sqrtw .* zX)
+        JCH_TRY(jch_launch_weiszfeld_dist(ctx, in.dX, n, pi, in.ldxd, mu, scal ? sd : nullptr, rr));
+        hipLaunchKernelGGL(k_ph_rowweight, dim3(jch_grid1(ctx, n)), dim3(XT_NT), 0, ctx->stream, (const double *)rr, (const double *)wn, n, dw);
+        hipLaunchKernelGGL(k_ph_nzero, dim3(1), dim3(XT_NT), 0, ctx->stream, (const double *)rr, n, cntd);
+        JCH_TRY(jch_launch_xtdx(ctx, in.dX, n, pi, in.ldxd, mu, dw, G, p));
+        if (scal) hipLaunchKernelGGL(k_xt_rescale, dim3(jch_grid1(ctx, p * p)), dim3(XT_NT), 0, ctx->stream, G, p, pi, (const double *)sd);
+        hipLaunchKernelGGL(k_xt_trace, dim3(1), dim3(XT_NT), 0, ctx->stream, (const double *)G, p, pi, trd);
+        JCH_HIP(ctx, hipGetLastError());
+        JCH_HIP(ctx, hipMemcpyAsync(xm.data(), mu, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(sdh.data(), sd, sizeof(double) * (size_t)pi, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(&trh, trd, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipMemcpyAsync(&cnth, cntd, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        // ---- P (:83)
+        JCH_TRY(jch_eig_lead(ctx, G, p, p, nullptr, A, tol, maxit, &eg));
+        JCH_HIP(ctx, hipMemcpyAsync(Ph.data(), eg.X, sizeof(double) * Ph.size(), hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (scal) xs = sdh;
+        // ---- T = Xs P (:86), zT = T / r (:84), sv = colmad(zT) (:85)
+        JCH_TRY(jch_transform(ctx, JCH_LOC_DEVICE, in.dX, n, p, in.ldxd, xm.data(), xs.data(), Ph.data(), A, Tw, n));
+        hipLaunchKernelGGL(k_ph_divrows, dim3(jch_grid1(ctx, n * A)), dim3(XT_NT), 0, ctx->stream, (const double *)Tw, (const double *)rr, n, A, zT);
+        JCH_HIP(ctx, hipGetLastError());
+        JCH_TRY(jch_launch_col_median_mad(ctx, zT, n, A, n, ws + omed, ws + omad));
+        JCH_HIP(ctx, hipMemcpyAsync(madh.data(), ws + omad, sizeof(double) * (size_t)A, hipMemcpyDeviceToHost, ctx->stream));
+        JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        // ---- the order of sv, descending, ties in eigen order (:87-90)
+        for (int e = 0; e < A; ++e) perm[e] = e;
+        std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return madh[a] > madh[b]; });
+        if (T)
+            for (int e = 0; e < A; ++e)
+                JCH_HIP(ctx, hipMemcpyAsync(T + (size_t)e * nn, Tw + (size_t)perm[e] * nn, sizeof(double) * nn, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                                            ctx->stream));
+        if (weights_norm) JCH_HIP(ctx, hipMemcpyAsync(weights_norm, wn, sizeof(double) * nn, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+        return JCH_OK;
+    }));
+    for (int e = 0; e < A; ++e) {
+        const int s = perm[e];
+        if (sv) sv[e] = madh[s];
+        if (eig) eig[e] = eg.theta[s];
+        if (resid) resid[e] = eg.resid[s];
+        if (P) std::copy(Ph.begin() + (size_t)s * pi, Ph.begin() + (size_t)(s + 1) * pi, P + (size_t)e * pi);
+    }
+    if (xmeans) std::copy(xm.begin(), xm.end(), xmeans);
+    if (xscales) std::copy(xs.begin(), xs.end(), xscales);
+    if (colvar)
+        for (int j = 0; j < pi; ++j) colvar[j] = sdh[j] * sdh[j];
+    if (sstot) *sstot = trh;
+    if (niter_med) *niter_med = nit_med;
+    if (converged_med) *converged_med = conv_med;
+    if (niter) *niter = eg.niter;
+    if (nlv_out) *nlv_out = A;
+    if (converged) *converged = eg.converged ? 1 : 0;
+    if (nzero) *nzero = (int64_t)cnth;
     return JCH_OK;
 }

@@ -8,6 +8,7 @@ from .krr import Krr, Krrda, gridscorelb, krr, krr_, krr_coef, krr_predict, krrd
 from .preproc import Savgk, detrend, detrend_, fdif, mavg, mavg_, mavg_runmean, savgk, savgol, savgol_, snv, snv_  # noqa: F401
 from .covsel import Covsel, Covselr, Mlr, covsel, covsel_, covselr, covselr_coef, covselr_predict  # noqa: F401
 from .pca import Pca, Pcr, pca_summary, pca_transform, pcaeigen, pcaeigen_, pcaeigenk, pcaeigenk_, pcasvd, pcasvd_, pcr, pcr_  # noqa: F401
+from .robpca import colmedspa, pcasph, pcasph_, weiszfeld_step  # noqa: F401
 from .occ import Occod, OccPred, Occsd, Occsdod, occ_predict, occod, occsd, occsdod, row_resid_ss  # noqa: F401
 from .stah import Occstah, Stah, col_median_mad, colmad, occstah, stah  # noqa: F401
 from .samp import Samp, Sampcla, Sampdp, farthest_pair, maxmin_select, sampcla, sampdp, sampks, sampsys  # noqa: F401

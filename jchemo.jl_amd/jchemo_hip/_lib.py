@@ -41,6 +41,7 @@ SYMBOLS = (
     "jch_knn_gda", "jch_lwplsda_predict_prepared",
     "jch_perm_fill", "jch_perm_score_sums",
     "jch_row_resid_ss_lv", "jch_lwplsravg_predict_prepared",
+    "jch_weiszfeld_step", "jch_spatial_median", "jch_pcasph_fit",
 )
 
 
@@ -142,6 +143,10 @@ def load():
     L.jch_row_resid_ss.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, i64, dp]
     L.jch_row_resid_ss_lv.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i64, i64, dp, i64, i32, i32, dp, i64]
     L.jch_col_median_mad.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, i32]
+    L.jch_weiszfeld_step.argtypes = [vp, i32, dp, i64, i64, i64, dp, f64, f64, dp, dp, C.POINTER(f64), C.POINTER(f64), C.POINTER(i64)]
+    L.jch_spatial_median.argtypes = [vp, i32, dp, i64, i64, i64, f64, i32, dp, dp, C.POINTER(i32), C.POINTER(f64), C.POINTER(i32)]
+    L.jch_pcasph_fit.argtypes = ([vp, i32, dp, i64, i64, i64, dp, i32, i32, f64, i32, i32, f64, i32] + [dp] * 7 + [C.POINTER(f64), dp] + [C.POINTER(i32)] * 3
+                                 + [dp] + [C.POINTER(i32)] * 2 + [C.POINTER(i64)])
     L.jch_stah.argtypes = [vp, i32, dp, i64, i64, i64, dp, dp, dp, i64, i64, i32, dp, dp, dp]
     L.jch_farthest_pair.argtypes = [vp, i32, dp, i64, i64, i64, dp, i32, dp, dp]
     L.jch_maxmin_select.argtypes = [vp, i32, dp, i64, i64, i64, i32, dp, i64, dp, dp]

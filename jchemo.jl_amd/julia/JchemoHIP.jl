@@ -37,6 +37,7 @@ export Plsr, Lwplsr, plskern, plskern!, plsnipals, plsnipals!, plssimp, plssimp!
        snv, snv!, detrend, detrend!, savgol, savgol!, savgk, mavg, mavg!, mavg_runmean, fdif,
        Covsel, Covselr, covsel, covsel!, covselr,
        Pca, Pcr, pcasvd, pcasvd!, pcaeigen, pcaeigen!, pcaeigenk, pcaeigenk!, pcr, pcr!, xtdx,
+       colmedspa, pcasph, pcasph!,
        Occsd, Occod, Occsdod, occsd, occod, occsdod, row_resid_ss, row_resid_ss_lv,
        Occstah, occstah, stah, colmad, col_median_mad,
        sampks, sampdp, sampsys, sampcla, farthest_pair, maxmin_select,
@@ -1598,6 +1599,56 @@ end
 const pcasvd! = pcasvd
 const pcaeigen! = pcaeigen
 const pcaeigenk! = pcaeigenk
+
+# ---- spatial median and spherical PCA (src/colmedspa.jl, src/pcasph.jl) over jch_spatial_median and jch_pcasph_fit (DESIGN.md §28).  Deviations:
+# `maxit` bounds the Weiszfeld loop (the reference has no bound); P comes from the Gram of the projected rows, not from an SVD of a transposed copy;
+# a row AT the centre gets weight 0 and a warning instead of NaN; `pcasph!` does not leave the centred X behind. ----------------------------------
+"""`colmedspa(X; delta = 1e-6)` — src/colmedspa.jl:4-33 through jch_spatial_median: the spatial median of the rows of X (a host vector); X is only
+read, once per Weiszfeld step.  `maxit` bounds the steps; reaching it warns and returns the last centre."""
+function colmedspa(X; delta = 1e-6, maxit = 1000, ctx = default_ctx())
+    delta > 0 || throw(ArgumentError("delta = $delta must be > 0"))
+    maxit >= 1 || throw(ArgumentError("maxit = $maxit must be >= 1"))
+    X = _in(X); n, p = size(X)
+    mu = zeros(p)
+    nit = Ref{Int32}(0); h = Ref{Float64}(0.0); cvg = Ref{Int32}(0)
+    GC.@preserve X check(ctx, ccall((:jch_spatial_median, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Int32}, Ref{Float64}, Ref{Int32}),
+        ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), Float64(delta), Int32(maxit), mu, Ptr{Float64}(C_NULL), nit, h, cvg))
+    cvg[] != 0 || @warn "colmedspa: no convergence in $(nit[]) steps" last_step = h[] threshold = delta * sqrt(p)
+    mu
+end
+
+"""`pcasph(X, weights; nlv, typc = "medspa", delta = .001, scal = false)` — src/pcasph.jl:54-92 through jch_pcasph_fit; X is only read.  Returns a
+`Pca`: sv = the MADs of the projected scores, eig = the eigenvalues of the Gram of the projected rows, sstot its trace."""
+function pcasph(X, weights = nothing; nlv, typc = "medspa", delta = .001, scal = false, ctx = default_ctx(), eig_tol = 1e-10, eig_maxit = 300)
+    nlv >= 1 || throw(ArgumentError("nlv = $nlv must be >= 1"))
+    typc in ("medspa", "mean") || throw(ArgumentError("typc = $typc must be \"medspa\" or \"mean\""))
+    delta > 0 || throw(ArgumentError("delta = $delta must be > 0"))
+    eig_maxit >= 1 || throw(ArgumentError("eig_maxit = $eig_maxit must be >= 1"))
+    eig_tol > 0 || throw(ArgumentError("eig_tol = $eig_tol must be > 0"))
+    X = _in(X); n, p = size(X)
+    weights = _w(weights, X)
+    weights === nothing || length(weights) == n || throw(DimensionMismatch("weights has $(length(weights)) entries, X has $n rows"))
+    a = min(nlv, n, p)                                                   # src/pcasph.jl:63
+    T = _similar(X, n, a); wn = _similar(X, n)
+    P = zeros(p, a); sv = zeros(a); eig = zeros(a); res = zeros(a); xm = zeros(p); xs = zeros(p); cvar = zeros(p)
+    sst = Ref{Float64}(0.0); nitm = Ref{Int32}(0); cvgm = Ref{Int32}(0); nit = Ref{Int32}(0); cvg = Ref{Int32}(0); got = Ref{Int32}(0); nz = Ref{Int64}(0)
+    GC.@preserve X weights T wn check(ctx, ccall((:jch_pcasph_fit, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int32, Int32, Float64, Int32, Int32, Float64, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ptr{Float64},
+         Ref{Int32}, Ref{Int32}, Ref{Int32}, Ptr{Float64}, Ref{Int32}, Ref{Int32}, Ref{Int64}),
+        ctx.h, _loc(X), pointer(X), n, p, max(stride(X, 2), n), weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights),
+        Int32(nlv), Int32(typc == "medspa" ? 0 : 1), Float64(delta), Int32(1000), Int32(scal ? 1 : 0), Float64(eig_tol), Int32(eig_maxit),
+        pointer(T), P, sv, eig, xm, xs, pointer(wn), sst, cvar, nitm, cvgm, nit, res, cvg, got, nz))
+    cvgm[] != 0 || @warn "pcasph: the spatial median did not converge in $(nitm[]) steps"
+    nz[] == 0 || @warn "pcasph: $(nz[]) row(s) lie at the centre (norm 0): they carry no direction and got weight 0"
+    conv = cvg[] != 0
+    conv || @warn "pcasph: the subspace iteration did not converge in $(nit[]) iterations" maxresid = maximum(res) tol = eig_tol * eig[1]
+    Pca(T, P, sv, xm, xs, wn, Int(nit[]), conv, eig, sst[], cvar, res, conv)
+end
+function pcasph!(X, weights = nothing; kwargs...)      # src/pcasph.jl:60 centres X in place; the fit here never writes X
+    pcasph(X, weights; kwargs...)
+end
 
 "`transform(object::Pca, X; nlv)` — src/pcasvd.jl:110-115: cscale(X, xmeans, xscales) * P[:, 1:nlv] (jch_affine_gemm)."
 function transform(object::Pca, X; nlv = nothing, ctx = default_ctx())
