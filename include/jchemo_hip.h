@@ -97,6 +97,41 @@ JCH_API int32_t jch_loopback_group_create(int32_t nranks, void **group_out);
 JCH_API int32_t jch_loopback_group_destroy(void *group);
 JCH_API int32_t jch_ctx_comm_init_loopback(jch_ctx *ctx, void *group, int32_t rank);
 
+/* ---- joined ctx contract: what every entry does on a ctx that was joined to a communicator of N > 1 ranks -----------------------
+ * (jch_ctx_comm_init, jch_ctx_p2p_import, jch_ctx_comm_init_loopback).  Every exported entry is in exactly one class; the lists below
+ * are read by tests/test_joined_ctx_static.py (a new export cannot arrive unclassified) and held by tests/test_gpu_joined_ctx.py.
+ *
+ * Class C -- collective.  Every rank makes the same call, with the same shapes but for the row count, on its own rows.  Outputs with one
+ *   entry per row (T, weights_norm) are per shard; everything else is replicated bit-identically on every rank and equals the result on
+ *   the concatenated rows up to the summation order.  A rank that does not call leaves the others waiting.
+ *   C: jch_plskern_fit jch_plsnipals_fit jch_plssimp_fit jch_plsrosa_fit jch_plswold_fit jch_plskern_fit_scaled
+ *   C: jch_col_stats jch_weighted_ss jch_weighted_cov jch_score_sums jch_score_sums_lv jch_ctx_allreduce_probe
+ *
+ * Class L -- rank-local.  The ranks are replicas or hold independent rows; the call enters no collective, may be made by any subset of the
+ *   ranks with any shapes, and returns exactly the bytes the same call returns on a ctx without a communicator.  This is what the replica
+ *   scheme of kNN-LWPLSR needs (the global model fitted row-sharded, the queries split over the ranks, every rank holding
+ *   all of Xtrain): the per-query jch_plskern_fit / jch_predict / jch_transform of the generic paths run with the communicator out of
+ *   reach (csrc/jch_internal.h jch_comm_off) and the ctx is handed back joined.
+ *   L: jch_affine_gemm jch_transform jch_predict jch_rows_standardize jch_rows_project_out jch_rows_fir
+ *   L: jch_row_resid_ss jch_row_resid_ss_lv jch_fill_uniform jch_chol_factor jch_chol_solve jch_chol_inv_fro2 jch_kc_panel jch_covsel_pass
+ *   L: jch_lwplsr_predict jch_lwplsr_prepare jch_lwplsr_predict_prepared jch_lwplsr_release jch_lwplsr_add_query_map
+ *   L: jch_knn_prepare jch_knn_release jch_knn_search jch_knn_wmean jch_knn_vote jch_knn_gather_median jch_knn_wls jch_knn_gda
+ *   L: jch_lwplsda_predict_prepared jch_lwplsravg_predict_prepared jch_kde_dens
+ *
+ * Class R -- refused.  The algorithm needs every row at once (a median, a Gram matrix, a selection over all rows) and has no replica
+ *   use: the call returns JCH_EINVAL with "one rank only (communicator of N)" in jch_last_error before any device work, writes no output
+ *   and enters no collective.  The argument checks that come first are those of the unjoined call.
+ *   R: jch_kernel_gram jch_dkplsr_fit jch_dkplsr_transform jch_dkplsr_predict jch_kplsr_fit jch_kplsr_transform jch_kplsr_predict
+ *   R: jch_kpca_fit jch_krr_fit jch_krr_solve jch_covsel_fit jch_xtdx jch_pca_fit jch_pcasph_fit jch_col_median_mad jch_stah
+ *   R: jch_weiszfeld_step jch_spatial_median jch_farthest_pair jch_maxmin_select jch_class_cov jch_gauss_factor jch_mahsq_chol
+ *   R: jch_perm_fill jch_perm_score_sums
+ *
+ * Class M -- ctx, communicator, p2p, profiling and counter management: what joins, inspects and frees a ctx.  Not covered by the above.
+ *   M: jch_version jch_ctx_create jch_ctx_destroy jch_last_error jch_comm_unique_id jch_ctx_comm_init jch_ctx_comm_info
+ *   M: jch_ctx_p2p_export jch_ctx_p2p_import jch_ctx_p2p_enable jch_loopback_group_create jch_loopback_group_destroy
+ *   M: jch_ctx_comm_init_loopback jch_ctx_set_profiling jch_ctx_get_profile jch_ctx_synchronize jch_ctx_get_counter
+ * ---- end of the joined ctx contract */
+
 typedef struct jch_pls_desc {
     int64_t n;       /* rows held by THIS rank (all rows when single-GPU) */
     int64_t p;       /* columns of X */
@@ -170,7 +205,9 @@ JCH_API int32_t jch_plskern_fit_scaled(jch_ctx *ctx, const jch_pls_desc *desc, v
                         double *yscales, double *weights_norm, int32_t *nlv_out);
 
 /* jch_col_stats — weighted column means and (stds != NULL) uncorrected standard deviations: `colmean`, `colstd`
- * (src/utility.jl:193-195,312-323) on their own.  X n x p [loc], weights n or NULL [loc]; means, stds (p) HOST. */
+ * (src/utility.jl:193-195,312-323) on their own.  X n x p [loc], weights n or NULL [loc]; means, stds (p) HOST.
+ * Collective on a joined ctx (the prologue kernels of the fits: the weight sum and the moments are all-reduced): every rank calls with its
+ * own rows and weights and gets the statistics of the concatenated rows, the same bits on every rank. */
 JCH_API int32_t jch_col_stats(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *weights,
                       double *means, double *stds);
 
@@ -257,6 +294,8 @@ JCH_API int32_t jch_weighted_ss(jch_ctx *ctx, int32_t loc, const double *X, int6
  * reference's own schedule (src/locwlv.jl:18-39); slower, never absent.
  * The constant-y shortcut of src/locwlv.jl:25-28 applies to q == 1 only, as in the reference.
  * Neighbours at equal distance are ordered by their row index.
+ * Rank-local on a joined ctx (class L of the joined ctx contract; so are the prepared forms and the discrimination and averaging entries
+ * built on them): the per-query fits of the generic path are one rank's own and never meet another rank's.
  */
 JCH_API int32_t jch_lwplsr_predict(jch_ctx *ctx, int32_t loc, const double *Xtrain, int64_t n, int64_t p, int64_t ldx,
                                    const double *Ytrain, int64_t q, int64_t ldy, const double *Ztrain, int64_t ldzt,
@@ -293,7 +332,8 @@ JCH_API int32_t jch_lwplsr_add_query_map(jch_ctx *ctx, jch_lwplsr_model *model, 
  * `Statistics.cov(Xtrain, corrected = false)` of getknn's Mahalanobis branch (src/getknn.jl:38; with nlvdis = 0 the
  * reference whitens the raw X, src/lwplsr.jl:21: d = p).  d <= 64: the X'DY kernels of the fit with Y = A; wider: the centred
  * row-major copy + the tiled MFMA SYRK of the opt-in algorithm #2.  A n x d [loc]; S (column-major d x d) and mu (d, may be
- * NULL) HOST. */
+ * NULL) HOST.  Collective on a joined ctx, on both paths (weight sum, means and the d x d sums are all-reduced): every rank calls with
+ * its own rows and gets S and mu of the concatenated rows, the same bits on every rank. */
 JCH_API int32_t jch_weighted_cov(jch_ctx *ctx, int32_t loc, const double *A, int64_t n, int64_t d, int64_t lda,
                                  const double *weights, double *S, double *mu);
 
@@ -572,7 +612,7 @@ JCH_API int32_t jch_pca_fit(jch_ctx *ctx, int32_t loc, const double *X, int64_t 
  * B (p x k, ldb >= p) HOST.  k = 0 is valid (Z and B may then be NULL): the centred row sums of squares.  Any m, p, k: coefficients that do not fit in
  * LDS are read from L2, more than 64 score columns are walked in chunks.  Rows >= m and columns >= p are never read.  Every sum has a fixed order and
  * no atomics: two runs give identical bits, and so do a host and a device X or Z and an aligned and an unaligned one.  A NaN at X[i, j] or Z[i, l]
- * reaches out[i] only.  One rank only. */
+ * reaches out[i] only.  Rank-local on a joined ctx: the rows are independent, no collective (class L of the joined ctx contract). */
 JCH_API int32_t jch_row_resid_ss(jch_ctx *ctx, int32_t loc, const double *X, int64_t m, int64_t p, int64_t ldx, const double *shift, const double *Z,
                                  int64_t k, int64_t ldz, const double *B, int64_t ldb, double *out);
 /* jch_row_resid_ss_lv -- the nested form, every level a_lo .. a_hi in ONE read of X (src/wshenk.jl:59-62 forms nlv `xresid` matrices):
@@ -582,7 +622,7 @@ JCH_API int32_t jch_row_resid_ss(jch_ctx *ctx, int32_t loc, const double *X, int
  * expanded form).  Any m, p, kz: one read of X holds for a_hi <= 32; beyond, every further 32 levels are one more launch that reads X again and replays the terms before its chunk.  Rows >= m, columns >= p and score columns >= a_hi
  * are never read; out beyond row m of a column is never written.  Every sum has a fixed order and no atomics: two runs give identical bits, and so do
  * a host and a device X or Z and an aligned and an unaligned one, and level a has the same bits whatever a_lo and a_hi.  A NaN at X[i, j] or Z[i, l]
- * reaches row i only.  One rank only. */
+ * reaches row i only.  Rank-local on a joined ctx, like jch_row_resid_ss. */
 JCH_API int32_t jch_row_resid_ss_lv(jch_ctx *ctx, int32_t loc, const double *X, int64_t m, int64_t p, int64_t ldx, const double *shift, const double *Z,
                                     int64_t kz, int64_t ldz, const double *B, int64_t ldb, int32_t a_lo, int32_t a_hi, double *out, int64_t ldo);
 
@@ -594,7 +634,8 @@ JCH_API int32_t jch_row_resid_ss_lv(jch_ctx *ctx, int32_t loc, const double *X, 
  * rank (n - 1) / 2; even n: Julia's middle(lo, hi) = lo / 2 + hi / 2 of ranks n / 2 - 1 and n / 2.  Any n >= 1 and p >= 1; rows >= n are never read; row
  * indices and counts are 64-bit.  Integer counters only: two runs give identical bits, and so do a host and a device X and an aligned and an
  * unaligned one.  A column holding a NaN gets med = mad = NaN and no other column is touched; +-Inf are ordinary ordered values (a NaN deviation
- * Inf - Inf makes that column's MAD NaN); the sign of a zero result is not specified. */
+ * Inf - Inf makes that column's MAD NaN); the sign of a zero result is not specified.  One rank only (a median needs every row: a
+ * communicator of more ranks is JCH_EINVAL before any device work, like jch_stah). */
 JCH_API int32_t jch_col_median_mad(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, double *med, double *mad, int32_t out_loc);
 /* jch_stah -- `stah` (src/stah.jl:37-58, fit != 0) and the distances of `predict(::Occstah, X)` (src/occstah.jl:55-73, fit = 0) in one entry:
  * d[i] = max_j |(t_ij - mu_j) / s_j| with T = ((X - 1 mu_scal') diag(1 / s_scal)) P.  X n x p (ldx >= n) and d (n) [loc], X read only; mu_scal and
@@ -706,7 +747,8 @@ JCH_API int32_t jch_chol_inv_fro2(jch_ctx *ctx, const double *L, int64_t n, int6
  *   entry of row self[i] if it is among them and of the last entry otherwise (also for self[i] < 0); weights and dmed are computed after the drop,
  *   over the k kept distances.  A query holding a NaN gets NaN distances, the in-range rows 0 .. k-1 and weights 1, and disturbs no other query.
  *   With loc and out_loc both JCH_LOC_DEVICE the call only enqueues on the ctx stream; otherwise it returns synchronised.  The screen counters
- *   (JCH_COUNTER_KNN_SCREENED / _REDONE) and the handle's "stop screening" rule follow host-output calls only.  One rank only.
+ *   (JCH_COUNTER_KNN_SCREENED / _REDONE) and the handle's "stop screening" rule follow host-output calls only.  All jch_knn_* entries are
+ *   rank-local on a joined ctx (class L of the joined ctx contract): every rank searches its own handle for its own queries, no collective.
  * jch_knn_wmean -- pred[i, c] = sum_j (w_ij / sum_j w_ij) Y[ind_ij, c] (`mweight` + `colmean`, src/knnr.jl:120-124).  Y n x q (ldy >= n), ind and w
  *   [m][k], pred m x q column-major (ld m), all [loc].  Fixed summation order (per query one wave: lane l adds the terms l, l + 64, ... in order, the
  *   64 partial sums combine in a fixed butterfly), no atomics: two runs give identical bits.  Error per element <= 4 (k + 4) 2^-53 sum_j w~_ij |y_ij|.
@@ -750,7 +792,7 @@ JCH_API int32_t jch_knn_gather_median(jch_ctx *ctx, int32_t loc, const double *v
  *   lives in LDS while 8 ((d + q) (k | 1) + 2 k + 3 d + q + ceil(k / 2)) bytes <= 150 KiB, beyond that in the ctx workspace (the same device code,
  *   slower, never absent).  The entry first writes a row-major copy [X | Y] (n (d + q) doubles) into the ctx workspace.  It reserves the kNN
  *   workspace only: the X copy a fit left for JCH_REUSE_XCOPY survives.  With loc JCH_LOC_DEVICE the call only enqueues on the ctx stream;
- *   otherwise it returns synchronised.  One rank only. */
+ *   otherwise it returns synchronised.  Rank-local on a joined ctx (class L): one QR per query, no collective. */
 JCH_API int32_t jch_knn_wls(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t d, int64_t ldx, const double *Y, int64_t q, int64_t ldy,
                             const double *Xq, int64_t m, int64_t ldq, const int32_t *ind, const double *w, int32_t k, double *pred, int32_t *info);
 
@@ -803,7 +845,8 @@ JCH_API int32_t jch_lwplsda_predict_prepared(jch_ctx *ctx, const jch_lwplsr_mode
  *   rss_r and rss_b [m][hi] (typf = 1 only), info [m], ind_out / dist_out / w_out [m][k].
  *   info[i] (typf = 1; 0 throughout for typf = 0): 0 = fitted; 1 = a constant univariate y in the neighbourhood (src/locw.jl:34-36): pred = that value, the
  *   wlv and rss rows NaN; 2 = a Shenk norm of lo..hi is 0 or not finite: the reference's arithmetic gives NaN there and so do pred[i] and wlv.
- * Outside the envelope of the p-space kernel (jch_lwplsda_predict_prepared's): JCH_EINVAL with a message naming k, p, q, nlv.  One rank only. */
+ * Outside the envelope of the p-space kernel (jch_lwplsda_predict_prepared's): JCH_EINVAL with a message naming k, p, q, nlv.  Rank-local on a
+ * joined ctx (class L): the ranks are replicas that hold the same handle and split the queries; no collective. */
 JCH_API int32_t jch_lwplsravg_predict_prepared(jch_ctx *ctx, const jch_lwplsr_model *model, int32_t loc, const double *Zq, int64_t ldzq, const double *Xq,
                                                int64_t m, int64_t ldxq, int32_t k, double h, double tol, int32_t scal, int32_t nlv_lo, int32_t nlv_hi,
                                                int32_t typf, double *pred, double *pred_lv, double *wlv, double *rss_r, double *rss_b, int32_t *info,

@@ -216,6 +216,7 @@ extern "C" int32_t jch_col_median_mad(jch_ctx *ctx, int32_t loc, const double *X
     if (!X || !med || n < 1 || p < 1 || ldx < n) return jch_fail(ctx, JCH_EINVAL, "jch_col_median_mad: bad arguments");
     if ((loc != JCH_LOC_HOST && loc != JCH_LOC_DEVICE) || (out_loc != JCH_LOC_HOST && out_loc != JCH_LOC_DEVICE))
         return jch_fail(ctx, JCH_EINVAL, "jch_col_median_mad: bad loc");
+    if (ctx->nranks > 1) return jch_fail(ctx, JCH_EINVAL, "jch_col_median_mad: one rank only (communicator of %d)", ctx->nranks);   // a median needs every row
     JCH_HIP(ctx, hipSetDevice(ctx->device));
     JCH_TRY(jch_colselect_reserve(ctx, p));
     if (loc == JCH_LOC_HOST) JCH_TRY(jch_reserve(ctx, ctx->xq, sizeof(double) * (size_t)n * (size_t)p));

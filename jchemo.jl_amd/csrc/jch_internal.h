@@ -179,6 +179,27 @@ inline int32_t jch_reserve_xr(jch_ctx *ctx, size_t bytes, bool keep_copy = false
 }
 int32_t jch_reserve_host(jch_ctx *ctx, size_t bytes);   // ctx->hstage (pinned)
 int32_t jch_allreduce_f64(jch_ctx *ctx, double *dev_buf, size_t count);  // no-op when nranks == 1
+// The communicator out of reach for a scope: a rank-local entry (include/jchemo_hip.h, "what an entry does on a joined ctx") that goes
+// through code which is a collective on a joined ctx — the per-query jch_plskern_fit of the local models: the other ranks are fitting
+// OTHER queries, or none — runs it as the one-rank code it is.  Everything jch_allreduce_f64, jch_allreduce_slices, the fits' shard
+// logic and the inbox fusion of the small-state kernels look at is taken away and put back on every way out.
+struct jch_comm_off {
+    jch_ctx *ctx;
+    void *comm, *loop;
+    int nranks, rank;
+    bool p2p_ready;
+    explicit jch_comm_off(jch_ctx *c) : ctx(c), comm(c->comm), loop(c->loop), nranks(c->nranks), rank(c->rank), p2p_ready(c->p2p.ready)
+    {
+        c->comm = nullptr; c->loop = nullptr; c->nranks = 1; c->rank = 0; c->p2p.ready = false;
+    }
+    ~jch_comm_off()
+    {
+        ctx->comm = comm; ctx->loop = loop; ctx->nranks = nranks; ctx->rank = rank;
+        ctx->p2p.ready = p2p_ready && !(ctx->p2p.host_status && *ctx->p2p.host_status != 0ull);   // (a timed-out inbox stays disabled: jch_p2p_check)
+    }
+    jch_comm_off(const jch_comm_off &) = delete;
+    jch_comm_off &operator=(const jch_comm_off &) = delete;
+};
 // all-reduce of the per-LV sweep output zt [nslice][ldz] (first m entries of every slice); *nslice_out = slices the
 // consumer has to add afterwards (1 when the transport summed them)
 int32_t jch_allreduce_slices(jch_ctx *ctx, double *zt, int m, int nslice, int ldz, int *nslice_out);

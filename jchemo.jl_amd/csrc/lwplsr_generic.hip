@@ -319,6 +319,7 @@ int32_t jch_lw_generic_fits_da(jch_ctx *ctx, const locw_args &g, const int *hcn)
     JCH_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the two host images go out of scope with this function)
     lw_one_fit fit(g, nlv_cap);
     lw_profiling_off quiet(ctx);
+    jch_comm_off local(ctx);     // the fits below are one rank's own: on a joined ctx they would all-reduce with the other ranks' queries
     for (int i = 0; i < m; ++i) {
         if (hinfo[(size_t)i]) continue;
         const int ql = nloc[(size_t)i];
@@ -359,6 +360,7 @@ int32_t jch_lw_generic_fits(jch_ctx *ctx, const locw_args &g, int64_t n, const i
     const int nlv_cap = std::min(std::min(nlv_req, p), k);
     lw_one_fit fit(g, nlv_cap);
     lw_profiling_off quiet(ctx);
+    jch_comm_off local(ctx);     // the fits below are one rank's own: on a joined ctx they would all-reduce with the other ranks' queries
     const int nloop = only ? n_only : m;
     for (int ii = 0; ii < nloop; ++ii) {
         const int i = only ? only[ii] : ii;

@@ -493,6 +493,10 @@ def lwplsravg_predict(obj: LwplsrAvg, X, *, seed=None, ctx: Optional[Context] = 
     q = ensure_mat(obj.Y).shape[1]
     if obj.typf == "shenk" and p <= 2048 and q <= 16 and rng[-1] <= 48 and locw_pspace_lds_bytes(k, p, q) <= 150 * 1024:
         return _lwplsravg_shenk_batched(obj, eng, X, k, rng, ctx)
+    if ctx is not None and getattr(ctx, "nranks", 1) > 1:
+        # the loop below fits `plsravg` per query through the collective entries (jch_plskern_fit, jch_col_stats, ...): on a joined ctx those
+        # would all-reduce with whatever the other ranks' queries are fitting (include/jchemo_hip.h, the joined ctx contract)
+        raise _lib.JchError(_lib.JCH_EINVAL, f"lwplsravg_predict: the per-query schedule is one rank only (communicator of {ctx.nranks})")
     res = lwplsr_predict(eng, X, nlv=0, ctx=ctx)                    # the search and the weights (level 0: the weighted means)
     m = X.shape[0]
     dev = _is_torch(obj.X)

@@ -1104,8 +1104,9 @@ def _run_sharded(J, fn_name, shards, nlv, scal, post=None, **kw):
 @pytest.mark.parametrize("alg", ["plskern", "plsnipals", "plssimp", "plsrosa", "plswold", "plskern_v2"])
 @pytest.mark.parametrize("cuts", [(0.5,), (0.3, 0.7), (0.002, 0.4, 0.75)])
 def test_row_sharded_fit_matches_unsharded(alg, cuts, J):
-    """rows sharded over 2-4 ranks (uneven shards, one of them smaller than nlv) must give the unsharded
-    result; every replicated output must be bit-identical on all ranks."""
+    """rows sharded over 2-4 ranks (uneven shards, the smallest 12 rows against nlv = 7: a shard below
+    min(p, nlv) is test_gpu_joined_ctx.py's small-shard case) must give the unsharded result; every replicated output
+    must be bit-identical on all ranks."""
     n, p, q, nlv = 6000, 140, 4, 7
     rng = np.random.default_rng(11)
     Lt = rng.standard_normal((n, 2 * nlv))
