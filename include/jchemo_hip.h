@@ -540,9 +540,18 @@ JCH_API int32_t jch_krr_solve(jch_ctx *ctx, int32_t loc, const double *Kd, int64
  *   mode JCH_FIR_SAME: p outputs, out[i, j] = sum_{t < f} taps[t] x[i, clamp(j + lo + t, 0, p - 1)] (replicate border), -(f - 1) <= lo <= 0
  *   (the window contains its output); any f, f > p included.  mode JCH_FIR_VALID: p - f + 1 outputs, lo == 0, f <= p, no clamping; in place
  *   the columns from p - f + 1 on keep their input values.  Taps that are exactly 0.0 are skipped (no 0 * Inf; fdif is one subtraction).
- *   Windows up to 57 run from a ring of the row's originals; wider ones from a copy of a bounded block of rows. */
+ *   Windows up to 57 run from a ring of the row's originals; wider ones from a copy of a bounded block of rows.
+ *   mode JCH_FIR_SAME | JCH_FIR_PER_COLUMN (`predict(::CalPds, X)`, src/calpds.jl:89-99, as one banded map): every output
+ *   column has taps and a constant of its own.  Table layout: taps is a HOST table of (f + 1) x p doubles, column-major with ld f + 1;
+ *   column j holds the f taps of output j followed by its constant c_j.  p outputs,
+ *     out[i, j] = (sum_{t < f} taps[t, j] x[i, clamp(j + lo + t, 0, p - 1)]) + c_j,   -(f - 1) <= lo <= 0, any f >= 1 (f > p included).
+ *   Summation order: the taps are summed in the order of t, starting from 0.0, and the constant is added last; a tap that is exactly 0.0 is
+ *   skipped (a zero-padded border window never multiplies a clamped column and never forms 0 * Inf).  JCH_FIR_PER_COLUMN is a flag ORed
+ *   into the mode: JCH_FIR_VALID | JCH_FIR_PER_COLUMN and every other value (2 and 3 are not modes) are JCH_EINVAL.  out == X, host
+ *   staging, the ring up to 57 taps and the row-block copy beyond are those of the uniform modes, whose code path and bits are unchanged. */
 #define JCH_FIR_SAME 0
 #define JCH_FIR_VALID 1
+#define JCH_FIR_PER_COLUMN 4   /* a flag, ORed into the mode; 2 and 3 are not modes */
 JCH_API int32_t jch_rows_standardize(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, int32_t cent, int32_t scal,
                                      double *out, int64_t ldo);
 JCH_API int32_t jch_rows_project_out(jch_ctx *ctx, int32_t loc, const double *X, int64_t n, int64_t p, int64_t ldx, const double *A, const double *V,

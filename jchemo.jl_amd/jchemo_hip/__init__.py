@@ -24,3 +24,5 @@ from .lwplsda import (LwplsdaPred, LwplsLda, LwplsQda, LwplsrS, Lwplsrda, Lwplsr
 from .viperm import PERM_QGROUP, PERM_SLICE_ROWS, Isel, Viperm, isel, isel_intervals, perm_fill, perm_score_sums, viperm  # noqa: F401
 from .plsavg import (LwplsdaAvg, LwplsrAvg, LwplsrAvgPred, lwplsravg_prepared_call, lwplsdaavg_predict, lwplsldaavg, lwplsqdaavg, lwplsravg, lwplsravg_predict, lwplsrdaavg, Plsdaavg, Plsravg, PlsravgCri, PlsravgShenk, PlsravgUnif, Plsrstack, findmax_cla, fweight, plsdaavg_predict, plsldaavg, plsqdaavg,  # noqa: F401
                      plsravg, plsravg_, plsravg_predict, plsrdaavg, row_resid_ss_lv, wshenk)
+from .caltransfer import (CalDs, CalPds, calds, calds_predict, calpds, calpds_predict, difmean, eposvd, mlr, mlr_, mlr_coef, mlr_predict, mlrchol, mlrchol_,  # noqa: F401
+                          mlrpinv, mlrpinv_, mlrpinvn, mlrpinvn_, mlrvec, mlrvec_, pds_table, pds_windows)

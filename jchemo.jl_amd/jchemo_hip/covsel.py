@@ -48,9 +48,11 @@ class Covsel:
 
 @dataclass
 class Mlr:
-    """The reference's `Mlr` as far as `covselr` uses it (src/mlr.jl): B (nlv x q) and int (1 x q) in the units of the raw Y."""
+    """The reference's `Mlr` (src/mlr.jl:1-5): B (p x q) and int (1 x q) in the units of the raw Y, and the normalised weights (None in
+    the record `covselr` builds, which never had any)."""
     B: np.ndarray
     int: np.ndarray
+    weights: Optional[np.ndarray] = None
 
 
 @dataclass

@@ -392,7 +392,11 @@ def _predict_range(fm: Plsr, X, lo: int, hi: int, ctx):
 
 def coef(fm: Plsr, *, nlv: Optional[int] = None):
     """src/plskern.jl:207-217 — (B p x q, int 1 x q); nlv = 0 gives B = 0.  p x q host glue.  Dkplsr: coef(object.fm)
-    (src/dkplsr.jl:146-148).  Kplsr: (beta = C[:, 1:nlv]', int = ymeans') (src/kplsr.jl:221-228).  Covselr: coef(object.fm)."""
+    (src/dkplsr.jl:146-148).  Kplsr: (beta = C[:, 1:nlv]', int = ymeans') (src/kplsr.jl:221-228).  Covselr: coef(object.fm).  Mlr:
+    src/mlr.jl:275-277 (caltransfer.mlr_coef)."""
+    if type(fm).__name__ == "Mlr":
+        from .caltransfer import mlr_coef
+        return mlr_coef(fm)
     if type(fm).__name__ == "Covselr":
         from .covsel import covselr_coef
         return covselr_coef(fm)
@@ -429,7 +433,14 @@ def predict(fm: Plsr, X, *, nlv: Union[None, int, Sequence[int]] = None, ctx: Op
     `rank` / `world` (kNN-LWPLSR only): split the queries over `world` replicas, see lwplsr_predict.
     A Covselr model: src/covselr.jl:61-64 (covselr_predict).  An Occsd, Occod or Occsdod model: src/occsd.jl:153-164, src/occod.jl:65-75,
     src/occsdod.jl:60-74; an Occstah model: src/occstah.jl:55-73 (occ_predict).  A Knnr or Knnda model: src/knnr.jl:137-169, src/knnda.jl:108-138; an
-    Occknndis or Occlknndis model: src/occknndis.jl:157-171, src/occlknndis.jl:173-199 (knn.py)."""
+    Occknndis or Occlknndis model: src/occknndis.jl:157-171, src/occlknndis.jl:173-199 (knn.py).  An Mlr, CalDs or CalPds model: src/mlr.jl:287-292,
+    src/calds.jl:74-76, src/calpds.jl:91-99 (caltransfer.py)."""
+    if type(fm).__name__ in ("Mlr", "CalDs", "CalPds"):
+        from . import caltransfer
+        kw = {} if nlv is None else {"nlv": nlv}
+        if type(fm).__name__ == "Mlr":
+            return caltransfer.mlr_predict(fm, X, ctx=ctx)
+        return (caltransfer.calds_predict if type(fm).__name__ == "CalDs" else caltransfer.calpds_predict)(fm, X, ctx=ctx, **kw)
     if type(fm).__name__ == "Covselr":
         from .covsel import covselr_predict
         return covselr_predict(fm, X, ctx=ctx)
